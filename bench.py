@@ -9,7 +9,7 @@ One "step" = one whole-slide prediction: every tile of the reference-ordered den
 ordered accumulate + argmax produce the int64 class map.  The slide is generated in HBM
 (closed form) before the timed region; nothing is read from the host inside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -75,7 +75,43 @@ def parse():
     ap.add_argument("--f32-steps", type=int, default=2, help="extra leg: whole slides in float32 (0 = skip)")
     ap.add_argument("--no-extra-legs", action="store_true", help="headline measurement only (profiling runs)")
     ap.add_argument("--p224-steps", type=int, default=2, help="extra leg: whole slides at the reference's 224 / 112 geometry (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (class map, per-tile logits) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: cap of all arrays together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each array as <out_dir>/<name>.npy in float32 (or float64 where float32 would not hold it exactly).  In the order given,
+    an array that does not fit the bytes left is replaced by a fixed sample: the elements at seeded random flat indices (sorted),
+    written beside it as <name>_index.npy (float64).  Returns {name: what was written} for the result line."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    left, written = DUMP_BYTES, {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.float64 or (a.dtype.kind in "iu" and a.size and max(abs(int(a.max())), abs(int(a.min()))) > 2 ** 24):
+            a = a.astype(np.float64)
+        else:
+            a = a.astype(np.float32)
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > left:
+            k = max(1, (left - 16 * 1024) // (a.itemsize + 8))   # values + float64 indices, .npy headers left over
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(out / f"{name}_index.npy", idx.astype(np.float64))
+            left -= idx.size * 8
+            a = a.reshape(-1)[idx]
+            entry["sampled"] = int(a.size)
+        np.save(out / f"{name}.npy", a)
+        left -= a.nbytes
+        written[name] = entry
+    return written
 
 
 def host_cores() -> int:
@@ -388,11 +424,12 @@ def main():
 
     exchange_events: list = []   # (start, end) HIP events around every all-gather of the timed region (world > 1)
 
-    def timed_predict(mdl, steps, warmup, micro_batch=None, sampler=None):
-        """(elapsed seconds for `steps` whole slides, dominant-kernel ms / flops / samples over the timed region, class map)"""
+    def timed_predict(mdl, steps, warmup, micro_batch=None, sampler=None, logits=False):
+        """(elapsed seconds for `steps` whole slides, dominant-kernel ms / flops / samples over the timed region, class map
+        [, logits]); `logits`: the last step's per-tile logits too (computed either way; only the returned tuple differs)"""
         def step():
             return predict_full_patched(sampler or smp, mdl, 5, downscale=args.downscale, micro_batch=micro_batch or args.micro_batch, streams=args.streams,
-                                        timing=exchange_events)
+                                        timing=exchange_events, return_logits=logits)
         for _ in range(warmup):
             step()
         fence()
@@ -408,12 +445,16 @@ def main():
         check(lib().dh_profile_stop(C.byref(k_ms), C.byref(k_flops), C.byref(k_n)), "dh_profile_stop")
         return el, k_ms.value, k_flops.value, int(k_n.value), cm
 
-    elapsed, k_ms_v, k_flops_v, k_n_v, cmap = timed_predict(model, args.steps, args.warmup)
+    elapsed, k_ms_v, k_flops_v, k_n_v, last = timed_predict(model, args.steps, args.warmup, logits=args.dump_outputs is not None)
+    cmap, tile_logits = last if args.dump_outputs is not None else (last, None)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     assert cmap.shape == (side // args.downscale, side // args.downscale)
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:   # every rank holds the same map and logits after the all-gather
+        dumped = dump_outputs(args.dump_outputs, {"logits": tile_logits.cpu().numpy(), "class_map": cmap.cpu().numpy()})
 
     # what RCCL saw (N > 1): every rank's device and tile range, gathered over the group itself
     ranks_seen = None
@@ -522,6 +563,8 @@ def main():
                          "avg_launch_us": 1e3 * k_ms_v / max(1, k_n_v),
                          "flops_per_launch": k_flops_v / max(1, k_n_v)},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": str(Path(args.dump_outputs).resolve()), "arrays": dumped}
         extra = world == 1 and not args.no_extra_legs
         if extra and args.f32_steps > 0 and args.dtype == "bf16":
             # the configuration north_star's "logits within 1e-4 of the CPU reference" belongs to: same slide, float32 MFMA
