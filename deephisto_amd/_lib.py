@@ -71,6 +71,12 @@ SIGNATURES = {
     "dh_grad_pack_bf16": (C.c_int, [_p, _p, _i64, _p]),
     "dh_grad_unpack_bf16": (C.c_int, [_p, _p, _i64, C.c_float, _p]),
     "dh_train2_backward_adam": (C.c_int, [_p, _p, C.c_float, C.c_float, C.c_float, C.c_float, _i64, _p]),
+    "dh_coverage_create": (C.c_int, [C.POINTER(_p), _i64, _i64, _i32, _i32, _i32, _i32, _p]),
+    "dh_coverage_step": (C.c_int, [_p, _p, _p, _i32, _i32, _p, _i32, _p]),
+    "dh_coverage_counters": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), _p]),
+    "dh_coverage_eligible_cells": (C.c_int, [_p, _p, _i32, C.POINTER(_i32), _p]),
+    "dh_coverage_read_map": (C.c_int, [_p, _p, _p]),
+    "dh_coverage_destroy": (None, [_p]),
     "dh_profile_start": (C.c_int, [_i32, _i32]),
     "dh_profile_stop": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }
@@ -103,6 +109,7 @@ DEBUG_SIGNATURES = {
     "dh_debug_bn_pool_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "dh_debug_stamps": (C.c_int, [_i32, _p]),
     "dh_debug_env_knobs": (C.c_int, [C.c_char_p, _i64]),
+    "dh_debug_coverage_set_map": (C.c_int, [_p, _p, _p]),
 }
 
 

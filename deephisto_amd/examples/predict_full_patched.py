@@ -6,7 +6,9 @@ downscale).process()`, `batch_predictor(patches, model, device)` and
 `predict_full_patched(...)`, the device-resident fast path used by bench.py:
 tile ranges are sharded over the ranks of a torch.distributed job (RCCL over
 xGMI), every rank runs fused gather+ResNet-18 on its range, per-tile logits are
-all-gathered, and the ordered accumulation + argmax run once.
+all-gathered, and the ordered accumulation + argmax run once; and
+`predict_random_patched(...)`, the same for the random sampler's branch (device
+coverage map, large forward launches, one ordered accumulation).
 """
 from __future__ import annotations
 
@@ -244,6 +246,80 @@ def predict_full_patched(sampler: FullImageDenseSampler, model: ResNet18HIP, n_c
     return (cmap, logits) if return_logits else cmap
 
 
+def predict_random_patched(sampler, model: ResNet18HIP, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
+                           return_canvas: bool = False, timing: dict | None = None):
+    """The reference's default branch (FullImageRndSampler through ImagePredictorPatched.process(),
+    predict_full_patched.py:40-63, 150-162) with the random sampler's device index logic and large forward launches.
+
+    The sampler's origin sequence does not depend on the model, so the batches are planned and stepped on a coverage
+    stream while `model.forward_tiles` runs over LARGE launches of the accumulated origins on the compute stream (4 096
+    tiles in bf16, 1 024 in float32: the dense path's micro-batches) behind an event: planning batch k+1 overlaps the
+    forward of earlier tiles, and the per-batch counter read-back never waits behind a forward.  All logits are
+    accumulated in sampler order with ONE ordered accumulate at the end.  Large and small launches give identical
+    logits, so the class map and canvas are bit-identical to the callback path under the same NumPy seed.
+    `timing` (a dict) receives n_batches, n_tiles, host_s (planning + stepping wall time) and wall_s.
+    Returns int64[h//d, w//d] on the device (and the float32 canvas when `return_canvas`)."""
+    import time
+
+    if not isinstance(model, ResNet18HIP):
+        raise TypeError("predict_random_patched needs a ResNet18HIP model (use ImagePredictorPatched for other modules)")
+    if not sampler.resident:
+        raise ValueError("predict_random_patched needs an HBM-resident slide (ONDISK_MULTIPROC: use ImagePredictorPatched)")
+    if getattr(sampler, "index_logic", None) != "device":
+        raise ValueError("predict_random_patched needs FullImageRndSampler(..., index_logic='device')")
+    t0 = time.perf_counter()
+    slide = sampler.data_device
+    dev, P, B = slide.device, sampler.patch_size, sampler.batch_size
+    mb = micro_batch or (4096 if getattr(model, "compute_dtype", "f32") == "bf16" else 1024)
+    cap = max(B, mb // B * B)                      # origins per launch group: whole batches
+    main = torch.cuda.current_stream(dev)
+    cov_stream = _side_stream(dev, "coverage")
+    cov_stream.wait_stream(main)                   # the slide / model state queued so far
+    model.eval()
+    model._ensure_handle()
+    chunks: list[torch.Tensor] = []                # int32[cap, 2] origin buffers (kept alive to the end)
+    logits: list[torch.Tensor] = []
+    hosts: list[np.ndarray] = []
+    fill = [cap]
+
+    def out(n):
+        if fill[0] + n > cap:
+            with torch.cuda.stream(cov_stream):    # allocated from the coverage stream's pool, read by the compute stream
+                chunks.append(torch.empty((cap, 2), dtype=torch.int32, device=dev))
+            chunks[-1].record_stream(main)
+            fill[0] = 0
+        t = chunks[-1][fill[0]:fill[0] + n]
+        fill[0] += n
+        return t, t.data_ptr()
+
+    def launch(o):
+        ev = torch.cuda.Event()
+        ev.record(cov_stream)
+        main.wait_event(ev)
+        with torch.cuda.stream(main):
+            for s0 in range(0, o.shape[0], mb):
+                logits.append(model.forward_tiles(slide, o[s0:s0 + mb], P))
+
+    n_batches, host_s = 0, 0.0
+    th = time.perf_counter()
+    for _, o_host, _filled in sampler._device_origin_batches(host_origins=True, out=out, stream=cov_stream):
+        hosts.append(o_host)
+        n_batches += 1
+        if fill[0] + B > cap:                      # the group is full: hand it to the compute stream
+            launch(chunks[-1][:fill[0]])
+    if fill[0] and fill[0] + B <= cap and chunks:  # the last, partial group
+        launch(chunks[-1][:fill[0]])
+    host_s = time.perf_counter() - th
+    origins = np.concatenate(hosts) if hosts else np.zeros((0, 2), np.int32)
+    with torch.cuda.stream(main):
+        lg = torch.cat(logits) if len(logits) > 1 else logits[0]
+        canvas, cmap = tiles.accumulate_logits(lg.contiguous(), origins, P, downscale, sampler.h, sampler.w)
+    if timing is not None:
+        torch.cuda.synchronize(dev)
+        timing.update(n_batches=n_batches, n_tiles=int(origins.shape[0]), host_s=host_s, wall_s=time.perf_counter() - t0)
+    return (cmap, canvas) if return_canvas else cmap
+
+
 def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int):
     """Logits of `origins` (this rank's range, reference order) when the slide is not resident: the tiles are
     grouped by tile row; the P-row strip of each group is read from the reader into a pinned buffer, uploaded
@@ -349,8 +425,9 @@ def main(argv=None, model=None):
     (dense branch, :165-167) stride 112; those are the defaults of the flags below.  The dense branch is the multi-GPU
     path: under `python -m torch.distributed.run --nproc-per-node N -m examples.predict_full_patched ...` every rank
     binds its GPU, joins the RCCL group, takes its contiguous tile range and the logits are exchanged with one
-    all-gather (`predict_full_patched`); rank 0 writes the three JPEGs.  `--random_sampler` keeps the reference's
-    default branch (`FullImageRndSampler` through `ImagePredictorPatched.process()`, single process).
+    all-gather (`predict_full_patched`); rank 0 writes the three JPEGs.  `--random_sampler` runs the reference's
+    default branch (`FullImageRndSampler`, single process): `predict_random_patched` for a resident slide and a ResNet18HIP
+    model, `ImagePredictorPatched.process()` with the per-batch callback for an injected foreign model or `--ondisk`.
     `--synthetic H W` runs on a closed-form slide when no .psi file / psimage is at hand; `--weights ''` = random init.
     `model`: an injected module (tests)."""
     import argparse
@@ -405,9 +482,13 @@ def main(argv=None, model=None):
                                    "the dense sampler is the multi-GPU path")
             smp = FullImageRndSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                       mode=mode, device=device)
-            pred = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),
-                                         batch_predictor=lambda patches: batch_predictor(patches, model, device),
-                                         anno=anno_dsc, layer=args.layer, downscale=args.downscale_vis, device=device).process()
+            if smp.resident and smp.index_logic == "device" and isinstance(model, ResNet18HIP):
+                pred = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis).cpu().numpy()
+            else:   # a foreign module or a slide streamed from disk: the reference's callback loop
+                pred = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),
+                                             batch_predictor=lambda patches: batch_predictor(patches, model, device),
+                                             anno=anno_dsc, layer=args.layer, downscale=args.downscale_vis,
+                                             device=device).process()
         else:
             smp = FullImageDenseSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                         mode=mode, stride=args.stride, device=device)

@@ -18,6 +18,8 @@ Documented deviations from the reference:
   a slide smaller than the patch raises ValueError (the reference yields negative origins);
   `mode` defaults to INMEMORY_SINGLEPROC (predict_full_patched.py:165-167 omits it);
   tensors from `generator_torch()` are on the sampler's device, not on the CPU;
+  FullImageRndSampler's device index logic refuses a coverage map with fewer than `batch_size` cells (ValueError;
+  the reference's top-up loop never ends on one);
   ONDISK_MULTIPROC keeps ONE reader open and reads patches / row strips on demand (pinned staging
   buffers, upload on a side stream) instead of a pool of worker processes that re-open the file per
   batch (:332-351, 406-423); read errors propagate instead of being printed and the batch dropped.
@@ -33,6 +35,7 @@ import torch
 
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, DH_LAYOUT_NHWC
+from ..coverage import CoveragePlanner
 from ..psimage_compat import Patch, open_slide
 
 
@@ -126,15 +129,20 @@ class FullImageRndSampler(_SlideHolder):
     """Coverage-driven random tile sampler -- drop-in for full_samplers.py:21-299.
 
     Keeps a `dh x dw` hit-count map at `speedup`x downscale and draws `batch_size` tile origins
-    per batch from the cells hit fewer than `dense_level` times, until every cell was hit.  The
-    index logic runs on the host and consumes the GLOBAL NumPy RNG with the reference's calls in
-    the reference's order (so `np.random.seed(s)` reproduces the reference's origins); pixels
-    stay in HBM (`DevicePatch`, `dh_tile_gather_raw`).  `generator_torch` yields the raw 0..255
-    floats like the reference (:286 has no /255)."""
+    per batch from the cells hit fewer than `dense_level` times, until every cell was hit.  Every random
+    number comes from the GLOBAL NumPy RNG with the reference's calls in the reference's order (so
+    `np.random.seed(s)` reproduces the reference's origins); pixels stay in HBM (`DevicePatch`,
+    `dh_tile_gather_raw`).  `generator_torch` yields the raw 0..255 floats like the reference (:286 has no /255).
+
+    `index_logic`: "device" keeps the map on the GPU (`tiles.CoverageMap`, csrc/coverage.hip) and plans each batch in
+    rank space on the host (`coverage.CoveragePlanner`: no whole-map scan per batch); "numpy" is the reference's
+    host NumPy logic; "auto" = "device" when the sampler's device is a GPU and `dense_level` is an integer >= 1.
+    Both give the same origins, filled ratios and RNG stream.  Deviation (device path only): a map with fewer than
+    `batch_size` cells raises ValueError (the reference's top-up loops forever)."""
 
     def __init__(self, psimage_path, layer: int, patch_size: int, batch_size: int,
                  mode: SamplerExecutionMode = SamplerExecutionMode.INMEMORY_SINGLEPROC,
-                 dense_level: int = 2, speedup: int = 16, device="cuda"):
+                 dense_level: int = 2, speedup: int = 16, device="cuda", index_logic: str = "auto"):
         self._open(psimage_path, layer, mode, device)
         self.dh, self.dw = self.h // speedup, self.w // speedup
         print(f"Image {self.h} x {self.w} at {speedup}x -> {self.dh} x {self.dw}")
@@ -143,9 +151,35 @@ class FullImageRndSampler(_SlideHolder):
         self._downscale = int(speedup)
         self.dense_level = dense_level
         self._filled_ratio = []
-        self._accum = None
+        self._accum_host = None
+        self._cov = None          # tiles.CoverageMap of the running device pass
+        self.planner = None       # coverage.CoveragePlanner of the running device pass (its .stats: paths taken)
         if self.h < self.patch_size or self.w < self.patch_size:
             raise ValueError(f"slide {self.h}x{self.w} is smaller than the patch {self.patch_size}")
+        if index_logic not in ("auto", "device", "numpy"):
+            raise ValueError(f"index_logic must be 'auto', 'device' or 'numpy' (got {index_logic!r})")
+        dl_ok = (isinstance(dense_level, (int, np.integer, float, np.floating)) and not isinstance(dense_level, bool)
+                 and float(dense_level).is_integer() and dense_level >= 1)
+        on_gpu = self.device.type == "cuda"
+        if index_logic == "auto":
+            index_logic = "device" if on_gpu and dl_ok else "numpy"
+        elif index_logic == "device" and not (on_gpu and dl_ok):
+            raise ValueError("index_logic='device' needs a GPU device and an integer dense_level >= 1")
+        if index_logic == "device" and self.dh * self.dw < self.batch_size:
+            raise ValueError(f"coverage map of {self.dh}x{self.dw} cells is smaller than the batch ({self.batch_size}): "
+                             "the reference's top-up would never end")
+        self.index_logic = index_logic
+
+    @property
+    def _accum(self):
+        """float32[dh, dw] host hit counts (the reference's attribute; materialised from the device map on access)."""
+        if self._cov is not None:
+            return self._cov.read_map().cpu().numpy()
+        return self._accum_host
+
+    @_accum.setter
+    def _accum(self, value):
+        self._accum_host = value
 
     def _calc_probmap(self):
         p = np.where(self._accum >= self.dense_level, 0, 1)
@@ -171,7 +205,8 @@ class FullImageRndSampler(_SlideHolder):
             self._accum[y // d:(y + s) // d, x // d:(x + s) // d] += 1
         return np.count_nonzero(self._accum) / self._accum.size
 
-    def _origin_batches(self):
+    def _numpy_origin_batches(self):
+        self._cov = None
         self._accum = np.zeros([self.dh, self.dw], dtype=np.float32)
         filled = 0
         while filled < 1:
@@ -180,6 +215,49 @@ class FullImageRndSampler(_SlideHolder):
             self._filled_ratio.append(filled)
             yield origins, filled
 
+    def _device_origin_batches(self, host_origins: bool, out=None, stream=None):
+        """Device index logic: yield (int32[B,2] device origins or None, int32[B,2] host origins or None, filled).
+
+        `out(B)` returns (tensor, device address) for a batch's origins (default: a fresh tensor on the current stream);
+        `stream`: the torch stream of the map's work (default: the current stream).  One host wait per batch: the
+        planner needs the map's counters before it can draw the next batch."""
+        B = self.batch_size
+        cov = tiles.CoverageMap(self.h, self.w, self.patch_size, self._downscale, int(self.dense_level), B,
+                                device=self.device, stream=stream)
+        self._cov = cov
+        self.planner = planner = CoveragePlanner(B, self._downscale, self.dh, self.dw)
+        filled, eligible = 0.0, cov.eligible
+        while filled < 1:
+            idx, explicit, jit = planner.plan(eligible, cov.eligible_cells)
+            if out is None:
+                o_dev = torch.empty((B, 2), dtype=torch.int32, device=self.device)
+                addr = o_dev.data_ptr()
+            else:
+                o_dev, addr = out(B)
+            cov.step(idx, explicit, jit, addr, host_origins)
+            nf, eligible, o_host = cov.counters()
+            filled = nf / cov.size
+            self._filled_ratio.append(filled)
+            yield o_dev, o_host, filled
+
+    def _origin_batches(self):
+        """(list of (y, x) host origins, filled) per batch, either index logic."""
+        if self.index_logic == "numpy":
+            yield from self._numpy_origin_batches()
+            return
+        for _, o_host, filled in self._device_origin_batches(host_origins=True):
+            yield [(int(y), int(x)) for y, x in o_host], filled
+
+    def _origin_batches_dev(self):
+        """(int32[B,2] device origins, int32[B,2] host origins or None, filled) per batch: on the device path the
+        origins stay on the device unless the slide is streamed from disk (the reader needs them on the host)."""
+        if self.index_logic == "numpy":
+            for origins, filled in self._numpy_origin_batches():
+                o = np.asarray(origins, dtype=np.int32).reshape(-1, 2)
+                yield torch.from_numpy(o).to(self.device), o, filled
+            return
+        yield from self._device_origin_batches(host_origins=not self.resident)
+
     def __iter__(self) -> Iterator[tuple[list[Patch], float]]:
         return self.generator()
 
@@ -187,28 +265,45 @@ class FullImageRndSampler(_SlideHolder):
         for origins, filled in self._origin_batches():
             yield [DevicePatch(self.layer, int(x), int(y), self.patch_size, self) for y, x in origins], filled
 
+    def _staged_image(self, o_host):
+        """ONDISK_MULTIPROC (full_samplers.py:237-262 reads every patch from the file): the batch's patches go from
+        the open reader into one pinned staging image [B*P, P, 3] on the device, plus the staging origins."""
+        P, B = self.patch_size, len(o_host)
+        pinned = torch.empty((B * P, P, 3), dtype=torch.uint8).pin_memory()
+        buf = pinned.numpy()
+        for j, (y, x) in enumerate(o_host):
+            buf[j * P:(j + 1) * P] = self.read_region(int(y), int(x), int(y) + P, int(x) + P)
+        img = pinned.to(self.device, non_blocking=True)
+        so = torch.stack([torch.arange(B, dtype=torch.int32) * P, torch.zeros(B, dtype=torch.int32)], 1).to(self.device)
+        return img, so
+
     def generator_torch(self) -> Iterator[tuple[torch.Tensor, torch.Tensor, float]]:
         """(features f32[B,P,P,3] with the RAW 0..255 values -- no /255 here, full_samplers.py:286 --,
         coords f32[B,2] (y,x), filled ratio)."""
         P = self.patch_size
         if not self.resident:
-            # ONDISK_MULTIPROC (full_samplers.py:237-262 reads every patch from the file): the batch's patches go from
-            # the open reader into one pinned staging image [B*P, P, 3] and are cut from it on the GPU
-            for origins, filled in self._origin_batches():
-                B = len(origins)
-                pinned = torch.empty((B * P, P, 3), dtype=torch.uint8).pin_memory()
-                buf = pinned.numpy()
-                for j, (y, x) in enumerate(origins):
-                    buf[j * P:(j + 1) * P] = self.read_region(int(y), int(x), int(y) + P, int(x) + P)
-                img = pinned.to(self.device, non_blocking=True)
-                so = torch.stack([torch.arange(B, dtype=torch.int32) * P, torch.zeros(B, dtype=torch.int32)], 1).to(self.device)
-                o_dev = torch.tensor(np.asarray(origins), dtype=torch.int32, device=self.device)
+            for o_dev, o_host, filled in self._origin_batches_dev():
+                img, so = self._staged_image(o_host)
                 yield tiles.gather_tiles_raw(img, so, P), tiles.tile_coords(o_dev), filled
             return
         slide = self.data_device
-        for origins, filled in self._origin_batches():
-            o_dev = torch.tensor(origins, dtype=torch.int32, device=slide.device)
+        for o_dev, _, filled in self._origin_batches_dev():
             yield tiles.gather_tiles_raw(slide, o_dev, P), tiles.tile_coords(o_dev), filled
+
+    def generator_device(self, layout: int = DH_LAYOUT_NCHW, dtype=torch.float32
+                         ) -> Iterator[tuple[torch.Tensor, torch.Tensor, float]]:
+        """(tiles on device in `layout`/`dtype` with values k/255, int32[B,2] device origins, filled ratio) --
+        the counterpart of FullImageDenseSampler.generator_device; the origins never leave the device on the
+        device path of a resident slide."""
+        P = self.patch_size
+        if not self.resident:
+            for o_dev, o_host, filled in self._origin_batches_dev():
+                img, so = self._staged_image(o_host)
+                yield tiles.gather_tiles(img, so, P, layout, dtype, check_bounds=False), o_dev, filled
+            return
+        slide = self.data_device
+        for o_dev, _, filled in self._origin_batches_dev():
+            yield tiles.gather_tiles(slide, o_dev, P, layout, dtype, check_bounds=False), o_dev, filled
 
 
 class FullImageDenseSampler(_SlideHolder):

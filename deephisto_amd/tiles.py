@@ -222,3 +222,91 @@ def overlay_blend(img: torch.Tensor, colored: torch.Tensor, alpha: float = 0.6) 
     check(lib().dh_overlay_blend(img.data_ptr(), colored.data_ptr(), img.numel(), float(alpha), out.data_ptr(),
                                  _stream(img.device)), "dh_overlay_blend")
     return out
+
+
+class CoverageMap:
+    """The device coverage map of FullImageRndSampler (`dh_coverage_*`, csrc/coverage.hip): int32 hit counts [dh, dw]
+    at 1/speedup scale, rank -> cell -> origin -> hits per batch.  The narrow interface of coverage.CoveragePlanner:
+    `eligible`, `filled`, `size`, `eligible_cells()`, `step(...)` + `counters()`.  Calls go on `stream` (a torch
+    stream; default: the device's current stream at construction)."""
+
+    def __init__(self, h: int, w: int, patch: int, speedup: int, dense_level: int, max_batch: int, device="cuda",
+                 stream: torch.cuda.Stream | None = None):
+        self.device = torch.device(device)
+        self.h, self.w, self.P, self.d, self.dl = int(h), int(w), int(patch), int(speedup), int(dense_level)
+        self.dh, self.dw = self.h // self.d, self.w // self.d
+        self.size = self.dh * self.dw
+        self.max_batch = int(max_batch)
+        self.stream = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._h = None
+        handle = C.c_void_p()
+        check(lib().dh_coverage_create(C.byref(handle), self.h, self.w, self.P, self.d, self.dl, self.max_batch,
+                                       self._s()), "dh_coverage_create")
+        self._h = handle
+        self.filled, self.eligible = 0, self.size
+        self._last_n, self._last_host = 0, False
+        self._host = np.empty((self.max_batch, 2), np.int32)
+        self._cells = np.empty(self.max_batch, np.int32)
+
+    def _s(self) -> C.c_void_p:
+        return C.c_void_p(self.stream.cuda_stream)
+
+    def step(self, idx, explicit: bool, jitter, origins_dev: int | None = None, host_origins: bool = False):
+        """Queue one batch: idx int[n] ranks among the eligible cells (or flat cells when `explicit`), jitter int[n, 2];
+        the origins go to the device address `origins_dev` (int32[n, 2]; None: not kept).  Read with counters()."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        jit = np.ascontiguousarray(jitter, dtype=np.int32).reshape(-1)
+        n = idx.size
+        if jit.size != 2 * n:
+            raise ValueError(f"{n} cells but {jit.size} jitter values")
+        check(lib().dh_coverage_step(self._h, idx.ctypes.data_as(C.c_void_p), jit.ctypes.data_as(C.c_void_p), n,
+                                     1 if explicit else 0, origins_dev, 1 if host_origins else 0, self._s()),
+              "dh_coverage_step")
+        self._last_n, self._last_host = n, host_origins
+
+    def counters(self):
+        """(filled, eligible, int32[n, 2] host origins of the last step or None); waits for the last step's read-back."""
+        f, e = C.c_int64(), C.c_int64()
+        want = self._last_host and self._last_n > 0
+        check(lib().dh_coverage_counters(self._h, C.byref(f), C.byref(e),
+                                         self._host.ctypes.data_as(C.c_void_p) if want else None), "dh_coverage_counters")
+        self.filled, self.eligible = f.value, e.value
+        return self.filled, self.eligible, (self._host[:self._last_n].copy() if want else None)
+
+    def eligible_cells(self) -> np.ndarray:
+        """Sorted flat indices of the cells hit fewer than dense_level times (only while there are at most max_batch)."""
+        n = C.c_int32()
+        check(lib().dh_coverage_eligible_cells(self._h, self._cells.ctypes.data_as(C.c_void_p), self.max_batch,
+                                               C.byref(n), self._s()), "dh_coverage_eligible_cells")
+        return self._cells[:n.value].astype(np.int64)
+
+    def read_map(self) -> torch.Tensor:
+        """float32[dh, dw] copy of the counts on the device (ordered after every queued step)."""
+        out = torch.empty((self.dh, self.dw), dtype=torch.float32, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            check(lib().dh_coverage_read_map(self._h, out.data_ptr(), self._s()), "dh_coverage_read_map")
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return out
+
+    def set_map(self, counts: np.ndarray):
+        """Test hook (dh_debug_coverage_set_map): replace the counts by int32[dh, dw] and recount."""
+        a = np.ascontiguousarray(counts, dtype=np.int32)
+        if a.shape != (self.dh, self.dw):
+            raise ValueError(f"map must be [{self.dh}, {self.dw}]")
+        check(lib().dh_debug_coverage_set_map(self._h, a.ctypes.data_as(C.c_void_p), self._s()), "dh_debug_coverage_set_map")
+        self._last_n = 0
+        f, e = C.c_int64(), C.c_int64()
+        check(lib().dh_coverage_counters(self._h, C.byref(f), C.byref(e), None), "dh_coverage_counters")
+        self.filled, self.eligible = f.value, e.value
+
+    def close(self):
+        if self._h is not None:
+            lib().dh_coverage_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -251,6 +251,40 @@ int dh_train2_adam_step(dh_train2* net, float lr, float beta1, float beta2, floa
  * engine's side stream.  Bit-identical to dh_train2_backward + dh_train2_adam_step; refused while gradient buckets are armed. */
 int dh_train2_backward_adam(dh_train2* net, const float* dlogits_dev, float lr, float beta1, float beta2, float eps, int64_t step,
                             void* stream);
+/* ---- f1: coverage map of FullImageRndSampler (patch_samplers/full_samplers.py:63-153) ---------------------------
+ * The reference keeps a float hit-count map at 1/speedup scale and, per batch, draws B tile origins from the cells hit
+ * fewer than dense_level times (np.random.choice over the whole map), until every cell was hit.  The host planner
+ * (deephisto_amd/coverage.py) draws every random number in the reference's order and reduces the choice to RANKS among
+ * the eligible cells in row-major order; this handle owns the int32 map [dh][dw] (dh = h / speedup, dw = w / speedup)
+ * and turns ranks into cells, origins and hits.  One handle per sampler; its calls are not thread-safe.
+ *   create         : zeroed map; dense_level >= 1; 1 <= max_batch <= 4096 and max_batch <= dh*dw (the reference's
+ *                    top-up never ends on a smaller map).  Asynchronous on `stream`.
+ *   step           : one batch of n <= max_batch tiles.  idx_host: int32[n] ranks in [0, eligible) (explicit_cells = 0)
+ *                    or flat cell indices in [0, dh*dw) (explicit_cells != 0: the forced top-up path);
+ *                    jitter_host: int32[n][2] (jy, jx) in [0, speedup).  Origin k =
+ *                    clamp((cell // dw - P//speedup//2) * speedup + jy, 0, h-P), same for x with cell % dw
+ *                    (full_samplers.py:144-153); written as int32[n][2] (y, x) to origins_dev (may be NULL), then every
+ *                    origin adds 1 over [y//d, (y+P)//d) x [x//d, (x+P)//d) (duplicates included; integer atomics).
+ *                    Ranks / cells / jitter go up in one staged copy, the counters (and the origins when host_origins
+ *                    != 0) come back in one copy; nothing is synchronised except the previous step's read-back (the
+ *                    host arrays are consumed before the call returns).
+ *   counters       : waits for the last step's read-back: *filled = cells hit at least once, *eligible = cells hit
+ *                    fewer than dense_level times; origins_host (may be NULL; the last step must have asked for host
+ *                    origins): int32[n][2] of the last step.
+ *   eligible_cells : the rare top-up path: the (at most max_batch) eligible cells as sorted flat indices in
+ *                    cells_host[cap], count in *n_out; synchronises `stream`.
+ *   read_map       : float32[dh][dw] copy of the counts into map_dev (the reference's `_accum`).  Asynchronous.
+ *   destroy        : waits for the device, frees everything (NULL is a no-op). */
+typedef struct dh_coverage dh_coverage;
+int dh_coverage_create(dh_coverage** out, int64_t h, int64_t w, int32_t patch, int32_t speedup, int32_t dense_level,
+                       int32_t max_batch, void* stream);
+int dh_coverage_step(dh_coverage* cov, const int32_t* idx_host, const int32_t* jitter_host, int32_t n, int32_t explicit_cells,
+                     int32_t* origins_dev, int32_t host_origins, void* stream);
+int dh_coverage_counters(dh_coverage* cov, int64_t* filled, int64_t* eligible, int32_t* origins_host);
+int dh_coverage_eligible_cells(dh_coverage* cov, int32_t* cells_host, int32_t cap, int32_t* n_out, void* stream);
+int dh_coverage_read_map(dh_coverage* cov, float* map_dev, void* stream);
+void dh_coverage_destroy(dh_coverage* cov);
+
 /* ---- measurement -----------------------------------------------------------------
  * Times the dominant kernel (3x3 stride-1 conv, ~85 % of the model FLOPs) with HIP
  * events recorded on the launch stream around every `sample_every`-th launch (at most

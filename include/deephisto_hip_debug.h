@@ -111,6 +111,10 @@ int dh_debug_stamps(int32_t enable, unsigned long long* out64_host);
  * line per knob, NUL-terminated, into buf_host[cap]; INTEGRATION.md lists the same table (tests/test_abi.py compares them). */
 int dh_debug_env_knobs(char* buf_host, int64_t cap);
 
+/* dh_debug_coverage_set_map: replace a coverage handle's map by int32 host counts [dh][dw] (>= 0) and recount its per-chunk
+ * eligible counts, filled and eligible (tests of the rank -> cell and compaction kernels on crafted maps); synchronises `stream`. */
+int dh_debug_coverage_set_map(dh_coverage* cov, const int32_t* map_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
