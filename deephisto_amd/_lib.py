@@ -47,6 +47,12 @@ SIGNATURES = {
     "dh_resnet18_finalize": (C.c_int, [_p, _p]),
     "dh_resnet18_forward": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
     "dh_resnet18_forward_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p]),
+    "dh_resnet50_create": (C.c_int, [C.POINTER(_p), _i32]),
+    "dh_resnet50_destroy": (None, [_p]),
+    "dh_resnet50_set_param": (C.c_int, [_p, C.c_char_p, _p, _i64]),
+    "dh_resnet50_finalize": (C.c_int, [_p, _p]),
+    "dh_resnet50_forward": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),
+    "dh_resnet50_forward_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p]),
     "dh_resnet18_train_begin": (C.c_int, [_p, _i64, _i32, _p]),
     "dh_resnet18_train_end": (C.c_int, [_p]),
     "dh_resnet18_forward_train": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),

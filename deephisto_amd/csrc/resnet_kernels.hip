@@ -1104,13 +1104,13 @@ int run_conv(const ConvLayer& L, const void* in, const void* res, void* out, int
 }
 
 // fused bf16 stem (conv1 + bn1 + relu + maxpool) of `B` tiles -> channel-blocked [image][2][H2][W2][32] bf16
-int launch_stem_pool(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
+int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
                      const int32_t* yx, int B, int P, void* out, hipStream_t st) {
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
   StemPoolParams sp;
   DH_REQUIRE(!slide || slide_w < (1 << 24), "stem: slide rows of %lld pixels are not supported (< 2^24)", (long long)slide_w);
   sp.x_nchw = x; sp.slide = slide; sp.yx = yx; sp.row_bytes = slide_w * 3; sp.slide_bytes = slide_h * slide_w * 3;
-  sp.w = net->convs[0].w_dev; sp.scale = net->convs[0].scale_dev; sp.shift = net->convs[0].shift_dev; sp.out = out;
+  sp.w = stem.w_dev; sp.scale = stem.scale_dev; sp.shift = stem.shift_dev; sp.out = out;
   sp.B = B; sp.P = P; sp.Hc = H1; sp.Wc = H1; sp.Hp = H2; sp.Wp = H2;
   sp.tiles_y = (H2 + SP_PR - 1) / SP_PR; sp.tiles_x = (H2 + SP_PC - 1) / SP_PC;
   sp.nstrips = B * sp.tiles_x;                 // a strip = one image x 15 pooled columns, swept top to bottom
@@ -1165,7 +1165,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
 
   if constexpr (sizeof(T) == 2) {
     // bf16: fused stem + BN + ReLU + maxpool (persistent, weights resident in LDS), straight into bufA
-    if (int rc = launch_stem_pool(net, x, slide, slide_h, slide_w, yx, B, P, bufA, st)) return rc;
+    if (int rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, bufA, st)) return rc;
   } else {
   // stem
   {
@@ -1463,7 +1463,7 @@ extern "C" int dh_debug_stem_pool_bf16(dh_resnet18* net, const uint8_t* slide_de
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
   void* tmp = nullptr;
   DH_HIP(hipMalloc(&tmp, (size_t)n * H2 * H2 * 64 * 2));
-  int rc = launch_stem_pool(net, nullptr, slide_dev, slide_h, slide_w, yx_dev, (int)n, P, tmp, st);
+  int rc = launch_stem_pool(net->convs[0], nullptr, slide_dev, slide_h, slide_w, yx_dev, (int)n, P, tmp, st);
   if (!rc) {
     hipLaunchKernelGGL(blocked_to_nhwc_f32_kernel, dim3(1024), dim3(256), 0, st, static_cast<const __bf16*>(tmp), out_dev, n, H2 * H2);
     if (hipGetLastError() != hipSuccess) rc = DH_EHIP;
@@ -1523,3 +1523,5 @@ extern "C" int dh_debug_stamps(int32_t enable, unsigned long long* out64_host) {
 #include "bn_fold.inc"
 #include "gemm1x1.inc"
 #include "train2.inc"
+#include "gemm1x1_infer.inc"
+#include "resnet50_infer.inc"

@@ -23,7 +23,7 @@ import os
 
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, check, lib
-from ..models.patch_cls_simple.model import ResNet18HIP, get_model
+from ..models.patch_cls_simple.model import ResNet18HIP, ResNet50HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..psimage_compat import Patch, open_slide
 
@@ -112,12 +112,54 @@ def batch_predictor(patches: list[Patch], model, device) -> np.ndarray:
     return out.detach().cpu().numpy()
 
 
-def load_model(weights_path, device, compute_dtype: str = "f32") -> torch.nn.Module:
-    """predict_full_patched.py:116-126: 5-class model, state_dict loaded weights_only."""
-    model = get_model(n_classes=5, compute_dtype=compute_dtype).to(device)
-    model.load_state_dict(torch.load(weights_path, weights_only=True, map_location=device))
+ARCHS = ("resnet18", "resnet50")
+
+
+def detect_arch(state_dict) -> str:
+    """Backbone of a checkpoint from its keys: a bottleneck's third convolution (`layer1.0.conv3.weight`) means ResNet-50."""
+    return "resnet50" if "layer1.0.conv3.weight" in state_dict else "resnet18"
+
+
+def resolve_arch(arch, state_dict=None) -> str:
+    """`arch` None / "auto": read it from `state_dict` (ResNet-18 without one, as the reference); an explicit arch must match the
+    checkpoint's keys."""
+    if arch not in (None, "auto") and arch not in ARCHS:
+        raise ValueError(f"unknown architecture {arch!r} (auto, {', '.join(ARCHS)})")
+    found = detect_arch(state_dict) if state_dict is not None else None
+    if arch in (None, "auto"):
+        return found or "resnet18"
+    if found is not None and found != arch:
+        raise ValueError(f"--arch {arch} does not match the checkpoint, whose keys are those of a {found} "
+                         f"({'has' if found == 'resnet50' else 'lacks'} layer1.0.conv3.weight)")
+    return arch
+
+
+def load_model(weights_path, device, compute_dtype: str = "f32", arch=None) -> torch.nn.Module:
+    """predict_full_patched.py:116-126: 5-class model, state_dict loaded weights_only.  `arch` None / "auto" picks the backbone from
+    the checkpoint's keys (resolve_arch); ResNet-50 runs in bf16 whatever `compute_dtype` says (as get_model)."""
+    sd = torch.load(weights_path, weights_only=True, map_location=device)
+    model = get_model(n_classes=5, compute_dtype=compute_dtype, arch=resolve_arch(arch, sd)).to(device)
+    model.load_state_dict(sd)
     model.to(device).eval()
     return model
+
+
+def _tiles_entry(model):
+    """The model's fused gather + forward entry (ResNet-18's without a model that names one)."""
+    if model is not None and hasattr(model, "tiles_entry"):
+        return model.tiles_entry()
+    return lib().dh_resnet18_forward_tiles, "dh_resnet18_forward_tiles"
+
+
+def _default_micro_batch(model) -> int:
+    if hasattr(model, "default_micro_batch"):
+        return model.default_micro_batch()
+    return 4096 if getattr(model, "compute_dtype", "f32") == "bf16" else 1024
+
+
+def _check_tiles_model(model, what):
+    if not isinstance(model, (ResNet18HIP, ResNet50HIP)):
+        raise TypeError(f"{what} needs a ResNet18HIP or ResNet50HIP model (use ImagePredictorPatched for other modules)")
 
 
 def shard_range(n_items: int, world: int, rank: int) -> tuple[int, int]:
@@ -162,13 +204,15 @@ def exchange_logits(local: torch.Tensor, n_unique: int, group=None) -> torch.Ten
     return torch.cat(rows)
 
 
-def predict_full_patched(sampler: FullImageDenseSampler, model: ResNet18HIP, n_classes: int,
+def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
                          downscale: int = 16, micro_batch: int | None = None, group=None,
                          return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None):
     """Device-resident whole-slide prediction (rows a1-a8 end to end).
 
+    `model`: ResNet18HIP or ResNet50HIP; it names its own fused entry (`tiles_entry`) and launch size
+    (`default_micro_batch`: ResNet-18 4 096 bf16 / 1 024 float32, ResNet-50 1 024).
     Single process: every tile (padding duplicates included) goes through the fused
-    gather+ResNet-18 kernels in micro-batches, logits stay in HBM, one ordered
+    gather+network kernels in micro-batches, logits stay in HBM, one ordered
     accumulate + argmax.  Under torch.distributed (one process per GPU, backend
     "nccl" = RCCL): rank r takes the contiguous range shard_range(n_unique, world, r)
     of the reference-ordered origin list, logits are exchanged with ONE all-gather
@@ -191,7 +235,7 @@ def predict_full_patched(sampler: FullImageDenseSampler, model: ResNet18HIP, n_c
     # tiles per kernel launch (independent of the sampler's batch size).  bf16: 4 096, the library's maximum (a 64 x 64 x 64-channel
     # map of 4 096 tiles is 2 GiB).  float32: 1 024 -- the same map would be 4 GiB per tensor at 4 096 tiles, past the 32-bit byte
     # offsets of the conv schedule tables (the library refuses it)
-    mb = micro_batch or (4096 if getattr(model, "compute_dtype", "f32") == "bf16" else 1024)
+    mb = micro_batch or _default_micro_batch(model)
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0
@@ -218,15 +262,15 @@ def predict_full_patched(sampler: FullImageDenseSampler, model: ResNet18HIP, n_c
     lanes = [main] + [_side_stream(dev, i) for i in range(1, len(handles))]
     for st in lanes[1:]:
         st.wait_stream(main)
-    fwd = lib().dh_resnet18_forward_tiles
+    fwd, fwd_name = _tiles_entry(model)
     if streamed:
-        _forward_streamed(sampler, handles[0], origins[lo:hi], local, n_classes, mb)
+        _forward_streamed(sampler, handles[0], origins[lo:hi], local, n_classes, mb, model)
     for k, s in enumerate(range(0, 0 if streamed else hi - lo, mb)):
         e = min(s + mb, hi - lo)
         lane = k % len(handles)
         check(fwd(handles[lane], slide.data_ptr(), sampler.h, sampler.w, o_dev.data_ptr() + 8 * s, e - s, P,
                   local.data_ptr() + 4 * n_classes * s, C.c_void_p(lanes[lane].cuda_stream)),
-              "dh_resnet18_forward_tiles")
+              fwd_name)
     for st in lanes[1:]:
         main.wait_stream(st)
     if distributed and timing is not None and local.is_cuda:
@@ -246,7 +290,7 @@ def predict_full_patched(sampler: FullImageDenseSampler, model: ResNet18HIP, n_c
     return (cmap, logits) if return_logits else cmap
 
 
-def predict_random_patched(sampler, model: ResNet18HIP, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
+def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
                            return_canvas: bool = False, timing: dict | None = None):
     """The reference's default branch (FullImageRndSampler through ImagePredictorPatched.process(),
     predict_full_patched.py:40-63, 150-162) with the random sampler's device index logic and large forward launches.
@@ -261,8 +305,7 @@ def predict_random_patched(sampler, model: ResNet18HIP, n_classes: int, downscal
     Returns int64[h//d, w//d] on the device (and the float32 canvas when `return_canvas`)."""
     import time
 
-    if not isinstance(model, ResNet18HIP):
-        raise TypeError("predict_random_patched needs a ResNet18HIP model (use ImagePredictorPatched for other modules)")
+    _check_tiles_model(model, "predict_random_patched")
     if not sampler.resident:
         raise ValueError("predict_random_patched needs an HBM-resident slide (ONDISK_MULTIPROC: use ImagePredictorPatched)")
     if getattr(sampler, "index_logic", None) != "device":
@@ -270,7 +313,7 @@ def predict_random_patched(sampler, model: ResNet18HIP, n_classes: int, downscal
     t0 = time.perf_counter()
     slide = sampler.data_device
     dev, P, B = slide.device, sampler.patch_size, sampler.batch_size
-    mb = micro_batch or (4096 if getattr(model, "compute_dtype", "f32") == "bf16" else 1024)
+    mb = micro_batch or _default_micro_batch(model)
     cap = max(B, mb // B * B)                      # origins per launch group: whole batches
     main = torch.cuda.current_stream(dev)
     cov_stream = _side_stream(dev, "coverage")
@@ -320,11 +363,12 @@ def predict_random_patched(sampler, model: ResNet18HIP, n_classes: int, downscal
     return (cmap, canvas) if return_canvas else cmap
 
 
-def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int):
+def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int, model=None):
     """Logits of `origins` (this rank's range, reference order) when the slide is not resident: the tiles are
     grouped by tile row; the P-row strip of each group is read from the reader into a pinned buffer, uploaded
     on a side stream (two strip buffers: the disk read and the upload of strip k+1 run under the forward of strip k) and
-    serves as the 'slide' of dh_resnet18_forward_tiles; logits land at their reference-order positions."""
+    serves as the 'slide' of the model's tiles entry (dh_resnet18_forward_tiles without a model); logits land at their
+    reference-order positions."""
     dev, P, w = sampler.device, sampler.patch_size, sampler.w
     main = torch.cuda.current_stream(dev)
     copy_stream = torch.cuda.Stream(dev)
@@ -334,7 +378,7 @@ def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor,
     strip = [torch.empty((P, w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
     uploaded = [torch.cuda.Event() for _ in range(2)]
     consumed = [None, None]
-    fwd = lib().dh_resnet18_forward_tiles
+    fwd, fwd_name = _tiles_entry(model)
 
     def stage(k):
         b = k & 1
@@ -358,7 +402,7 @@ def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor,
         for s0 in range(0, len(idx), micro_batch):
             e0 = min(s0 + micro_batch, len(idx))
             check(fwd(handle, strip[b].data_ptr(), P, w, o_dev.data_ptr() + 8 * s0, e0 - s0, P,
-                      out.data_ptr() + 4 * n_classes * s0, C.c_void_p(main.cuda_stream)), "dh_resnet18_forward_tiles")
+                      out.data_ptr() + 4 * n_classes * s0, C.c_void_p(main.cuda_stream)), fwd_name)
         local[torch.from_numpy(idx).to(dev)] = out
         consumed[b] = torch.cuda.Event()
         consumed[b].record(main)
@@ -427,8 +471,9 @@ def main(argv=None, model=None):
     binds its GPU, joins the RCCL group, takes its contiguous tile range and the logits are exchanged with one
     all-gather (`predict_full_patched`); rank 0 writes the three JPEGs.  `--random_sampler` runs the reference's
     default branch (`FullImageRndSampler`, single process): `predict_random_patched` for a resident slide and a ResNet18HIP
-    model, `ImagePredictorPatched.process()` with the per-batch callback for an injected foreign model or `--ondisk`.
+    or ResNet50HIP model, `ImagePredictorPatched.process()` with the per-batch callback for an injected foreign model or `--ondisk`.
     `--synthetic H W` runs on a closed-form slide when no .psi file / psimage is at hand; `--weights ''` = random init.
+    `--arch auto` reads the backbone from the checkpoint (ResNet-50 when it has `layer1.0.conv3.weight`).
     `model`: an injected module (tests)."""
     import argparse
 
@@ -449,6 +494,8 @@ def main(argv=None, model=None):
     ap.add_argument("--random_sampler", action="store_true", default=False)
     ap.add_argument("--ondisk", action="store_true", help="SamplerExecutionMode.ONDISK_MULTIPROC: stream row strips")
     ap.add_argument("--compute_dtype", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--arch", choices=["auto", *ARCHS], default="auto",
+                    help="backbone; auto: from the checkpoint's keys (ResNet-18 with --weights ''); ResNet-50 is bf16")
     ap.add_argument("--out_dir", default="./output/")
     ap.add_argument("--no_visualizations", action="store_true")
     args = ap.parse_args(argv)
@@ -464,10 +511,10 @@ def main(argv=None, model=None):
             if device.type != "cuda":
                 raise RuntimeError("predict_full_patched runs on the GPU only (HIP kernels); no CPU fallback")
             if args.weights:
-                model = load_model(args.weights, device, args.compute_dtype)
+                model = load_model(args.weights, device, args.compute_dtype, arch=args.arch)
             else:
                 torch.manual_seed(0)   # the same random init on every rank
-                model = get_model(n_classes=5, compute_dtype=args.compute_dtype).to(device).eval()
+                model = get_model(n_classes=5, compute_dtype=args.compute_dtype, arch=resolve_arch(args.arch)).to(device).eval()
         anno_dsc = AnnoDescription.with_known_colors(KNOWN_COLORS)
         n_cls = len(anno_dsc.anno_classes)
         if args.synthetic is not None:
@@ -482,7 +529,7 @@ def main(argv=None, model=None):
                                    "the dense sampler is the multi-GPU path")
             smp = FullImageRndSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                       mode=mode, device=device)
-            if smp.resident and smp.index_logic == "device" and isinstance(model, ResNet18HIP):
+            if smp.resident and smp.index_logic == "device" and isinstance(model, (ResNet18HIP, ResNet50HIP)):
                 pred = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis).cpu().numpy()
             else:   # a foreign module or a slide streamed from disk: the reference's callback loop
                 pred = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),

@@ -359,6 +359,14 @@ class ResNet18HIP(nn.Module):
         self._buffers_dirty = True
         return out
 
+    def tiles_entry(self):
+        """(ctypes entry, its name) of the fused gather + forward from the uint8 slide (predict_full_patched's launches)."""
+        return lib().dh_resnet18_forward_tiles, "dh_resnet18_forward_tiles"
+
+    def default_micro_batch(self) -> int:
+        """Tiles per launch: 4 096 in bf16 (the library's maximum), 1 024 in float32 (32-bit offsets of the conv tables)."""
+        return 4096 if self.compute_dtype == "bf16" else 1024
+
     def forward_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int) -> torch.Tensor:
         """Fused gather + /255 + forward straight from the uint8 slide in HBM."""
         if self.training:

@@ -41,6 +41,7 @@ class Train2Engine:
         self.overlap_log = []      # (bucket, offset, count) in launch order of the last data-parallel backward (tests)
         self.ddp_wire = None        # gradient wire format of data-parallel steps: None = DH_DDP_WIRE (default f32), "f32", "bf16"
         self.fuse_optimizer = True  # single-rank train_step: dh_train2_backward_adam (False: backward, then adam_step; tests)
+        self.generation = 0         # bumped by every training forward: the library's parameters / running statistics may have moved
 
     # ---- handle and parameter traffic -------------------------------------------------------------------
     def _stream(self, dev):
@@ -78,6 +79,8 @@ class Train2Engine:
     # ---- forward / backward -----------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, training: bool, pull_stats: bool = True) -> torch.Tensor:
         h = self.ensure(x.device)
+        if training:
+            self.generation += 1
         n, p = int(x.shape[0]), int(x.shape[2])
         out = torch.empty((n, self.n_classes), dtype=torch.float32, device=x.device)
         check(lib().dh_train2_forward(h, x.data_ptr(), n, p, out.data_ptr(), 1 if training else 0, self._stream(x.device)),
@@ -233,12 +236,98 @@ class ResNet50HIP(nn.Module):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         self._engine = Train2Engine(self, "resnet50", self.n_classes)
+        self._lanes = []   # inference handles (dh_resnet50, BN folded): [handle, signature of the parameters it holds]
 
     def __del__(self):
         try:
             self._engine.release()
         except Exception:
             pass
+        try:
+            self._release_inference()
+        except Exception:
+            pass
+
+    # ---- inference engine (dh_resnet50: eval BN folded, one pass per convolution) ----------------------------
+    MAX_TILES = 1024   # DH_RESNET50_MAX_TILES: tiles per dh_resnet50_forward_tiles call
+
+    def tiles_entry(self):
+        """(ctypes entry, its name) of the fused gather + forward from the uint8 slide (predict_full_patched's launches)."""
+        return lib().dh_resnet50_forward_tiles, "dh_resnet50_forward_tiles"
+
+    def default_micro_batch(self) -> int:
+        return self.MAX_TILES
+
+    def _signature(self):
+        # state_dict() first pulls what a fused train_step left in the training engine; `generation` covers running statistics the
+        # training forwards wrote in place (no version bump)
+        sd = self.state_dict(keep_vars=True)
+        return (self._engine.generation,) + tuple((k, v.data_ptr(), v._version) for k, v in sd.items())
+
+    def _sync_handle(self, lane, sig):
+        if not lane[0]:
+            h = C.c_void_p()
+            check(lib().dh_resnet50_create(C.byref(h), self.n_classes), "dh_resnet50_create")
+            lane[0] = h
+        for name, t in self.state_dict().items():
+            if name.endswith("num_batches_tracked"):
+                continue
+            a = t.detach().to("cpu", torch.float32).contiguous()
+            check(lib().dh_resnet50_set_param(lane[0], name.encode(), a.data_ptr(), a.numel()), f"dh_resnet50_set_param({name})")
+        check(lib().dh_resnet50_finalize(lane[0], None), "dh_resnet50_finalize")
+        lane[1] = sig
+
+    def lane_handles(self, n: int):
+        """n inference handles holding the current parameters (re-synced whenever parameters or running statistics changed), each
+        with its own activation workspace, so that n launches can be in flight on n HIP streams."""
+        sig = self._signature()
+        while len(self._lanes) < max(1, n):
+            self._lanes.append([C.c_void_p(), None])
+        for lane in self._lanes[:max(1, n)]:
+            if lane[1] != sig:
+                self._sync_handle(lane, sig)
+        return [lane[0] for lane in self._lanes[:max(1, n)]]
+
+    def _ensure_handle(self):
+        return self.lane_handles(1)[0]
+
+    def _release_inference(self):
+        for lane in getattr(self, "_lanes", []):
+            if lane[0]:
+                lib().dh_resnet50_destroy(lane[0])
+        self._lanes = []
+
+    def forward_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int) -> torch.Tensor:
+        """Fused gather + /255 + eval forward straight from the uint8 slide in HBM (dh_resnet50_forward_tiles): one launch of at most
+        MAX_TILES tiles.  float32[n, n_classes] raw logits.  `forward` keeps the training engine's eval route."""
+        if self.training:
+            raise NotImplementedError("forward_tiles is an inference entry point; call .eval()")
+        if not (slide.is_cuda and origins_dev.is_cuda):
+            raise RuntimeError("slide and origins must live in GPU memory")
+        if slide.dtype != torch.uint8 or slide.dim() != 3 or not slide.is_contiguous():
+            raise ValueError("slide must be contiguous uint8[h, w, 3]")
+        if origins_dev.dtype != torch.int32 or origins_dev.dim() != 2 or origins_dev.shape[-1] != 2 or not origins_dev.is_contiguous():
+            raise ValueError("origins must be contiguous int32[n, 2]")
+        h = self._ensure_handle()
+        n = int(origins_dev.shape[0])
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=slide.device)
+        stream = C.c_void_p(torch.cuda.current_stream(slide.device).cuda_stream)
+        check(lib().dh_resnet50_forward_tiles(h, slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n,
+                                              int(patch), out.data_ptr(), stream), "dh_resnet50_forward_tiles")
+        return out
+
+    def forward_infer(self, x: torch.Tensor) -> torch.Tensor:
+        """float32[n, 3, P, P] in [0, 1] on the GPU -> logits through the inference engine (dh_resnet50_forward, one launch of at most
+        MAX_TILES tiles).  The same function as forward_tiles on the gathered tiles."""
+        if not x.is_cuda or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise ValueError("expected float32[n, 3, P, P] on the GPU")
+        x = x.detach().to(torch.float32).contiguous()
+        h = self._ensure_handle()
+        n = int(x.shape[0])
+        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=x.device)
+        check(lib().dh_resnet50_forward(h, x.data_ptr(), n, int(x.shape[2]), out.data_ptr(),
+                                        C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "dh_resnet50_forward")
+        return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda:

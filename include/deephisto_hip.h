@@ -167,6 +167,26 @@ int dh_resnet18_forward_tiles(dh_resnet18* net, const uint8_t* slide_dev, int64_
                               const int32_t* yx_dev, int64_t n, int32_t patch,
                               float* logits_dev, void* stream);
 
+/* ---- ResNet-50 patch classifier forward (bf16 inference) ------------------------------------
+ * The same entry points for the network get_model(..., arch="resnet50") returns (torchvision resnet50 v1.5 +
+ * fc[n_cls, 2048]), in eval mode: bf16 activations, bf16 MFMA with f32 accumulation, f32 logits.  finalize folds the
+ * eval BN (running statistics) into the convolution weights and a per-channel bias; every convolution is then one
+ * pass that writes its final activation (bias [+ identity], ReLU).  set_param takes torchvision state_dict names.
+ * P: 64 <= P <= 256, P % 32 == 0.  At most DH_RESNET50_MAX_TILES tiles per call (the activation maps stay within 2^31
+ * bytes); more is refused.  forward_tiles reads the n origins back and checks them against the slide (one
+ * synchronisation of `stream`) before any launch.  Per-tile logits do not depend on the launch size. */
+#define DH_RESNET50_MAX_TILES 1024
+typedef struct dh_resnet50 dh_resnet50;
+int dh_resnet50_create(dh_resnet50** out, int32_t n_classes);
+void dh_resnet50_destroy(dh_resnet50* net);
+int dh_resnet50_set_param(dh_resnet50* net, const char* name, const float* data_host, int64_t n_elem);
+int dh_resnet50_finalize(dh_resnet50* net, void* stream);
+int dh_resnet50_forward(dh_resnet50* net, const float* x_dev, int64_t n, int32_t patch, float* logits_dev,
+                        void* stream);
+int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64_t h, int64_t w,
+                              const int32_t* yx_dev, int64_t n, int32_t patch, float* logits_dev,
+                              void* stream);
+
 /* ---- a7: training step (float32) -------------------------------------------------------
  * Replaces, for the same network, models/patch_cls_simple/train.py:168-172:
  *   outputs = model(inputs); loss = criterion(outputs, labels); loss.backward(); optimizer.step()
