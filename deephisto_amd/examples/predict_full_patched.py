@@ -22,8 +22,9 @@ import ctypes as C
 import os
 
 from .. import tiles
-from .._lib import DH_LAYOUT_NCHW, check, lib
-from ..models.patch_cls_simple.model import ResNet18HIP, ResNet50HIP, get_model
+from .._lib import DH_LAYOUT_NCHW, check
+from ..models.patch_cls_simple.engine import ResNetHIP
+from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..psimage_compat import Patch, open_slide
 
@@ -144,24 +145,6 @@ def load_model(weights_path, device, compute_dtype: str = "f32", arch=None) -> t
     return model
 
 
-def _tiles_entry(model):
-    """The model's fused gather + forward entry (ResNet-18's without a model that names one)."""
-    if model is not None and hasattr(model, "tiles_entry"):
-        return model.tiles_entry()
-    return lib().dh_resnet18_forward_tiles, "dh_resnet18_forward_tiles"
-
-
-def _default_micro_batch(model) -> int:
-    if hasattr(model, "default_micro_batch"):
-        return model.default_micro_batch()
-    return 4096 if getattr(model, "compute_dtype", "f32") == "bf16" else 1024
-
-
-def _check_tiles_model(model, what):
-    if not isinstance(model, (ResNet18HIP, ResNet50HIP)):
-        raise TypeError(f"{what} needs a ResNet18HIP or ResNet50HIP model (use ImagePredictorPatched for other modules)")
-
-
 def shard_range(n_items: int, world: int, rank: int) -> tuple[int, int]:
     """Contiguous [lo, hi) share of `n_items` for `rank` (sizes differ by at most 1)."""
     base, rem = divmod(n_items, world)
@@ -235,7 +218,7 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     # tiles per kernel launch (independent of the sampler's batch size).  bf16: 4 096, the library's maximum (a 64 x 64 x 64-channel
     # map of 4 096 tiles is 2 GiB).  float32: 1 024 -- the same map would be 4 GiB per tensor at 4 096 tiles, past the 32-bit byte
     # offsets of the conv schedule tables (the library refuses it)
-    mb = micro_batch or _default_micro_batch(model)
+    mb = micro_batch or model.default_micro_batch()
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0
@@ -262,7 +245,7 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     lanes = [main] + [_side_stream(dev, i) for i in range(1, len(handles))]
     for st in lanes[1:]:
         st.wait_stream(main)
-    fwd, fwd_name = _tiles_entry(model)
+    fwd, fwd_name = model.tiles_entry()
     if streamed:
         _forward_streamed(sampler, handles[0], origins[lo:hi], local, n_classes, mb, model)
     for k, s in enumerate(range(0, 0 if streamed else hi - lo, mb)):
@@ -305,7 +288,8 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     Returns int64[h//d, w//d] on the device (and the float32 canvas when `return_canvas`)."""
     import time
 
-    _check_tiles_model(model, "predict_random_patched")
+    if not isinstance(model, ResNetHIP):
+        raise TypeError("predict_random_patched needs a ResNet18HIP or ResNet50HIP model (use ImagePredictorPatched for other modules)")
     if not sampler.resident:
         raise ValueError("predict_random_patched needs an HBM-resident slide (ONDISK_MULTIPROC: use ImagePredictorPatched)")
     if getattr(sampler, "index_logic", None) != "device":
@@ -313,13 +297,13 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     t0 = time.perf_counter()
     slide = sampler.data_device
     dev, P, B = slide.device, sampler.patch_size, sampler.batch_size
-    mb = micro_batch or _default_micro_batch(model)
+    mb = micro_batch or model.default_micro_batch()
     cap = max(B, mb // B * B)                      # origins per launch group: whole batches
     main = torch.cuda.current_stream(dev)
     cov_stream = _side_stream(dev, "coverage")
     cov_stream.wait_stream(main)                   # the slide / model state queued so far
     model.eval()
-    model._ensure_handle()
+    model.lane_handles(1)
     chunks: list[torch.Tensor] = []                # int32[cap, 2] origin buffers (kept alive to the end)
     logits: list[torch.Tensor] = []
     hosts: list[np.ndarray] = []
@@ -363,11 +347,11 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     return (cmap, canvas) if return_canvas else cmap
 
 
-def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int, model=None):
+def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int, model):
     """Logits of `origins` (this rank's range, reference order) when the slide is not resident: the tiles are
     grouped by tile row; the P-row strip of each group is read from the reader into a pinned buffer, uploaded
     on a side stream (two strip buffers: the disk read and the upload of strip k+1 run under the forward of strip k) and
-    serves as the 'slide' of the model's tiles entry (dh_resnet18_forward_tiles without a model); logits land at their
+    serves as the 'slide' of the model's tiles entry; logits land at their
     reference-order positions."""
     dev, P, w = sampler.device, sampler.patch_size, sampler.w
     main = torch.cuda.current_stream(dev)
@@ -378,7 +362,7 @@ def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor,
     strip = [torch.empty((P, w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
     uploaded = [torch.cuda.Event() for _ in range(2)]
     consumed = [None, None]
-    fwd, fwd_name = _tiles_entry(model)
+    fwd, fwd_name = model.tiles_entry()
 
     def stage(k):
         b = k & 1
@@ -529,7 +513,7 @@ def main(argv=None, model=None):
                                    "the dense sampler is the multi-GPU path")
             smp = FullImageRndSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                       mode=mode, device=device)
-            if smp.resident and smp.index_logic == "device" and isinstance(model, (ResNet18HIP, ResNet50HIP)):
+            if smp.resident and smp.index_logic == "device" and isinstance(model, ResNetHIP):
                 pred = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis).cpu().numpy()
             else:   # a foreign module or a slide streamed from disk: the reference's callback loop
                 pred = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),

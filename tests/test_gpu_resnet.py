@@ -147,6 +147,9 @@ def test_model_errors(dev):
         m(torch.zeros(1, 3, 64, 64))
     with pytest.raises(ValueError):
         m(torch.zeros(1, 4, 64, 64, device=dev))
+    slide = torch.zeros((256, 256, 3), dtype=torch.uint8, device=dev)
+    with pytest.raises(ValueError, match=r"int32\[n, 2\]"):                        # int32[n]: the kernel would read 2n values
+        m.forward_tiles(slide, torch.zeros(4, dtype=torch.int32, device=dev), 64)
 
 
 @pytest.mark.parametrize("dtype,P,n", [("bf16", 256, 70), ("bf16", 224, 300), ("f32", 128, 130), ("bf16", 256, 4096), ("f32", 256, 1024),

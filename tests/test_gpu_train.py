@@ -95,6 +95,31 @@ def test_three_adam_steps_torch_optimizer(dev):
         assert float(d.max()) <= 6e-4 and float(d.mean()) <= 2e-5, (k, float(d.max()), float(d.mean()))
 
 
+def test_autograd_step_after_fused_steps_starts_from_the_library(dev):
+    """Fused `train_step`s leave the library's masters newer than the nn.Parameters; the next autograd step (loss.backward();
+    torch.optim.Adam.step()) must step those newest values, so inserting a state_dict() call (which pulls them) before it changes
+    nothing."""
+    from deephisto_amd.models.patch_cls_simple.model import get_model
+    g = torch.Generator().manual_seed(13)
+    x = torch.rand(8, 3, 64, 64, generator=g).to(dev)
+    y = torch.randint(0, 5, (8,), generator=g).to(dev)
+    finals = []
+    for pull_first in (False, True):
+        torch.manual_seed(4)
+        m = get_model(5, "f32").to(dev).train()
+        for _ in range(2):
+            m.train_step(x, y, lr=1e-2)
+        if pull_first:
+            m.state_dict()
+        opt = torch.optim.Adam(m.parameters(), lr=1e-2)
+        opt.zero_grad()
+        F.cross_entropy(m(x), y).backward()
+        opt.step()
+        finals.append({k: v.clone() for k, v in m.state_dict().items()})
+    for k in finals[0]:
+        assert torch.equal(finals[0][k], finals[1][k]), k
+
+
 def test_fused_train_step_and_eval_roundtrip(dev):
     """HIP CrossEntropy + fused Adam (model.train_step), then eval-mode inference and a
     state_dict round trip through the oracle."""

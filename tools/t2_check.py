@@ -54,7 +54,7 @@ loss = F.cross_entropy(out, y.to(dev))
 loss.backward()
 torch.cuda.synchronize()
 # third oracle run: bf16-emulated with the ENGINE's ReLU patterns imposed
-eng = m._engine if arch == "resnet50" else m._engine2
+eng = m._engine
 masks = {}
 for name, a in acts.items():
     if "downsample" in name:
