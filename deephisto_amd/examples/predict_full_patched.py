@@ -27,6 +27,7 @@ from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..psimage_compat import Patch, open_slide
+from ..tissue import TissueFilter, fill_uncovered, score_tiles
 
 
 def _n_classes(anno) -> int:
@@ -189,7 +190,8 @@ def exchange_logits(local: torch.Tensor, n_unique: int, group=None) -> torch.Ten
 
 def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
                          downscale: int = 16, micro_batch: int | None = None, group=None,
-                         return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None):
+                         return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None,
+                         tissue: TissueFilter | None = None, tissue_info: dict | None = None):
     """Device-resident whole-slide prediction (rows a1-a8 end to end).
 
     `model`: ResNet18HIP or ResNet50HIP; it names its own fused entry (`tiles_entry`) and launch size
@@ -205,16 +207,36 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     `dedupe_padding=True` leaves the padding duplicates of the corner tile out of the accumulation (the reference adds them,
     predict_full_patched.py:49-54, which is the default here).
     `timing`: a list that receives one (start, end) pair of HIP events around the all-gather (bench.py's `allgather_ms`).
-    Returns int64[h//d, w//d] on the device (and the float32[n_padded, n_cls] logits).
+    `tissue`: a TissueFilter: the unique tiles are scored on the device and only the kept ones run through
+    the network (sharded over the ranks like the full list: every rank computes the same kept list); the ordered accumulation
+    runs over the kept tiles (the corner's padding duplicates follow the corner), then the map cells no kept tile covers get
+    `tissue.fill_class`.  The result is the unmasked computation with the rejected tiles' logits left out.  Needs a resident
+    dense sampler.  `tissue_info`: a dict that receives threshold, min_pixels, n_tiles, n_kept, kept (int64 indices into the
+    unique tiles) and, after Otsu, histogram.
+    Returns int64[h//d, w//d] on the device (and the float32[n_padded, n_cls] logits; rows of rejected tiles are NaN).
     """
     import torch.distributed as dist
 
     streamed = not sampler.resident          # ONDISK_MULTIPROC: row strips are uploaded as they are needed
+    if tissue is not None:
+        if not isinstance(sampler, FullImageDenseSampler):
+            raise ValueError("the tissue filter works on the dense sampler's grid only (not on the random sampler's branch)")
+        if streamed:
+            raise ValueError("the tissue filter needs an HBM-resident slide (ONDISK_MULTIPROC streams it)")
     slide = None if streamed else sampler.data_device
     dev = sampler.device if streamed else slide.device
     P = sampler.patch_size
     origins = sampler.origins                      # padded, reference order
     n_unique, n_padded = sampler.n_tiles, len(origins)
+    kept = None
+    if tissue is not None:
+        # the launch list becomes the kept tiles, in grid order (integer-exact: the same on every rank)
+        kept_idx_dev, kept_yx_dev, info = score_tiles(slide, torch.from_numpy(origins[:n_unique]).to(dev), P, tissue,
+                                                      origins[:n_unique])
+        kept = kept_idx_dev.cpu().numpy().astype(np.int64)
+        if tissue_info is not None:
+            tissue_info.update(info, kept=kept)
+    n_work = n_unique if kept is None else len(kept)
     # tiles per kernel launch (independent of the sampler's batch size).  bf16: 4 096, the library's maximum (a 64 x 64 x 64-channel
     # map of 4 096 tiles is 2 GiB).  float32: 1 024 -- the same map would be 4 GiB per tensor at 4 096 tiles, past the 32-bit byte
     # offsets of the conv schedule tables (the library refuses it)
@@ -222,7 +244,7 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
     rank = dist.get_rank(group) if distributed else 0
-    lo, hi = shard_range(n_unique, world, rank)
+    lo, hi = shard_range(n_work, world, rank)
     if hi - lo > mb:
         # near-equal launches instead of full ones plus a short tail, each a MULTIPLE OF 128 TILES (all but the last): the persistent
         # kernels run one tile per workgroup per iteration on 256 CUs (stem: 768 workgroups), and a layer has 8 / 4 / 2 / 2 conv tiles
@@ -234,8 +256,8 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
         mb = min(mb, max(128, -(-per // 128) * 128)) if mb >= 128 else per
         if os.environ.get("DH_MB_ALIGN") == "0":   # A/B: the round-3 rule (equal launches, any size)
             mb = per
-    o_dev = torch.from_numpy(origins[lo:hi]).to(dev)
-    per_rank = -(-n_unique // world)
+    o_dev = torch.from_numpy(origins[lo:hi]).to(dev) if kept is None else kept_yx_dev[lo:hi]
+    per_rank = -(-n_work // world)
     local = torch.zeros((per_rank, n_classes), dtype=torch.float32, device=dev)
     # parameters are synced to the native handles once; the loop below is launches only.
     # Micro-batches alternate over `streams` HIP streams (one workspace each) so that the short
@@ -256,21 +278,52 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
               fwd_name)
     for st in lanes[1:]:
         main.wait_stream(st)
-    if distributed and timing is not None and local.is_cuda:
+    if n_work == 0:   # every rank rejected every tile: nothing to exchange
+        logits_unique = local[:0]
+    elif distributed and timing is not None and local.is_cuda:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record(main)
-        logits_unique = exchange_logits(local, n_unique, group)
+        logits_unique = exchange_logits(local, n_work, group)
         ev[1].record(main)
         timing.append(ev)
     else:
-        logits_unique = exchange_logits(local, n_unique, group) if distributed else local[:n_unique]
+        logits_unique = exchange_logits(local, n_work, group) if distributed else local[:n_work]
     pad = n_padded - n_unique
+    if kept is not None:
+        return _finish_masked(sampler, logits_unique, kept, kept_yx_dev, n_classes, downscale, dedupe_padding, tissue,
+                              return_logits)
     logits = torch.cat([logits_unique, logits_unique[-1:].expand(pad, -1)]) if pad else logits_unique
     if dedupe_padding:
         _, cmap = tiles.accumulate_logits(logits_unique.contiguous(), origins[:n_unique], P, downscale, sampler.h, sampler.w)
     else:
         _, cmap = tiles.accumulate_logits(logits.contiguous(), origins, P, downscale, sampler.h, sampler.w)
     return (cmap, logits) if return_logits else cmap
+
+
+def _finish_masked(sampler, logits_kept, kept, kept_yx_dev, n_classes, downscale, dedupe_padding, tissue, return_logits):
+    """The tissue-filtered tail of predict_full_patched: ordered accumulation over the kept tiles (plus the corner's padding
+    duplicates when the corner is kept), argmax, fill of the uncovered cells; logits scattered back to the padded list."""
+    origins, n_unique, P = sampler.origins, sampler.n_tiles, sampler.patch_size
+    h, w, dev = sampler.h, sampler.w, logits_kept.device
+    pad = len(origins) - n_unique
+    k = len(kept)
+    if k == 0:   # all glass: no forward ran, every cell is uncovered
+        cmap = torch.zeros((h // downscale, w // downscale), dtype=torch.int64, device=dev)
+    else:
+        acc, yx = logits_kept, origins[:n_unique][kept]
+        if pad and not dedupe_padding and kept[-1] == n_unique - 1:   # the corner is the last unique tile
+            acc = torch.cat([acc, acc[-1:].expand(pad, -1)])
+            yx = np.concatenate([yx, origins[n_unique:]])
+        _, cmap = tiles.accumulate_logits(acc.contiguous(), yx, P, downscale, h, w)
+    fill_uncovered(cmap, kept_yx_dev, P, downscale, h, w, tissue.fill_class)
+    if not return_logits:
+        return cmap
+    logits = torch.full((len(origins), n_classes), float("nan"), dtype=torch.float32, device=dev)
+    if k:
+        logits[torch.from_numpy(kept).to(dev)] = logits_kept
+    if pad:
+        logits[n_unique:] = logits[n_unique - 1]
+    return cmap, logits
 
 
 def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
@@ -446,6 +499,33 @@ KNOWN_COLORS = {   # predict_full_patched.py:139-148
 }
 
 
+def _tissue_from_args(ap, args) -> TissueFilter | None:
+    """The TissueFilter of the --tissue flags, or None for `--tissue off`; a bad combination is an argparse error."""
+    from ..anno.utils import AnnoDescription
+
+    if args.tissue == "off":
+        return None
+    if args.random_sampler:
+        ap.error("--tissue works on the dense sampler's grid; it cannot be combined with --random_sampler")
+    if args.ondisk:
+        ap.error("--tissue needs the slide resident in HBM; it cannot be combined with --ondisk")
+    labels = {a.label: a.id for a in AnnoDescription.with_known_colors(KNOWN_COLORS).anno_classes}
+    if args.tissue_fill in labels:
+        fill = labels[args.tissue_fill]
+    elif args.tissue_fill == "-1":
+        fill = -1
+    else:
+        ap.error(f"--tissue_fill must be one of {', '.join(labels)} or -1, not {args.tissue_fill!r}")
+    try:
+        threshold = "otsu" if args.tissue == "otsu" else int(args.tissue)
+    except ValueError:
+        ap.error(f"--tissue must be off, otsu or an integer threshold in [0, 255], not {args.tissue!r}")
+    try:
+        return TissueFilter(threshold, args.tissue_min_fraction, fill)
+    except ValueError as e:
+        ap.error(f"--tissue {args.tissue} / --tissue_min_fraction {args.tissue_min_fraction}: {e}")
+
+
 def main(argv=None, model=None):
     """The reference's `__main__` (predict_full_patched.py:128-177) as a per-rank program.
 
@@ -458,6 +538,8 @@ def main(argv=None, model=None):
     or ResNet50HIP model, `ImagePredictorPatched.process()` with the per-batch callback for an injected foreign model or `--ondisk`.
     `--synthetic H W` runs on a closed-form slide when no .psi file / psimage is at hand; `--weights ''` = random init.
     `--arch auto` reads the backbone from the checkpoint (ResNet-50 when it has `layer1.0.conv3.weight`).
+    `--tissue otsu|<0..255>` classifies only the tiles that hold tissue (dense branch, resident slide; TissueFilter), with
+    `--tissue_min_fraction` and `--tissue_fill` (a class label, or -1 for no class) for the cells no kept tile covers.
     `model`: an injected module (tests)."""
     import argparse
 
@@ -482,7 +564,13 @@ def main(argv=None, model=None):
                     help="backbone; auto: from the checkpoint's keys (ResNet-18 with --weights ''); ResNet-50 is bf16")
     ap.add_argument("--out_dir", default="./output/")
     ap.add_argument("--no_visualizations", action="store_true")
+    ap.add_argument("--tissue", default="off", metavar="{off,otsu,<int>}",
+                    help="classify only tiles with tissue: chroma threshold 'otsu' or 0..255 (dense branch only)")
+    ap.add_argument("--tissue_min_fraction", type=float, default=0.25,
+                    help="share of a tile's pixels that must be tissue (0.25: a conventional default, not validated here)")
+    ap.add_argument("--tissue_fill", default="-1", help="class label for cells no kept tile covers, or -1 (no class)")
     args = ap.parse_args(argv)
+    tissue = _tissue_from_args(ap, args)
 
     rank, world, _dev_index, owned = init_from_env()   # binds the rank's GPU before any other GPU call
     ok = False
@@ -523,7 +611,11 @@ def main(argv=None, model=None):
         else:
             smp = FullImageDenseSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                         mode=mode, stride=args.stride, device=device)
-            pred = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis)   # sharded when world > 1
+            info: dict = {}
+            pred = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
+                                        tissue=tissue, tissue_info=info)
+            if tissue is not None and rank == 0:
+                print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
         if rank == 0 and not args.no_visualizations:
             src = img if isinstance(img, torch.Tensor) or not smp.resident else smp.data_device
             perform_and_save_visualizations(src, anno_dsc, pred, out_dir=Path(args.out_dir), stem=stem, device=device)

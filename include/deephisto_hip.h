@@ -305,6 +305,32 @@ int dh_coverage_eligible_cells(dh_coverage* cov, int32_t* cells_host, int32_t ca
 int dh_coverage_read_map(dh_coverage* cov, float* map_dev, void* stream);
 void dh_coverage_destroy(dh_coverage* cov);
 
+/* ---- t1: tissue mask for whole-slide prediction -------------------------------
+ * Not in the reference, which classifies every tile.  A pixel is tissue when its chroma
+ * max(R,G,B) - min(R,G,B) exceeds `threshold` (0..255); a tile is kept when its P x P window holds at
+ * least `min_pixels` tissue pixels.  Integer work only, so the result is exact.  slide_dev:
+ * uint8[h][w][3], 16-byte aligned.
+ * dh_tissue_histogram: hist_dev = uint64[256] chroma histogram of the whole slide (zeroed by the call).
+ * dh_tissue_tile_counts: counts_dev[i] = tissue pixels of the window at yx_dev[i] (int32[n][2], (y, x),
+ *   any origin with 0 <= y <= h-P, 0 <= x <= w-P; a device origin outside the slide gets -1).  bitmap_dev is
+ *   the caller's workspace of bitmap_words >= ceil(h*w / 64) uint64 words (one bit per pixel).  When
+ *   yx_host_check != NULL (the same n pairs on the host) every origin is checked before any launch.
+ * dh_tissue_select: kept_idx_dev = int32[k] indices i with counts_dev[i] >= min_pixels in increasing
+ *   order, kept_yx_dev (optional) = their origins int32[k][2]; both need capacity n.  status_dev: int32[2]
+ *   device workspace (k, origins counted -1).  With n_kept_host != NULL the call synchronises the stream,
+ *   stores k, and refuses a count of -1.
+ * dh_fill_uncovered: map_dev int64[h/d][w/d] cells outside the footprint [y/d, (y+P)/d) x [x/d, (x+P)/d)
+ *   (clipped) of every origin of yx_dev get fill_class; cover_dev: uint8[h/d * w/d] workspace. */
+int dh_tissue_histogram(const uint8_t* slide_dev, int64_t h, int64_t w, uint64_t* hist_dev, void* stream);
+int dh_tissue_tile_counts(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                          const int32_t* yx_host_check, int64_t n, int32_t patch, int32_t threshold,
+                          uint64_t* bitmap_dev, int64_t bitmap_words, int32_t* counts_dev, void* stream);
+int dh_tissue_select(const int32_t* counts_dev, const int32_t* yx_dev, int64_t n, int32_t min_pixels,
+                     int32_t* kept_idx_dev, int32_t* kept_yx_dev, int32_t* status_dev, int64_t* n_kept_host,
+                     void* stream);
+int dh_fill_uncovered(const int32_t* yx_dev, int64_t n, int32_t patch, int32_t downscale, int64_t h, int64_t w,
+                      int64_t fill_class, uint8_t* cover_dev, int64_t* map_dev, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------
  * Times the dominant kernel (3x3 stride-1 conv, ~85 % of the model FLOPs) with HIP
  * events recorded on the launch stream around every `sample_every`-th launch (at most
