@@ -113,7 +113,7 @@ int r50_gemm(const ConvLayer& L, const bf16_t* in, const bf16_t* res, bf16_t* ou
 }
 
 int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w, const int32_t* yx,
-                     int B, int P, float* logits, hipStream_t st) {
+                     int B, int P, float* logits, hipStream_t st, Tap* tap = nullptr) {
   const int H2 = P / 4;   // stem 7x7/2 -> P/2, maxpool 3x3/2 -> P/4 (P % 32 == 0)
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t px = (size_t)B * H2 * H2 * 2;   // bytes per channel of a stage-1 map
@@ -132,22 +132,28 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
   bf16_t* T2 = reinterpret_cast<bf16_t*>(base + 2 * big + t1);
   int rc;
   if ((rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, X, st))) return rc;
+  for (const char* nm : {"conv1", "maxpool"})   // the fused stem stores only the pooled map
+    if ((rc = tap_after<__bf16>(tap, nm, X, 64, H2, H2, 32, st))) return rc;
   int H = H2;
   for (const dh_resnet50::Blk& b : net->blocks) {
     const ConvLayer &c1 = net->convs[b.c1], &c2 = net->convs[b.c2], &c3 = net->convs[b.c3];
     const int Ho = (H - 1) / b.stride + 1;
     if ((rc = r50_gemm(c1, X, nullptr, T1, B, H, H, true, st))) return rc;
+    if ((rc = tap_after<__bf16>(tap, c1.name, T1, c1.cout, H, H, 32, st))) return rc;
     rc = b.stride == 1 ? launch_conv3x3<__bf16, 1>(c2, T1, nullptr, T2, B, H, H, true, st, Ho, Ho, nullptr, nullptr, true)
                        : launch_conv3x3<__bf16, 2>(c2, T1, nullptr, T2, B, H, H, true, st, Ho, Ho, nullptr, nullptr, true);
     if (rc) return rc;
+    if ((rc = tap_after<__bf16>(tap, c2.name, T2, c2.cout, Ho, Ho, 32, st))) return rc;
     const bf16_t* idt = X;
     if (b.ds >= 0) {
       if ((rc = r50_gemm(net->convs[b.ds], X, nullptr, D, B, H, H, false, st))) return rc;
+      if ((rc = tap_after<__bf16>(tap, net->convs[b.ds].name, D, c3.cout, Ho, Ho, 32, st))) return rc;
       idt = D;
     }
     // the join: conv3 + identity, ReLU.  Without a downsample the output overwrites the identity in place (every lane reads its residual
     // pieces before it stores them); with one, X is dead once conv1 and the downsample have run (stream order)
     if ((rc = r50_gemm(c3, T2, idt, X, B, Ho, Ho, true, st))) return rc;
+    if ((rc = tap_after<__bf16>(tap, c3.name, X, c3.cout, Ho, Ho, 32, st))) return rc;
     H = Ho;
   }
   hipLaunchKernelGGL(r50_head_kernel, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits);
@@ -274,4 +280,44 @@ extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide,
                "the %lldx%lld slide", (long long)i, y, x, P, (long long)h, (long long)w);
   }
   return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st);
+}
+
+// Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (Tap above), and a conv's
+// operands as the engine holds them after finalize: the folded, bf16-rounded weight, scale (1) and the folded bias.
+extern "C" int dh_debug_resnet50_forward_tap(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n,
+                                             int32_t P, const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev,
+                                             int64_t out_elems, float* logits_dev, void* stream) {
+  if (int rc = r50_check_forward(net, n, P, logits_dev, "resnet50 forward tap")) return rc;
+  DH_REQUIRE(n > 0 && slide && yx_dev && conv_name, "resnet50 forward tap: null argument or empty launch");
+  DH_REQUIRE(h >= P && w >= P, "resnet50 forward tap: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
+  DH_REQUIRE(tap_name_known(net, conv_name), "resnet50 forward tap: unknown conv '%s'", conv_name);
+  hipStream_t st = dh::as_stream(stream);
+  if (int rc = tap_check(sel_dev, k, n, out_dev, logits_dev, st)) return rc;
+  Tap tap;
+  tap.name = conv_name; tap.sel = sel_dev; tap.k = k; tap.out = out_dev; tap.out_elems = out_elems;
+  if (int rc = r50_forward_impl(net, nullptr, slide, h, w, yx_dev, (int)n, P, logits_dev, st, &tap)) return rc;
+  DH_REQUIRE(tap.hit, "resnet50 forward tap: '%s' is not stored by this engine", conv_name);
+  return DH_OK;
+}
+
+extern "C" int dh_debug_resnet50_operands(dh_resnet50* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
+                                          float* shift_host, int64_t c_elems) {
+  DH_REQUIRE(net && net->finalized && conv_name, "resnet50 operands: needs a finalized network");
+  for (const auto& c : net->convs) {
+    if (c.name != conv_name) continue;
+    if (c.ks != 1) return read_operands(c, 2, true, w_host, w_elems, scale_host, shift_host, c_elems);
+    DH_REQUIRE(w_host && scale_host && shift_host && w_elems == (int64_t)c.cout * c.cin && c_elems == c.cout,
+               "resnet50 operands %s: bad buffers", c.name.c_str());
+    std::vector<uint16_t> wb((size_t)w_elems);   // gemm1x1_infer.inc's W operand: plain bf16 [cout][cin]
+    DH_HIP(hipMemcpy(wb.data(), c.w_dev, wb.size() * 2, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < w_elems; ++i) {
+      const uint32_t u = (uint32_t)wb[i] << 16;
+      memcpy(&w_host[i], &u, 4);
+    }
+    DH_HIP(hipMemcpy(scale_host, c.scale_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
+    DH_HIP(hipMemcpy(shift_host, c.shift_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
+    return DH_OK;
+  }
+  dh::set_error("resnet50 operands: unknown conv '%s'", conv_name);
+  return DH_EINVAL;
 }

@@ -676,6 +676,61 @@ void pack_stem_pool_weights(const float* w, std::vector<uint8_t>& out) {
         }
 }
 
+// Inverses of the three packers (test hooks: the operand the kernels read, back as float32 [cout][cin][ks][ks]).  Slots that carry no
+// weight are skipped; an element no slot carries stays as the caller left it.
+inline float packed_value(const std::vector<uint8_t>& in, size_t o, int esz) {
+  float v;
+  if (esz == 4) { memcpy(&v, &in[o], 4); return v; }
+  uint16_t hb; memcpy(&hb, &in[o], 2);
+  const uint32_t u = (uint32_t)hb << 16;
+  memcpy(&v, &u, 4);
+  return v;
+}
+
+void unpack_conv_weights(const std::vector<uint8_t>& in, int cout, int cin, int ks, int esz, float* w) {
+  const int cpc = CHUNK_BYTES / esz, epl = 16 / esz, taps = ks * ks;
+  const int ncb = cout / 64, nch = cin / cpc;
+  size_t o = 0;
+  for (int cb = 0; cb < ncb; ++cb)
+    for (int ch = 0; ch < nch; ++ch)
+      for (int tap = 0; tap < taps; ++tap)
+        for (int k2 = 0; k2 < 2; ++k2)
+          for (int mt = 0; mt < 2; ++mt)
+            for (int l = 0; l < 64; ++l)
+              for (int e = 0; e < epl; ++e, o += esz) {
+                const int co = cb * 64 + mt * 32 + (l & 31);
+                const int ci = ch * cpc + k2 * (cpc / 2) + (l >> 5) * epl + e;
+                w[((size_t)co * cin + ci) * taps + tap] = packed_value(in, o, esz);
+              }
+}
+
+void unpack_stem_weights_f32(const std::vector<uint8_t>& in, float* w) {
+  size_t o = 0;
+  for (int kh = 0; kh < 7; ++kh)
+    for (int s = 0; s < 11; ++s)
+      for (int mt = 0; mt < 2; ++mt)
+        for (int l = 0; l < 64; ++l, o += 4) {
+          const int i = 2 * s + (l >> 5), co = mt * 32 + (l & 31);
+          if (i < 1 || i > 21) continue;
+          const int kw = (i - 1) / 3, c = (i - 1) % 3;
+          w[((size_t)(co * 3 + c) * 7 + kh) * 7 + kw] = packed_value(in, o, 4);
+        }
+}
+
+void unpack_stem_pool_weights(const std::vector<uint8_t>& in, float* w) {
+  size_t o = 0;
+  for (int ks = 0; ks < SP_KS; ++ks)
+    for (int mt = 0; mt < 2; ++mt)
+      for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j, o += 2) {
+          int kh, sl;
+          sp_kslot(ks, l >> 5, j, &kh, &sl);
+          if (kh < 0 || sl < 1 || sl > 21) continue;
+          const int co = mt * 32 + (l & 31), kw = (sl - 1) / 3, c = (sl - 1) % 3;
+          w[((size_t)(co * 3 + c) * 7 + kh) * 7 + kw] = packed_value(in, o, 2);
+        }
+}
+
 // Optional in-library timing of the dominant kernel (3x3 stride-1 conv): HIP events on
 // the launch stream around sampled launches, summed by dh_profile_stop (bench.py's
 // `roofline.achieved`).  Off by default; costs nothing when off.
@@ -1135,9 +1190,58 @@ int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide
   return DH_OK;
 }
 
+// Test hook of the inference forwards (dh_debug_resnet18_forward_tap, dh_debug_resnet50_forward_tap): right after the launch that stores
+// conv `name`'s output, that buffer's images sel[0..k) as float32 NCHW [k][C][H][W], stream-ordered before any later launch can overwrite
+// it.  A forward without a tap (nullptr) issues exactly its own launches.
+struct Tap {
+  std::string name;
+  const int32_t* sel = nullptr;   // device, checked against the launch's n by the hook
+  int k = 0;
+  float* out = nullptr;
+  int64_t out_elems = 0;
+  bool hit = false;
+};
+
+// in: [image][C/cp][H][W][cp] -- cp = 32: channel-blocked, 16: 16-channel planes, C: NHWC
+template <typename T>
+__global__ void tap_gather_kernel(const T* __restrict__ in, const int32_t* __restrict__ sel, int C, int cp, int64_t hw, int64_t total,
+                                  float* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t px = i % hw;
+    const int c = (int)((i / hw) % C);
+    const int64_t b = sel[i / hw / C];
+    out[i] = (float)in[((b * (C / cp) + c / cp) * hw + px) * cp + c % cp];
+  }
+}
+
+template <typename T>
+int tap_after(Tap* tap, const std::string& name, const void* buf, int C, int H, int W, int cp, hipStream_t st) {
+  if (!tap || name != tap->name) return DH_OK;
+  const int64_t total = (int64_t)tap->k * C * H * W;
+  DH_REQUIRE(total == tap->out_elems, "forward tap %s: the output holds %lld elements, [%d][%d][%d][%d] needs %lld", name.c_str(),
+             (long long)tap->out_elems, tap->k, C, H, W, (long long)total);
+  hipLaunchKernelGGL((tap_gather_kernel<T>), dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, st,
+                     static_cast<const T*>(buf), tap->sel, C, cp, (int64_t)H * W, total, tap->out);
+  DH_LAUNCH_CHECK();
+  tap->hit = true;
+  return DH_OK;
+}
+
+// Host checks of a tap request before any launch: k in [1, n], every sel in [0, n) (read back: one synchronisation of `st`)
+int tap_check(const int32_t* sel_dev, int32_t k, int64_t n, float* out_dev, const float* logits_dev, hipStream_t st) {
+  DH_REQUIRE(sel_dev && out_dev && logits_dev, "forward tap: null argument");
+  DH_REQUIRE(k > 0 && k <= n, "forward tap: k = %d selected images out of range [1, %lld]", k, (long long)n);
+  std::vector<int32_t> sel(k);
+  DH_HIP(hipMemcpyAsync(sel.data(), sel_dev, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+  DH_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < k; ++i)
+    DH_REQUIRE(sel[i] >= 0 && sel[i] < n, "forward tap: sel[%d] = %d outside the launch of %lld tiles", i, sel[i], (long long)n);
+  return DH_OK;
+}
+
 template <typename T>
 int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
-                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st) {
+                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st, Tap* tap = nullptr) {
   const int B = (int)n64;
   const int esz = (int)sizeof(T);
   const int H1 = (P + 6 - 7) / 2 + 1;       // stem out
@@ -1166,6 +1270,8 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
   if constexpr (sizeof(T) == 2) {
     // bf16: fused stem + BN + ReLU + maxpool (persistent, weights resident in LDS), straight into bufA
     if (int rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, bufA, st)) return rc;
+    for (const char* nm : {"conv1", "maxpool"})   // the fused stem stores only the pooled map
+      if (int rc = tap_after<T>(tap, nm, bufA, 64, H2, H2, 32, st)) return rc;
   } else {
   // stem
   {
@@ -1185,6 +1291,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
       hipLaunchKernelGGL((stem_kernel<T, false>), dim3(grid), dim3(256), lds, st, sp);
     }
     DH_LAUNCH_CHECK();
+    if (int rc = tap_after<T>(tap, "conv1", S, 64, H1, H1, 64, st)) return rc;
   }
   // maxpool
   {
@@ -1193,6 +1300,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
     hipLaunchKernelGGL((maxpool_kernel<T>), dim3(grid), dim3(256), 0, st, static_cast<const T*>(S),
                        static_cast<T*>(bufA), B, H1, H1, 64, H2, H2);
     DH_LAUNCH_CHECK();
+    if (int rc = tap_after<T>(tap, "maxpool", bufA, 64, H2, H2, 64, st)) return rc;
   }
   }
   // residual stages: X lives in bufA; T in bufB; downsample in bufC.  bf16 activations are channel-blocked
@@ -1216,12 +1324,14 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
         Ho = (H + 2 - 3) / 2 + 1; Wo = (W + 2 - 3) / 2 + 1;
         rc = launch_conv3x3<T, 2>(c1, X, nullptr, bufB, B, H, W, true, st, Ho, Wo, &net->convs[ci + 2], other, BLK, 0, 0, x16, false);
         if (rc) return rc;
+        if ((rc = tap_after<T>(tap, net->convs[ci + 2].name, other, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
         resid = other;
       } else {
         DH_REQUIRE(!x16, "resnet18 forward: only a downsample block reads 16-channel planes");
         rc = run_conv<T>(c1, X, nullptr, bufB, B, H, W, true, st, &Ho, &Wo, BLK);
         if (rc) return rc;
       }
+      if ((rc = tap_after<T>(tap, c1.name, bufB, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
       // the block that follows starts with a stride-2 conv on the wide kernel: this block's output goes out in 16-channel planes
       x16 = false;
       if (blk == 1 && s < 3) {
@@ -1236,6 +1346,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
       else if (x16) O = other;
       rc = run_conv<T>(c2, bufB, resid, O, B, Ho, Wo, true, st, &h2, &w2, BLK, x16);
       if (rc) return rc;
+      if ((rc = tap_after<T>(tap, c2.name, O, c2.cout, Ho, Wo, x16 ? 16 : BLK ? 32 : c2.cout, st))) return rc;
       X = O;
       H = Ho; W = Wo;
       ci += has_ds ? 3 : 2;
@@ -1471,6 +1582,65 @@ extern "C" int dh_debug_stem_pool_bf16(dh_resnet18* net, const uint8_t* slide_de
   }
   (void)hipFree(tmp);
   return rc;
+}
+
+namespace {
+// the stored activations a tap may name: every conv of the topology, and "maxpool" (the pooled stem output)
+template <typename Net>
+bool tap_name_known(const Net* net, const char* name) {
+  if (!strcmp(name, "maxpool")) return true;
+  for (const auto& c : net->convs)
+    if (c.name == name) return true;
+  return false;
+}
+
+// a conv's operands as the engine holds them: the packed weight read back from the device and unpacked, scale and shift (or 1 and the
+// folded bias) read back; synchronous
+int read_operands(const ConvLayer& c, int esz, bool fused_stem, float* w_host, int64_t w_elems, float* scale_host, float* shift_host,
+                  int64_t c_elems) {
+  DH_REQUIRE(w_host && scale_host && shift_host, "operands: null argument");
+  DH_REQUIRE(w_elems == (int64_t)c.cout * c.cin * c.ks * c.ks && c_elems == c.cout, "operands %s: buffers of %lld / %lld elements, "
+             "expected %lld / %d", c.name.c_str(), (long long)w_elems, (long long)c_elems, (long long)c.cout * c.cin * c.ks * c.ks, c.cout);
+  size_t bytes;
+  if (c.ks == 7) bytes = fused_stem ? (size_t)SP_WBYTES : (size_t)7 * 11 * 2 * 256;
+  else bytes = (size_t)(c.cout / 64) * (c.cin / (CHUNK_BYTES / esz)) * c.ks * c.ks * SLAB_TAP;
+  std::vector<uint8_t> packed(bytes);
+  DH_HIP(hipMemcpy(packed.data(), c.w_dev, bytes, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < w_elems; ++i) w_host[i] = NAN;   // an element no slot carries stays NaN
+  if (c.ks == 7 && fused_stem) unpack_stem_pool_weights(packed, w_host);
+  else if (c.ks == 7) unpack_stem_weights_f32(packed, w_host);
+  else unpack_conv_weights(packed, c.cout, c.cin, c.ks, esz, w_host);
+  DH_HIP(hipMemcpy(scale_host, c.scale_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
+  DH_HIP(hipMemcpy(shift_host, c.shift_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
+  return DH_OK;
+}
+}  // namespace
+
+extern "C" int dh_debug_resnet18_forward_tap(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n,
+                                             int32_t P, const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev,
+                                             int64_t out_elems, float* logits_dev, void* stream) {
+  if (int rc = check_forward_args(net, n, P, logits_dev)) return rc;
+  DH_REQUIRE(n > 0 && slide && yx_dev && conv_name, "resnet18 forward tap: null argument or empty launch");
+  DH_REQUIRE(h >= P && w >= P, "resnet18 forward tap: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
+  DH_REQUIRE(tap_name_known(net, conv_name), "resnet18 forward tap: unknown conv '%s'", conv_name);
+  hipStream_t st = dh::as_stream(stream);
+  if (int rc = tap_check(sel_dev, k, n, out_dev, logits_dev, st)) return rc;
+  Tap tap;
+  tap.name = conv_name; tap.sel = sel_dev; tap.k = k; tap.out = out_dev; tap.out_elems = out_elems;
+  const int rc = net->dtype == DH_DTYPE_F32 ? forward_impl<float>(net, nullptr, slide, h, w, yx_dev, n, P, logits_dev, st, &tap)
+                                            : forward_impl<__bf16>(net, nullptr, slide, h, w, yx_dev, n, P, logits_dev, st, &tap);
+  if (rc) return rc;
+  DH_REQUIRE(tap.hit, "resnet18 forward tap: '%s' is not stored by this engine", conv_name);
+  return DH_OK;
+}
+
+extern "C" int dh_debug_resnet18_operands(dh_resnet18* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
+                                          float* shift_host, int64_t c_elems) {
+  DH_REQUIRE(net && net->finalized && conv_name, "resnet18 operands: needs a finalized network");
+  for (const auto& c : net->convs)
+    if (c.name == conv_name) return read_operands(c, net->esz(), net->esz() == 2, w_host, w_elems, scale_host, shift_host, c_elems);
+  dh::set_error("resnet18 operands: unknown conv '%s'", conv_name);
+  return DH_EINVAL;
 }
 
 // ---------------------------------------------------------------------------

@@ -111,6 +111,25 @@ int dh_debug_stamps(int32_t enable, unsigned long long* out64_host);
  * line per knob, NUL-terminated, into buf_host[cap]; INTEGRATION.md lists the same table (tests/test_abi.py compares them). */
 int dh_debug_env_knobs(char* buf_host, int64_t cap);
 
+/* Per-layer taps of the inference engines.  dh_debug_*_forward_tap runs the launches of dh_*_forward_tiles for all n tiles and, right after
+ * the launch that stores conv `conv_name`'s output (a state_dict conv name; "maxpool" = the pooled stem output, which the fused bf16 stems
+ * also store under "conv1"; the float32 ResNet-18 stores "conv1" = relu(bn1(conv1)) before its pool), copies that stored activation of the
+ * images sel_dev[0..k) as float32 NCHW [k][C][H][W] into out_dev (out_elems = k*C*H*W), stream-ordered before any later launch overwrites
+ * it; logits_dev receives the logits of the same run.  Refused (dh_last_error) for an unknown name, k outside [1, n], or a sel outside
+ * [0, n) (read back: one synchronisation).  dh_debug_*_operands: conv `conv_name`'s operands as the engine holds them after finalize,
+ * read back from the device into host buffers: the weight unpacked to float32 [cout][cin][ks][ks] (bf16 engines: bf16-rounded;
+ * ResNet-50: BN folded, then rounded), scale and shift [cout] (ResNet-50: 1 and the folded bias); synchronous. */
+int dh_debug_resnet18_forward_tap(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n, int32_t P,
+                                  const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev, int64_t out_elems,
+                                  float* logits_dev, void* stream);
+int dh_debug_resnet50_forward_tap(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n, int32_t P,
+                                  const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev, int64_t out_elems,
+                                  float* logits_dev, void* stream);
+int dh_debug_resnet18_operands(dh_resnet18* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
+                               float* shift_host, int64_t c_elems);
+int dh_debug_resnet50_operands(dh_resnet50* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
+                               float* shift_host, int64_t c_elems);
+
 /* dh_debug_coverage_set_map: replace a coverage handle's map by int32 host counts [dh][dw] (>= 0) and recount its per-chunk
  * eligible counts, filled and eligible (tests of the rank -> cell and compaction kernels on crafted maps); synchronises `stream`. */
 int dh_debug_coverage_set_map(dh_coverage* cov, const int32_t* map_host, void* stream);

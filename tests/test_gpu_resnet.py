@@ -120,17 +120,28 @@ def test_resnet18_f32_batch64_and_determinism(dev):
     assert torch.equal(c, a[3:7])
 
 
-def test_resnet18_bf16_logits(dev):
+def _bf16_logit_error(dev, P):
+    """max |bf16 logit - float32 oracle logit| of six random P x P inputs, and the gate's scale max(1, max |logit|)."""
     oracle = oracle_net.seeded_model(321, 5, perturb_bn=True).eval()
     model = _hip_model(oracle, dev, "bf16")
     g = torch.Generator().manual_seed(2)
-    x = torch.rand(6, 3, 256, 256, generator=g)
+    x = torch.rand(6, 3, P, P, generator=g)
     with torch.no_grad():
         want = oracle(x)
     got = model(x.to(dev)).cpu()
-    scale = max(1.0, float(want.abs().max()))
-    err = float((got - want).abs().max())
+    return float((got - want).abs().max()), max(1.0, float(want.abs().max()))
+
+
+def test_resnet18_bf16_logits(dev):
+    err, scale = _bf16_logit_error(dev, 256)
     assert err <= 2e-2 * scale, f"bf16 logit error {err} at scale {scale}"
+
+
+@pytest.mark.parametrize("P", [224, 96])
+def test_resnet18_bf16_logits_reference_geometry(dev, P):
+    """The same gate at the reference's own patch size (224: 56 / 28 / 14 / 7 maps) and at the smallest maps (96: 3 x 3 in layer 4)."""
+    err, scale = _bf16_logit_error(dev, P)
+    assert err <= 2e-2 * scale, f"bf16 logit error {err} at scale {scale} (P = {P})"
 
 
 def test_model_errors(dev):
