@@ -9,14 +9,16 @@ One "step" = one whole-slide prediction: every tile of the reference-ordered den
 ordered accumulate + argmax produce the int64 class map.  The slide is generated in HBM
 (closed form) before the timed region; nothing is read from the host inside it.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task description) with extra objects:
-`roofline` for the dominant kernel (3x3 stride-1 conv on 512-pixel tiles: layers 1-4, MFMA-bound) timed live with HIP
-events on the launch stream; `cpu_baseline`: the oracle's CPU restatement of the reference
-path (NumPy tiling + torch-CPU ResNet-18 fp32) timed on a bounded sample; and, at N = 1,
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set-up, W warm-up slides, K timed
+slides, the arrays of --dump-outputs, and the line, which carries `roofline` for the dominant kernel (3x3 stride-1 conv on
+512-pixel tiles: layers 1-4, MFMA-bound), sampled live with HIP events on the launch stream during the timed slides, and at
+N > 1 what the process group saw (below).  Everything else runs only with `--full`, after the timed slides:
+`cpu_baseline`: the oracle's CPU restatement of the reference path (NumPy tiling + torch-CPU ResNet-18 fp32) timed on a
+bounded sample; and, at N = 1,
   `f32`        the same slide in float32 (the mode of north_star's "logits within 1e-4"), its own roofline vs 157.3 TF;
   `train`      BASELINE configs[1]: fused ResNet-18 f32 training steps/s at 64 x 224^2, with a roofline object;
   `train_bf16` the same network trained on the bf16 engine (bf16 MFMA, f32 master weights): informational, configs[1] is fp32;
@@ -26,10 +28,10 @@ path (NumPy tiling + torch-CPU ResNet-18 fp32) timed on a bounded sample; and, a
   `p224`       the reference's OWN geometry (examples/predict_full_patched.py:157-167, config.yaml:23): the same slide at 224 x 224 tiles,
                stride 112 (198 916 tiles), patches/s, whole-model fraction at 3.6271 GFLOP per tile, dominant-kernel roofline.
 At N > 1 the line also carries `ranks` (what RCCL saw: rank, device index, PCI bus id / uuid and tile range of every rank, gathered over
-the group), `backend`, `nccl_version`, `allgather_ms`, and `train_ddp`: ResNet-50 bf16 data-parallel steps/s with the bucketed RCCL all-reduce
-(configs[4]) overlapped with the backward pass AND (`overlap_off`) exchanged after it -- the difference shows whether RCCL's kernels got CUs beside
-the persistent convolutions.  A failure in that leg is reported in the object; the ranks agree on it through the rendezvous store (never through a
-collective a failed rank may no longer take part in) before anyone enters the closing barrier.
+the group), `backend`, `nccl_version`, `allgather_ms`, and, with `--full`, `train_ddp`: ResNet-50 bf16 data-parallel steps/s with the bucketed
+RCCL all-reduce (configs[4]) overlapped with the backward pass AND (`overlap_off`) exchanged after it -- the difference shows whether RCCL's
+kernels got CUs beside the persistent convolutions.  A failure in that leg is reported in the object; the ranks agree on it through the
+rendezvous store (never through a collective a failed rank may no longer take part in) before anyone enters the closing barrier.
 """
 from __future__ import annotations
 
@@ -68,13 +70,16 @@ def parse():
     ap.add_argument("--downscale", type=int, default=16)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the CPU baselines and the extra legs (float32 and 224 / 112 slides, "
+                         "gather kernels, training steps; train_ddp at N > 1); the options below shape them")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--train-steps", type=int, default=60,
-                    help="extra legs: time this many fused training steps (configs[1] f32 ResNet-18, configs[4] bf16 ResNet-50); 0 = skip")
-    ap.add_argument("--f32-steps", type=int, default=2, help="extra leg: whole slides in float32 (0 = skip)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="headline measurement only (profiling runs)")
-    ap.add_argument("--p224-steps", type=int, default=2, help="extra leg: whole slides at the reference's 224 / 112 geometry (0 = skip)")
+                    help="with --full: time this many fused training steps (configs[1] f32 ResNet-18, configs[4] bf16 ResNet-50); 0 = skip")
+    ap.add_argument("--f32-steps", type=int, default=2, help="with --full: whole slides in float32 (0 = skip)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the extra legs and the extra CPU baselines (`cpu_baseline` still runs)")
+    ap.add_argument("--p224-steps", type=int, default=2, help="with --full: whole slides at the reference's 224 / 112 geometry (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (class map, per-tile logits) as DIR/<name>.npy "
                          "in float32, at most 64 MB in all (rank 0)")
@@ -378,6 +383,7 @@ def self_launch(n: int) -> int:
 
 def main():
     args = parse()
+    extra_legs = args.full and not args.no_extra_legs
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -473,7 +479,7 @@ def main():
     if world > 1 and exchange_events:
         allgather_ms = sum(a.elapsed_time(b) for a, b in exchange_events) / len(exchange_events)
     train_ddp = None
-    if world > 1 and args.train_steps > 0 and not args.no_extra_legs:
+    if world > 1 and args.train_steps > 0 and extra_legs:
         try:
             del slide, smp
             torch.cuda.empty_cache()
@@ -565,7 +571,7 @@ def main():
         }
         if dumped is not None:
             out["dumped_outputs"] = {"dir": str(Path(args.dump_outputs).resolve()), "arrays": dumped}
-        extra = world == 1 and not args.no_extra_legs
+        extra = world == 1 and extra_legs
         if extra and args.f32_steps > 0 and args.dtype == "bf16":
             # the configuration north_star's "logits within 1e-4 of the CPU reference" belongs to: same slide, float32 MFMA
             m32 = get_model(5, "f32").to(dev).eval()
@@ -617,9 +623,9 @@ def main():
             out["distinct_devices"] = len({(r or {}).get("pci_bus_id") or (r or {}).get("uuid") or (r or {}).get("device") for r in ranks_seen})
             out["allgather_ms"] = allgather_ms   # HIP-event time of the ONE RCCL all-gather of per-tile logits, mean per slide (rank 0)
             out["train_ddp"] = train_ddp
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)   # rank 0, after the group is gone
-            if not args.no_extra_legs and world == 1:
+            if extra_legs and world == 1:
                 out["cpu_baselines"] = {"sampler_generator_torch": cpu_sampler_baseline(args, 4.0),
                                         "train_step_resnet18_f32": cpu_train_baseline(2),
                                         "train_step_resnet50_f32": cpu_train_baseline(2, "resnet50")}

@@ -113,13 +113,13 @@ def test_train_cli_two_ranks_replicas_identical(built_lib, tmp_path, arch, dtype
 
 def test_bench_self_launch_two_ranks_share_gpu(built_lib, tmp_path):
     """VERDICT r3 missing #2: `python bench.py --gpus N` (the driver's command shape, no launcher environment) starts the N ranks
-    itself as a child torch.distributed.run job and relays ONE JSON line carrying the multi-GPU objects: all-gather time,
-    data-parallel ResNet-50 step with the exposed all-reduce time in both wire formats, and the CPU baseline."""
+    itself as a child torch.distributed.run job and relays ONE JSON line carrying the multi-GPU objects: all-gather time and,
+    with --full, data-parallel ResNet-50 step with the exposed all-reduce time in both wire formats, and the CPU baseline."""
     import json
     env = dict(os.environ, DH_BENCH_SHARE_GPU="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--slide", "4096", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--slide", "4096", "--steps", "1", "--warmup", "1", "--full",
            "--train-steps", "3", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, env=env, cwd=tmp_path, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -149,9 +149,31 @@ def test_bench_failing_ddp_leg_is_agreed_through_the_store(built_lib, tmp_path):
     env = dict(os.environ, DH_BENCH_SHARE_GPU="1", DH_BENCH_FAIL_DDP="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--slide", "4096", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--slide", "4096", "--steps", "1", "--warmup", "1", "--full",
            "--train-steps", "2", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=tmp_path, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert out["value"] > 0 and "DH_BENCH_FAIL_DDP" in out["train_ddp"]["error"]
+
+
+def test_bench_plain_run_is_the_headline_alone(built_lib, tmp_path):
+    """Without --full, bench.py sets up, warms up, times the slides, writes --dump-outputs and prints ONE line: the headline
+    figure with its live-sampled roofline, and none of the CPU baselines or extra legs."""
+    import json
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--slide", "4096", "--steps", "1", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, env=env, cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 1 and out["config"]["n_tiles"] == 256 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["higher_is_better"] is True and out["dtype"] == "bf16" and out["roofline"]["launches_timed"] > 0
+    assert out["cpu_baseline"] is None
+    assert not {"f32", "p224", "tiler", "train", "train_bf16", "train_r50", "cpu_baselines", "train_ddp"} & set(out), sorted(out)
+    assert set(out["dumped_outputs"]["arrays"]) == {"logits", "class_map"}
+    assert np.load(tmp_path / "out" / "class_map.npy").shape == (256, 256)

@@ -1,13 +1,13 @@
 # Regenerates everything under profiles/ for one round on the GPU box (run through gpurun from the repository root):
 #   bash tools/refresh_profiles.sh r02      -> gpurun_out/profiles_r02/*  (copy to profiles/ afterwards: tools/collect_profiles.sh r02)
-# default bench line, rocprofv3 kernel stats of the same command, the two --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs,
+# the bench --full line, rocprofv3 kernel stats of the headline command, the two --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs,
 # kernel trace only), per-layer table, MFMA utilisation per layer (SQ counters), conv phase stamps, training kernel stats.
 set -e
 RND=${1:-r05}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; P=$O/profiles_$RND; mkdir -p $P
 cd $R
-python3 bench.py > $P/${RND}_bench_line.json 2> $O/bench_default.err
+python3 bench.py --full > $P/${RND}_bench_line.json 2> $O/bench_default.err
 echo "bench done"
 rm -rf $O/prof_stats $O/pmc_fetch $O/pmc_write
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/prof_stats -o st -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs --train-steps 0 > $O/bench_prof.json 2> $O/bench_prof.err
