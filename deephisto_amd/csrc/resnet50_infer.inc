@@ -131,7 +131,8 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
   bf16_t* T1 = reinterpret_cast<bf16_t*>(base + 2 * big);
   bf16_t* T2 = reinterpret_cast<bf16_t*>(base + 2 * big + t1);
   int rc;
-  if ((rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, X, st))) return rc;
+  DH_REQUIRE(stem_seam_bytes(B, P) <= t1, "resnet50 forward: seam scratch larger than the bottleneck buffer");
+  if ((rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, X, T1, st))) return rc;   // T1: free until conv1
   for (const char* nm : {"conv1", "maxpool"})   // the fused stem stores only the pooled map
     if ((rc = tap_after<__bf16>(tap, nm, X, 64, H2, H2, 32, st))) return rc;
   int H = H2;

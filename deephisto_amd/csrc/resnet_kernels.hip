@@ -1158,23 +1158,52 @@ int run_conv(const ConvLayer& L, const void* in, const void* res, void* out, int
   return DH_EINVAL;
 }
 
-// fused bf16 stem (conv1 + bn1 + relu + maxpool) of `B` tiles -> channel-blocked [image][2][H2][W2][32] bf16
-int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
-                     const int32_t* yx, int B, int P, void* out, hipStream_t st) {
+int g_stem_pc_force = 0;   // dh_debug_stem_strip_width: 0 = by geometry, 15 / 16 = that strip width
+
+// pooled columns per strip of the fused stem: 16 (strips joined by the seam pass) only where that saves a strip
+int stem_pool_pc(int P) {
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
+  if (g_stem_pc_force) return g_stem_pc_force;
+  return (H2 + 15) / 16 < (H2 + 14) / 15 ? 16 : 15;
+}
+
+// bytes of the seam scratch of launch_stem_pool (0: the geometry has no seams)
+size_t stem_seam_bytes(int B, int P) {
+  const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
+  return stem_pool_pc(P) == 16 ? (size_t)B * ((H2 + 15) / 16 - 1) * H2 * 64 * 2 : 0;
+}
+
+template <int PC>
+int launch_stem_pool_pc(const StemPoolParams& sp, int grid, hipStream_t st) {
+  int arc;
+  if ((arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<true, false, PC>), SP_LDS)) ||
+      (arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<true, true, PC>), SP_LDS)) ||
+      (arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<false, false, PC>), SP_LDS))) return arc;
+  if (sp.slide && sp.stamps) hipLaunchKernelGGL((stem_pool_kernel<true, true, PC>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
+  else if (sp.slide) hipLaunchKernelGGL((stem_pool_kernel<true, false, PC>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
+  else hipLaunchKernelGGL((stem_pool_kernel<false, false, PC>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// fused bf16 stem (conv1 + bn1 + relu + maxpool) of `B` tiles -> channel-blocked [image][2][H2][W2][32] bf16.  `seam`: scratch of
+// stem_seam_bytes(B, P) bytes, dead once the call's launches have run (may be null when that is 0)
+int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
+                     const int32_t* yx, int B, int P, void* out, void* seam, hipStream_t st) {
+  const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
+  const int pc = stem_pool_pc(P);
   StemPoolParams sp;
   DH_REQUIRE(!slide || slide_w < (1 << 24), "stem: slide rows of %lld pixels are not supported (< 2^24)", (long long)slide_w);
   sp.x_nchw = x; sp.slide = slide; sp.yx = yx; sp.row_bytes = slide_w * 3; sp.slide_bytes = slide_h * slide_w * 3;
   sp.w = stem.w_dev; sp.scale = stem.scale_dev; sp.shift = stem.shift_dev; sp.out = out;
   sp.B = B; sp.P = P; sp.Hc = H1; sp.Wc = H1; sp.Hp = H2; sp.Wp = H2;
-  sp.tiles_y = (H2 + SP_PR - 1) / SP_PR; sp.tiles_x = (H2 + SP_PC - 1) / SP_PC;
-  sp.nstrips = B * sp.tiles_x;                 // a strip = one image x 15 pooled columns, swept top to bottom
+  sp.tiles_y = (H2 + SP_PR - 1) / SP_PR; sp.tiles_x = (H2 + pc - 1) / pc;
+  sp.seam = seam;
+  const int nseam = pc == 16 ? sp.tiles_x - 1 : 0;
+  DH_REQUIRE(!nseam || seam, "stem: %d strips of 16 pooled columns need a seam scratch", sp.tiles_x);
+  sp.nstrips = B * sp.tiles_x;                 // a strip = one image x pc pooled columns, swept top to bottom
   const int grid = std::min(768, sp.nstrips);  // persistent: three 4-wave workgroups per CU
   sp.iters = ((sp.nstrips + grid - 1) / grid) * sp.tiles_y;
-  int arc;
-  if ((arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<true, false>), SP_LDS)) ||
-      (arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<true, true>), SP_LDS)) ||
-      (arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_pool_kernel<false, false>), SP_LDS))) return arc;
   sp.stamps = nullptr;
   if (g_stamps_on && slide) {
     if (!g_stamps_dev) {
@@ -1183,10 +1212,13 @@ int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide
     }
     sp.stamps = g_stamps_dev + 8 * 7;
   }
-  if (slide && sp.stamps) hipLaunchKernelGGL((stem_pool_kernel<true, true>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
-  else if (slide) hipLaunchKernelGGL((stem_pool_kernel<true, false>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
-  else hipLaunchKernelGGL((stem_pool_kernel<false, false>), dim3(grid), dim3(SP_T), SP_LDS, st, sp);
-  DH_LAUNCH_CHECK();
+  if (int rc = pc == 16 ? launch_stem_pool_pc<16>(sp, grid, st) : launch_stem_pool_pc<15>(sp, grid, st)) return rc;
+  if (nseam) {   // first pooled column of every strip but an image's first: fold in the neighbour's last conv column
+    const int64_t total = (int64_t)B * nseam * H2 * 8;
+    hipLaunchKernelGGL(stem_seam_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, static_cast<const void*>(seam),
+                       static_cast<__bf16*>(out), total, nseam, H2, H2);
+    DH_LAUNCH_CHECK();
+  }
   return DH_OK;
 }
 
@@ -1268,8 +1300,10 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
   void* bufC = base + al(stem_bytes) + 2 * al(act_bytes);
 
   if constexpr (sizeof(T) == 2) {
-    // bf16: fused stem + BN + ReLU + maxpool (persistent, weights resident in LDS), straight into bufA
-    if (int rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, bufA, st)) return rc;
+    // bf16: fused stem + BN + ReLU + maxpool (persistent, weights resident in LDS), straight into bufA.  The unfused stem's slot S
+    // of the workspace is free in this path and holds the seam scratch ((tiles_x - 1) * H2 <= H1 * H1 pixels per image)
+    DH_REQUIRE(stem_seam_bytes(B, P) <= al(stem_bytes), "resnet18 forward: seam scratch larger than the stem slot");
+    if (int rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, bufA, S, st)) return rc;
     for (const char* nm : {"conv1", "maxpool"})   // the fused stem stores only the pooled map
       if (int rc = tap_after<T>(tap, nm, bufA, 64, H2, H2, 32, st)) return rc;
   } else {
@@ -1573,8 +1607,10 @@ extern "C" int dh_debug_stem_pool_bf16(dh_resnet18* net, const uint8_t* slide_de
   hipStream_t st = dh::as_stream(stream);
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
   void* tmp = nullptr;
-  DH_HIP(hipMalloc(&tmp, (size_t)n * H2 * H2 * 64 * 2));
-  int rc = launch_stem_pool(net->convs[0], nullptr, slide_dev, slide_h, slide_w, yx_dev, (int)n, P, tmp, st);
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t out_bytes = al((size_t)n * H2 * H2 * 64 * 2);
+  DH_HIP(hipMalloc(&tmp, out_bytes + stem_seam_bytes((int)n, P) + 256));
+  int rc = launch_stem_pool(net->convs[0], nullptr, slide_dev, slide_h, slide_w, yx_dev, (int)n, P, tmp, static_cast<char*>(tmp) + out_bytes, st);
   if (!rc) {
     hipLaunchKernelGGL(blocked_to_nhwc_f32_kernel, dim3(1024), dim3(256), 0, st, static_cast<const __bf16*>(tmp), out_dev, n, H2 * H2);
     if (hipGetLastError() != hipSuccess) rc = DH_EHIP;
@@ -1683,6 +1719,13 @@ extern "C" int dh_debug_stamps(int32_t enable, unsigned long long* out64_host) {
     DH_HIP(hipMemcpy(out64_host, g_stamps_dev, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     DH_HIP(hipMemset(g_stamps_dev, 0, 64 * sizeof(unsigned long long)));
   }
+  return DH_OK;
+}
+
+// Test hook: strips of the fused bf16 stem of 15 or 16 pooled columns whatever the geometry; 0 = chosen by geometry (the default).
+extern "C" int dh_debug_stem_strip_width(int32_t pc) {
+  DH_REQUIRE(pc == 0 || pc == 15 || pc == 16, "debug stem strip width: %d is not 0, 15 or 16", pc);
+  g_stem_pc_force = pc;
   return DH_OK;
 }
 

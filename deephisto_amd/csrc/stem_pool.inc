@@ -4,8 +4,8 @@
 // The unfused pair (stem_kernel + maxpool_kernel) writes the 128x128x64 stem activation to HBM
 // and reads it back (536 MB per 128 tiles in bf16) and re-stages the weight image for
 // every 256 output pixels.  Here a PERSISTENT 4-wave workgroup keeps the weights in LDS for its
-// whole life and sweeps column strips of (image, 15 pooled columns) from top to bottom, 4 pooled rows
-// (= 8 conv rows) per step:
+// whole life and sweeps column strips of (image, PC pooled columns) from top to bottom, 4 pooled rows
+// (= 8 conv rows) per step (PC = 15 or 16, chosen per geometry by the launcher: see the end of this comment):
 //   * the 21 x 69-pixel input window of the step's 8 x 32 conv tile is staged in LDS as normalised bf16
 //     (straight from the uint8 slide: 4-byte loads, prefetched into registers one step ahead);
 //   * MFMA 32x32x16: a window row holds (pixel, channel) pairs interleaved, so the 21 taps of one kernel row are 21
@@ -20,8 +20,15 @@
 //     row horizontally before the exchange: twice the DPP work; one before that let every wave compute three
 //     conv rows: +50 % MFMA work);
 //   * bf16 values order like signed 16-bit integers within a sign and every negative is below +0, so max_i16
-//     against 0 at the end is the ReLU (bf16(relu(x)) == relu(bf16(x))).  Even lanes hold the 15 pooled pixels of
+//     against 0 at the end is the ReLU (bf16(relu(x)) == relu(bf16(x))).  Even lanes hold the pooled pixels of
 //     the row and store them with 16-byte stores (half-waves trade halves, permlane32 swap).
+// Strip width.  A 32-column conv tile holds the three conv columns 2c-1 .. 2c+1 of 15 pooled columns c.
+//   PC = 15: lane 0 is conv column 2*px0 - 1; even lane 2j pools lanes 2j .. 2j+2.  Strips are independent.
+//   PC = 16: lane 0 is conv column 2*px0 (the aligned tile: 128 conv columns are 4 strips, not 5); even lane 2j pools
+//     lanes 2j-1 .. 2j+1.  Pooled column px0 of a strip s >= 1 lacks conv column 2*px0 - 1, the LAST lane of strip s-1:
+//     that strip writes the column's vertical 3-row max (lanes 31 and 63 of the row-combined registers, after the ReLU)
+//     to the seam scratch [image][seam][Hp][64 couts in lane order], and stem_seam_kernel, next on the stream, folds it into the output with
+//     max_i16.  Max is exact and order-free and every value is a non-negative bf16: the same nine values, the same bits.
 // Conv rows/cols outside the image contribute 0, which is neutral for a max that ends in a ReLU.
 // The kernel is bound by vector-ALU issue, not by the matrix pipe (ablations in profiles/): everything per conv
 // output that is not the MFMA is kept to a handful of instructions.
@@ -33,7 +40,7 @@
 constexpr int SP_W = 4;
 constexpr int SP_T = SP_W * 64;
 constexpr int SP_CR = 2 * SP_W, SP_CC = 32;        // conv tile of a step: wave w computes rows {2w, 2w+1}
-constexpr int SP_PR = SP_W, SP_PC = 15;            // pooled tile
+constexpr int SP_PR = SP_W;                        // pooled rows of a step (pooled columns: the template parameter PC)
 constexpr int SP_WR = 2 * SP_CR + 5;               // window rows (21)
 constexpr int SP_WE = 224;                         // elements per window row (slot 0 dummy, 1..207 data)
 #ifndef SP_PF
@@ -63,14 +70,17 @@ inline void sp_kslot(int ks, int hh, int j, int* kh, int* s) {
 struct StemPoolParams {
   const float* x_nchw; const uint8_t* slide; const int32_t* yx; int64_t row_bytes, slide_bytes;
   const void* w; const float* scale; const float* shift; void* out;
+  void* seam;   // PC = 16: [B][tiles_x - 1][Hp][64] bf16, the last conv column of every strip but an image's last
   int B, P, Hc, Wc, Hp, Wp, tiles_y, tiles_x, nstrips, iters;   // strips = (image, tile column); iters = strips per workgroup x tiles_y
   unsigned long long* stamps;
 };
 
 typedef unsigned short sp_u16x2 __attribute__((ext_vector_type(2)));
 
-template <bool SRC_U8, bool STAMP>
+template <bool SRC_U8, bool STAMP, int PC>
 __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams p) {
+  static_assert(PC == 15 || PC == 16, "strips of 15 or 16 pooled columns");
+  constexpr int CX = 16 - PC;   // lane 0 is conv column 2*px0 - CX
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* w_lds = smem;
   char* win_lds = smem + SP_WBYTES;
@@ -88,7 +98,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
   // steps of this workgroup: strip k * gridDim + blockIdx (k = 0, 1, ...), tile rows top to bottom.  The cursor below
   // walks them incrementally (one division per strip, not per step); the tile's slide origin (ty0, tx0) is loaded in
   // next_tile(), an iteration before load_window needs it.
-  int cur_sid = (int)blockIdx.x, cur_ty = 0, cur_b = cur_sid / p.tiles_x, cur_px0 = (cur_sid % p.tiles_x) * SP_PC, cur_it = 0;
+  int cur_sid = (int)blockIdx.x, cur_ty = 0, cur_b = cur_sid / p.tiles_x, cur_px0 = (cur_sid % p.tiles_x) * PC, cur_it = 0;
   auto next_tile = [&]() __attribute__((always_inline)) {
     Tile t;
     t.valid = cur_sid < p.nstrips && cur_it < p.iters;
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
     ++cur_it;
     if (++cur_ty == p.tiles_y) {
       cur_ty = 0; cur_sid += (int)gridDim.x;
-      cur_b = cur_sid / p.tiles_x; cur_px0 = (cur_sid % p.tiles_x) * SP_PC;
+      cur_b = cur_sid / p.tiles_x; cur_px0 = (cur_sid % p.tiles_x) * PC;
     }
     return t;
   };
@@ -111,7 +121,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
   constexpr int SP_TAIL = SP_WR * SP_DW - (SP_NLOAD - 1) * SP_T;   // threads that own a piece in the last round
   uint32_t wr[SP_NLOAD], wr2[SP_NLOAD];   // window pieces of the next tile (staged this step) / of the one after (in flight)
   uint32_t woff[SP_NLOAD];  // byte offset of the piece from (window origin - 1)
-  int wrd[SP_NLOAD];        // r << 8 | d
+  uint32_t wdst[SP_NLOAD];  // byte offset of the piece in the window buffer: (r * SP_WE + 4 * d) * 2
   uint32_t colm[SP_NLOAD];  // byte mask of the piece: columns of the current strip that lie inside the tile
 #pragma unroll
   for (int k = 0; k < SP_NLOAD; ++k) {
@@ -120,13 +130,20 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
     const bool own = idx < SP_WR * SP_DW;
     const int r = own ? idx / SP_DW : 0, d = own ? idx % SP_DW : 0;
     woff[k] = (uint32_t)(r * (int)p.row_bytes + 4 * d);
-    wrd[k] = r << 8 | d;
+    wdst[k] = (uint32_t)((r * SP_WE + 4 * d) * 2);
   }
+  // (r, d) of piece k for the masks of edge windows.  Recomputed where it is used: the opaque copy keeps the compiler from hoisting r,
+  // d and what is derived from them out of the sweep, where they would hold registers through every step for the sake of a few
+  auto piece_rd = [&](int k, int* r, int* d) __attribute__((always_inline)) {
+    uint32_t w = wdst[k];
+    asm volatile("" : "+v"(w));
+    *r = (int)(w / (uint32_t)(SP_WE * 2)); *d = (int)(w % (uint32_t)(SP_WE * 2)) >> 3;
+  };
   struct __attribute__((packed, aligned(1))) U32 { uint32_t v; };
-  // window of tile t: input rows iy0 + r (r < 21), bytes 3*ix0 + q (q < 207), iy0 = 4*py0 - 3, ix0 = 4*px0 - 5
+  // window of tile t: input rows iy0 + r (r < 21), bytes 3*ix0 + q (q < 207), iy0 = 4*py0 - 3, ix0 = 2*(2*px0 - CX) - 3
   auto load_window = [&](const Tile& t, uint32_t (&wr)[SP_NLOAD]) __attribute__((always_inline)) {
     if constexpr (SRC_U8) {
-      const int iy0 = 4 * t.py0 - 3, ix0 = 4 * t.px0 - 5;
+      const int iy0 = 4 * t.py0 - 3, ix0 = 4 * t.px0 - 2 * CX - 3;
       const int64_t worg = (int64_t)(t.ty0 + iy0) * p.row_bytes + (int64_t)(t.tx0 + ix0) * 3 - 1;   // byte before the window
       const int64_t wend = worg + (int64_t)(SP_WR - 1) * p.row_bytes + 4 * SP_DW;                    // one past its last dword
       if constexpr (SP_ABL & 2) return;
@@ -148,7 +165,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
   };
   auto store_window = [&](const Tile& t, uint32_t (&wr)[SP_NLOAD]) __attribute__((always_inline)) {
     uint16_t* win = reinterpret_cast<uint16_t*>(win_lds);
-    const int iy0 = 4 * t.py0 - 3, ix0 = 4 * t.px0 - 5;
+    const int iy0 = 4 * t.py0 - 3, ix0 = 4 * t.px0 - 2 * CX - 3;
     if constexpr (SRC_U8) {
       if constexpr (SP_ABL & 4) {   // consume the loads, convert nothing
 #pragma unroll
@@ -162,7 +179,9 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
         const int q_lo = max(0, -ix0) * 3, q_hi = min(207, (p.P - ix0) * 3);   // bytes of pixels inside the tile
 #pragma unroll
         for (int k = 0; k < SP_NLOAD; ++k) {
-          const int q0 = 4 * (wrd[k] & 255) - 1;
+          int r, d;
+          piece_rd(k, &r, &d);
+          const int q0 = 4 * d - 1;
           const int lo = min(max(q_lo - q0, 0), 4), hi = min(max(q_hi - q0, 0), 4);   // bytes [lo, hi) of the dword stay
           colm[k] = (lo < 4 ? 0xFFFFFFFFu << (8 * lo) : 0u) & (hi > 0 ? 0xFFFFFFFFu >> (32 - 8 * hi) : 0u);
         }
@@ -175,7 +194,8 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
         const int r_lo = max(0, -iy0), r_hi = min(SP_WR, p.P - iy0);
 #pragma unroll
         for (int k = 0; k < SP_NLOAD; ++k) {
-          const int r = wrd[k] >> 8;
+          int r, d;
+          piece_rd(k, &r, &d);
           if (r < r_lo || r >= r_hi) wr[k] = 0u;
         }
       }
@@ -189,7 +209,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
           typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
           const bf16x4_t w4 = {(__bf16)((float)(w & 0xFFu) * r255), (__bf16)((float)((w >> 8) & 0xFFu) * r255),
                                (__bf16)((float)((w >> 16) & 0xFFu) * r255), (__bf16)((float)(w >> 24) * r255)};
-          *reinterpret_cast<bf16x4_t*>(win + (wrd[k] >> 8) * SP_WE + 4 * (wrd[k] & 255)) = w4;   // element 4d = slot 0 (dummy) when d == 0
+          *reinterpret_cast<bf16x4_t*>(win_lds + wdst[k]) = w4;   // element 4d = slot 0 (dummy) when d == 0
         }
       }
     } else {
@@ -233,11 +253,18 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
   auto max16 = [](uint32_t a, uint32_t b) __attribute__((always_inline)) {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(sp_i16x2, a), __builtin_bit_cast(sp_i16x2, b)));
   };
-  auto hmax3 = [&](uint32_t v0) __attribute__((always_inline)) {   // lanes tx, tx+1, tx+2
-    // wave_shl:1 with bound_ctrl: lane 63 reads 0 and no lane keeps its old value, so the destination needs no initialisation
+  // horizontal 3-max and the ReLU.  PC = 15: lanes tx, tx+1, tx+2; PC = 16: lanes tx-1, tx, tx+1 of values that have the ReLU behind them
+  auto hmax3 = [&](uint32_t v0) __attribute__((always_inline)) {
+    // wave_shl:1 / wave_shr:1 with bound_ctrl: lane 63 / lane 0 reads 0 and no lane keeps its old value, so the destination needs
+    // no initialisation
     const uint32_t v1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v0, 0x130, 0xF, 0xF, true);  // lane+1
-    const uint32_t v2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v1, 0x130, 0xF, 0xF, true);  // lane+2
-    return max16(max16(v0, v1), v2);
+    if constexpr (PC == 16) {
+      const uint32_t vl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v0, 0x138, 0xF, 0xF, true);  // lane-1
+      return max16(max16(v0, v1), tx == 0 ? 0u : vl);   // lane 32's left neighbour is the other half-wave's last column: the seam
+    } else {
+      const uint32_t v2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v1, 0x130, 0xF, 0xF, true);  // lane+2
+      return max16(max16(max16(v0, v1), v2), 0u);
+    }
   };
   // exchange slot addressing: [lane][4 quads of 16 B], quad mt*2 + pr holds the groups g = 2pr, 2pr+1 of cout half mt;
   // quads are XOR-swizzled with lane bits 2..3 (8 consecutive lanes of a ds_*_b128 pass hit 8 different bank groups)
@@ -311,7 +338,7 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
       }
       stamp(1);
       // BN + pack.  Row b (the wave's second conv row) goes to the neighbour through LDS as it is.
-      const int r0 = 2 * cur.py0, c0 = 2 * cur.px0 - 1;
+      const int r0 = 2 * cur.py0, c0 = 2 * cur.px0 - CX;
       const bool interior = r0 + SP_CR <= p.Hc && c0 >= 0 && c0 + SP_CC <= p.Wc;   // workgroup-uniform
       char* slot = xch_lds + (wave < SP_W - 1 ? wave : SP_W - 1 + (it & 1)) * SP_XCH + xlane;
       auto bn_pack = [&](auto inside) __attribute__((always_inline)) {
@@ -369,10 +396,17 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
       const bool have_prev = wave > 0 || !cur.first;   // wave-uniform
       // even lanes hold pooled pixel (py0 + wave, px0 + tx/2); 16-byte stores after the half-wave swap
       const int py = cur.py0 + wave, px = cur.px0 + (tx >> 1);
-      const bool st_ok = even && (tx >> 1) < SP_PC && py < p.Hp && px < p.Wp;
+      const bool st_ok = even && (tx >> 1) < PC && py < p.Hp && px < p.Wp;
       // channel-blocked output [image][2 chunks of 32 couts][Hp][Wp][32] (the layout the 3x3 kernels read)
       const int plane = p.Hp * p.Wp * 32;
       __bf16* out = static_cast<__bf16*>(p.out) + (int64_t)cur.b * 2 * plane + (py * p.Wp + px) * 32;
+      // PC = 16: lanes 31 and 63 hold conv column 2*px0 + 31, which the next strip's first pooled column needs
+      const bool seam_ok = PC == 16 && tx == 31 && py < p.Hp && cur.px0 + PC < p.Wp;
+      // the seam pixel's 64 channels as the two lanes hold them, [half-wave][cout half][group][4 couts]: one 16-byte store per
+      // (cout half, group pair).  Wave-uniform; the lane's part is added at the store
+      __bf16* seam = nullptr;
+      if constexpr (PC == 16)
+        seam = static_cast<__bf16*>(p.seam) + (((int64_t)cur.b * (p.tiles_x - 1) + cur.px0 / PC) * p.Hp + py) * 64;
       uint4 pvq[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) pvq[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -387,9 +421,16 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
           const uint4 pv = pvq[mt * 2 + pr];
           uint32_t v[4] = {max16(vm[mt][2 * pr][0], pv.x), max16(vm[mt][2 * pr][1], pv.y),
                            max16(vm[mt][2 * pr + 1][0], pv.z), max16(vm[mt][2 * pr + 1][1], pv.w)};
+          if constexpr (PC == 16) {   // the ReLU first (max commutes with it): the seam column goes out with it applied
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = max16(v[i], 0u);
+            if constexpr (!(SP_ABL & 16)) {
+              if (seam_ok) *reinterpret_cast<uint4*>(seam + h * 32 + mt * 16 + pr * 8) = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+          }
           if constexpr (!(SP_ABL & 8)) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = max16(hmax3(v[i]), 0u);   // horizontal 3-max ... and the ReLU
+            for (int i = 0; i < 4; ++i) v[i] = hmax3(v[i]);   // horizontal 3-max ... and the ReLU
           }
           uint32_t a0 = v[0], a1 = v[1], b0 = v[2], b1 = v[3];
           { const auto r = __builtin_amdgcn_permlane32_swap(a0, b0, false, false); a0 = r[0]; b0 = r[1]; }
@@ -419,4 +460,21 @@ __global__ __launch_bounds__(SP_T, 3) void stem_pool_kernel(const StemPoolParams
       atomicAdd(p.stamps + 6, 1ull);
     }
   }
+}
+
+// PC = 16: out[b][:][py][16(s+1)] = max(out, seam[b][s][py]) for every seam pixel, 16 bytes (8 channels) per thread.
+// Non-negative bf16 order like 16-bit integers.
+__global__ __launch_bounds__(256) void stem_seam_kernel(const void* __restrict__ seam, __bf16* __restrict__ out, int64_t total,
+                                                        int nseam, int Hp, int Wp) {
+  typedef short sp_i16x8 __attribute__((ext_vector_type(8)));
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // [b][s][py][8 pieces]
+  if (i >= total) return;
+  const int c8 = (int)(i & 7);   // channels 8*c8 ..: cout half c8 >> 2, group c8 & 3; its couts 0..3 / 4..7 come from half-wave 0 / 1
+  const int64_t px = i >> 3;
+  const int py = (int)(px % Hp), s = (int)((px / Hp) % nseam);
+  const int64_t b = px / Hp / nseam;
+  uint4* o = reinterpret_cast<uint4*>(out + (((b * 2 + (c8 >> 2)) * Hp + py) * Wp + 16 * (s + 1)) * 32 + (c8 & 3) * 8);
+  const uint2* row = reinterpret_cast<const uint2*>(seam) + px * 16 + c8;   // seam row: [half-wave][cout half][group][4 couts]
+  const uint2 lo = row[0], hi = row[8];
+  *o = __builtin_bit_cast(uint4, __builtin_elementwise_max(__builtin_bit_cast(sp_i16x8, *o), __builtin_bit_cast(sp_i16x8, make_uint4(lo.x, lo.y, hi.x, hi.y))));
 }

@@ -104,6 +104,10 @@ int dh_debug_maxpool_f32(const float* x_dev, float* y_dev, const float* dy_dev, 
 int dh_debug_bn_pool_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, float* pooled_dev, uint8_t* idx_dev,
                          const float* dpool_dev, float* dz_dev, float* dgamma_dev, float* dbeta_dev, int32_t B, int32_t Hi, int32_t Wi,
                          int32_t C, void* stream);
+/* dh_debug_stem_strip_width: pooled columns per column strip of the fused bf16 stem for every later launch of the process: 15
+ * (independent strips), 16 (aligned strips joined by stem_seam_kernel), or 0 = chosen by geometry, the default: 16 where that
+ * needs fewer strips.  The stem's output does not depend on it, bit for bit (tests/test_gpu_stem_strips.py). */
+int dh_debug_stem_strip_width(int32_t pooled_columns);
 /* dh_debug_stamps: switch the 3x3-conv kernel to its cycle-stamped diagnostic variant and/or read
  * (and clear) its 8x8 table of summed phase cycles; out64_host may be NULL. */
 int dh_debug_stamps(int32_t enable, unsigned long long* out64_host);

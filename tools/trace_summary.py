@@ -32,7 +32,7 @@ def main(path, micro_batch=256):
         elif "conv3x3_kernel" in n and forwards and len(forwards[-1]) <= len(SEQ):
             forwards[-1].append((SEQ[len(forwards[-1]) - 1], us))
         else:
-            lab = next((v for k, v in (("avgpool", "avgpool+fc"), ("accumulate", "accumulate"), ("argmax", "argmax"),
+            lab = next((v for k, v in (("stem_seam", "stem seam"), ("avgpool", "avgpool+fc"), ("accumulate", "accumulate"), ("argmax", "argmax"),
                                        ("gather", "gather"), ("synth", "synth")) if k in n), None)
             if lab:
                 other[lab].append(us)
@@ -46,7 +46,7 @@ def main(path, micro_batch=256):
     agg.update(other)
     tot = sum(sum(v) for v in agg.values())
     print(f"{'kernel':12s} {'calls':>6s} {'avg_us':>9s} {'min_us':>9s} {'share':>7s} {'TFLOP/s':>8s}   (full micro-batches of {micro_batch} only)")
-    for k in ["stem+pool"] + sorted(set(SEQ), key=SEQ.index) + ["avgpool+fc", "accumulate", "argmax", "synth"]:
+    for k in ["stem+pool", "stem seam"] + sorted(set(SEQ), key=SEQ.index) + ["avgpool+fc", "accumulate", "argmax", "synth"]:
         v = agg.get(k)
         if not v:
             continue
