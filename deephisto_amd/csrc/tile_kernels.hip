@@ -453,7 +453,7 @@ extern "C" int dh_tile_coords_f32(const int32_t* yx_dev, int64_t n, float* out, 
 // reference's order: float32 results are bit-identical to the NumPy `+=` loop,
 // with no atomics.  Traffic: canvas read+write once, logits/lists from L2.
 // ---------------------------------------------------------------------------
-struct BinGeom { int32_t G, bins_x, dh, dw, n_cls, P, d; };
+using dh::BinGeom;
 
 __global__ __launch_bounds__(256) void accumulate_bins_kernel(
     const float* __restrict__ logits, const int32_t* __restrict__ yx,
@@ -519,6 +519,71 @@ extern "C" int dh_argmax_map(const float* canvas, int64_t n_cells, int32_t n_cls
   return DH_OK;
 }
 
+// The bin lists depend only on (origins, P, d, h, w): whole-slide prediction repeats the same
+// grid slide after slide, so the last plan (host CSR + its device copies) is kept and reused
+// when the origins compare equal -- no rebuild, no upload, no stream synchronisation.  Shared by
+// every ordered accumulation (dh_accumulate_logits, dh_accumulate_mean): the class map and the
+// probabilities of one slide are built from one plan.
+namespace dh {
+int bin_plan(const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int64_t h, int64_t w, hipStream_t st, BinPlan* out) {
+  struct Plan {
+    std::vector<int32_t> yx; int32_t P = 0, d = 0; int64_t h = 0, w = 0, nbins = 0, total = 0; int G = 0, bins_x = 0;
+    int32_t *d_start = nullptr, *d_tiles = nullptr, *d_yx = nullptr; int device = -1;
+  };
+  static thread_local Plan plan;
+  const int64_t dh_ = h / d, dw_ = w / d;
+  int dev_id = 0;
+  DH_HIP(hipGetDevice(&dev_id));
+  const bool hit = plan.device == dev_id && plan.P == P && plan.d == d && plan.h == h && plan.w == w &&
+                   (int64_t)plan.yx.size() == 2 * n && memcmp(plan.yx.data(), yx_host, (size_t)n * 8) == 0;
+  if (!hit) {
+    const int G = std::max(1, std::min(P / d, 64));
+    const int64_t bins_y = (dh_ + G - 1) / G, bins_x = (dw_ + G - 1) / G;
+    const int64_t nbins = bins_y * bins_x;
+    DH_REQUIRE(nbins < INT32_MAX, "accumulate: too many bins");
+    std::vector<int32_t> start(nbins + 1, 0);
+    auto span = [&](int64_t i, int64_t& cy0, int64_t& cy1, int64_t& cx0, int64_t& cx1) {
+      const int64_t y = yx_host[2 * i], x = yx_host[2 * i + 1];
+      cy0 = std::max<int64_t>(y / d, 0); cy1 = std::min<int64_t>((y + P) / d, dh_);
+      cx0 = std::max<int64_t>(x / d, 0); cx1 = std::min<int64_t>((x + P) / d, dw_);
+      return y >= 0 && x >= 0 && cy1 > cy0 && cx1 > cx0;
+    };
+    int64_t total = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      int64_t a, b, c, e;
+      DH_REQUIRE(yx_host[2 * i] >= 0 && yx_host[2 * i + 1] >= 0, "accumulate: negative origin");
+      if (!span(i, a, b, c, e)) continue;
+      for (int64_t by = a / G; by <= (b - 1) / G; ++by)
+        for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) { ++start[by * bins_x + bx + 1]; ++total; }
+    }
+    DH_REQUIRE(total < INT32_MAX, "accumulate: incidence list too long");
+    for (int64_t b = 0; b < nbins; ++b) start[b + 1] += start[b];
+    std::vector<int32_t> fill(start.begin(), start.end() - 1), tiles((size_t)std::max<int64_t>(total, 1));
+    for (int64_t i = 0; i < n; ++i) {
+      int64_t a, b, c, e;
+      if (!span(i, a, b, c, e)) continue;
+      for (int64_t by = a / G; by <= (b - 1) / G; ++by)
+        for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) tiles[fill[by * bins_x + bx]++] = (int32_t)i;
+    }
+    DH_HIP(hipStreamSynchronize(st));  // the previous plan's buffers may still be in use on this stream
+    if (plan.d_start) { (void)hipFree(plan.d_start); (void)hipFree(plan.d_tiles); (void)hipFree(plan.d_yx); }
+    plan = Plan();
+    const size_t sb = (size_t)(nbins + 1) * 4, tb = (size_t)std::max<int64_t>(total, 1) * 4, yb = (size_t)n * 8;
+    DH_HIP(hipMalloc((void**)&plan.d_start, sb));
+    DH_HIP(hipMalloc((void**)&plan.d_tiles, tb));
+    DH_HIP(hipMalloc((void**)&plan.d_yx, yb));
+    DH_HIP(hipMemcpy(plan.d_start, start.data(), sb, hipMemcpyHostToDevice));
+    DH_HIP(hipMemcpy(plan.d_tiles, tiles.data(), tb, hipMemcpyHostToDevice));
+    DH_HIP(hipMemcpy(plan.d_yx, yx_host, yb, hipMemcpyHostToDevice));
+    plan.yx.assign(yx_host, yx_host + 2 * n);
+    plan.P = P; plan.d = d; plan.h = h; plan.w = w; plan.nbins = nbins; plan.total = total; plan.G = G;
+    plan.bins_x = (int)bins_x; plan.device = dev_id;
+  }
+  *out = BinPlan{plan.G, (int32_t)plan.bins_x, plan.nbins, plan.total, plan.d_start, plan.d_tiles, plan.d_yx};
+  return DH_OK;
+}
+}  // namespace dh
+
 extern "C" int dh_accumulate_logits(const float* logits, const int32_t* yx_host, int64_t n,
                                     int32_t P, int32_t d, int32_t n_cls, int64_t h, int64_t w,
                                     float* canvas, int64_t* map, void* stream) {
@@ -530,63 +595,10 @@ extern "C" int dh_accumulate_logits(const float* logits, const int32_t* yx_host,
   if (dh_ == 0 || dw_ == 0) return DH_OK;
   DH_REQUIRE(dh_ * dw_ <= (int64_t)INT32_MAX, "accumulate: canvas too large");
   if (n > 0) {
-    // The bin lists depend only on (origins, P, d, h, w): whole-slide prediction repeats the same
-    // grid slide after slide, so the last plan (host CSR + its device copies) is kept and reused
-    // when the origins compare equal -- no rebuild, no upload, no stream synchronisation.
-    struct Plan {
-      std::vector<int32_t> yx; int32_t P = 0, d = 0; int64_t h = 0, w = 0, nbins = 0, total = 0; int G = 0, bins_x = 0;
-      int32_t *d_start = nullptr, *d_tiles = nullptr, *d_yx = nullptr; int device = -1;
-    };
-    static thread_local Plan plan;
-    int dev_id = 0;
-    DH_HIP(hipGetDevice(&dev_id));
-    const bool hit = plan.device == dev_id && plan.P == P && plan.d == d && plan.h == h && plan.w == w &&
-                     (int64_t)plan.yx.size() == 2 * n && memcmp(plan.yx.data(), yx_host, (size_t)n * 8) == 0;
-    if (!hit) {
-      const int G = std::max(1, std::min(P / d, 64));
-      const int64_t bins_y = (dh_ + G - 1) / G, bins_x = (dw_ + G - 1) / G;
-      const int64_t nbins = bins_y * bins_x;
-      DH_REQUIRE(nbins < INT32_MAX, "accumulate: too many bins");
-      std::vector<int32_t> start(nbins + 1, 0);
-      auto span = [&](int64_t i, int64_t& cy0, int64_t& cy1, int64_t& cx0, int64_t& cx1) {
-        const int64_t y = yx_host[2 * i], x = yx_host[2 * i + 1];
-        cy0 = std::max<int64_t>(y / d, 0); cy1 = std::min<int64_t>((y + P) / d, dh_);
-        cx0 = std::max<int64_t>(x / d, 0); cx1 = std::min<int64_t>((x + P) / d, dw_);
-        return y >= 0 && x >= 0 && cy1 > cy0 && cx1 > cx0;
-      };
-      int64_t total = 0;
-      for (int64_t i = 0; i < n; ++i) {
-        int64_t a, b, c, e;
-        DH_REQUIRE(yx_host[2 * i] >= 0 && yx_host[2 * i + 1] >= 0, "accumulate: negative origin");
-        if (!span(i, a, b, c, e)) continue;
-        for (int64_t by = a / G; by <= (b - 1) / G; ++by)
-          for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) { ++start[by * bins_x + bx + 1]; ++total; }
-      }
-      DH_REQUIRE(total < INT32_MAX, "accumulate: incidence list too long");
-      for (int64_t b = 0; b < nbins; ++b) start[b + 1] += start[b];
-      std::vector<int32_t> fill(start.begin(), start.end() - 1), tiles((size_t)std::max<int64_t>(total, 1));
-      for (int64_t i = 0; i < n; ++i) {
-        int64_t a, b, c, e;
-        if (!span(i, a, b, c, e)) continue;
-        for (int64_t by = a / G; by <= (b - 1) / G; ++by)
-          for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) tiles[fill[by * bins_x + bx]++] = (int32_t)i;
-      }
-      DH_HIP(hipStreamSynchronize(st));  // the previous plan's buffers may still be in use on this stream
-      if (plan.d_start) { (void)hipFree(plan.d_start); (void)hipFree(plan.d_tiles); (void)hipFree(plan.d_yx); }
-      plan = Plan();
-      const size_t sb = (size_t)(nbins + 1) * 4, tb = (size_t)std::max<int64_t>(total, 1) * 4, yb = (size_t)n * 8;
-      DH_HIP(hipMalloc((void**)&plan.d_start, sb));
-      DH_HIP(hipMalloc((void**)&plan.d_tiles, tb));
-      DH_HIP(hipMalloc((void**)&plan.d_yx, yb));
-      DH_HIP(hipMemcpy(plan.d_start, start.data(), sb, hipMemcpyHostToDevice));
-      DH_HIP(hipMemcpy(plan.d_tiles, tiles.data(), tb, hipMemcpyHostToDevice));
-      DH_HIP(hipMemcpy(plan.d_yx, yx_host, yb, hipMemcpyHostToDevice));
-      plan.yx.assign(yx_host, yx_host + 2 * n);
-      plan.P = P; plan.d = d; plan.h = h; plan.w = w; plan.nbins = nbins; plan.total = total; plan.G = G;
-      plan.bins_x = (int)bins_x; plan.device = dev_id;
-    }
+    dh::BinPlan plan;
+    if (const int rc = dh::bin_plan(yx_host, n, P, d, h, w, st, &plan)) return rc;
     if (plan.total > 0) {
-      BinGeom g{plan.G, (int32_t)plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
+      dh::BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
       hipLaunchKernelGGL(accumulate_bins_kernel, dim3((unsigned)plan.nbins), dim3(256), 0, st, logits, plan.d_yx,
                          plan.d_start, plan.d_tiles, g, canvas);
       DH_LAUNCH_CHECK();

@@ -8,7 +8,9 @@ tile ranges are sharded over the ranks of a torch.distributed job (RCCL over
 xGMI), every rank runs fused gather+ResNet-18 on its range, per-tile logits are
 all-gathered, and the ordered accumulation + argmax run once; and
 `predict_random_patched(...)`, the same for the random sampler's branch (device
-coverage map, large forward launches, one ordered accumulation).
+coverage map, large forward launches, one ordered accumulation).  With `return_proba=True` both also return
+the per-cell mean softmax probabilities, hit counts, their class map and confidence (`tiles.SlideProbabilities`,
+DESIGN.md section 4.8); `ImagePredictorPatched.process_proba()` is the same for the callback route.
 """
 from __future__ import annotations
 
@@ -53,6 +55,7 @@ class ImagePredictorPatched:
         self.layer = layer
         self.downscale = downscale
         self.device = torch.device(device)
+        self._cached_runs = None
         if isinstance(psim_path, (tuple, list)):  # (h, w) given directly
             self.h, self.w = int(psim_path[0]), int(psim_path[1])
         elif isinstance(psim_path, torch.Tensor):
@@ -66,6 +69,32 @@ class ImagePredictorPatched:
         batch_predictor like the reference (predict_full_patched.py:47-48); the per-patch
         `prediction[...] += logits` loop and the argmax (:49-62) run on the GPU, in the
         same order (padding duplicates included), once all batches are in."""
+        canvas, cmap = None, None
+        for ps, origins, logits in self._runs():
+            canvas, cmap = tiles.accumulate_logits(logits, origins, ps, self.downscale, self.h, self.w, canvas=canvas)
+        if cmap is None:
+            return np.zeros((self.h // self.downscale, self.w // self.downscale), dtype=np.int64)
+        return cmap.cpu().numpy()
+
+    def process_proba(self, fill_class: int = -1) -> tiles.SlideProbabilities:
+        """The callback route of process() with the probability finish: the softmax of every patch's
+        logits is summed and counted per cell in the sampler's order, then divided.  Returns a tiles.SlideProbabilities on
+        `device` (proba, count, class_map = argmax of the mean probability, confidence); cells no patch covered hold
+        `fill_class`.  process() and its argmax of logit sums are unchanged."""
+        runs = self._runs() or [(1, np.zeros((0, 2), np.int32),
+                                 torch.zeros((0, _n_classes(self.anno)), dtype=torch.float32, device=self.device))]
+        state = None
+        for k, (ps, origins, logits) in enumerate(runs):
+            state = tiles.accumulate_probabilities(logits, origins, ps, self.downscale, self.h, self.w, state=state,
+                                                   fill_class=fill_class, finish=k == len(runs) - 1)
+        return state
+
+    def _runs(self) -> list[tuple[int, np.ndarray, torch.Tensor]]:
+        """Iterates the sampler and the batch_predictor once: (patch_size, int32 origins, float32 device logits) per run of
+        patches of one size, in the sampler's order.  Kept, so that process() and process_proba() of one predictor share the
+        one pass a sampler's generator allows."""
+        if self._cached_runs is not None:
+            return self._cached_runs
         n = _n_classes(self.anno)
         runs: list[tuple[int, list, list]] = []  # (patch_size, origins, logits) per run of equal size
         for patches, _progress in self.patch_sampler:
@@ -81,14 +110,9 @@ class ImagePredictorPatched:
                     runs.append((p.patch_size, [], []))
                 runs[-1][1].append((p.pos_y, p.pos_x))
                 runs[-1][2].append(preds[i:i + 1])
-        canvas, cmap = None, None
-        for ps, origins, logit_rows in runs:
-            logits = torch.cat(logit_rows).to(self.device).contiguous()
-            canvas, cmap = tiles.accumulate_logits(logits, np.asarray(origins, dtype=np.int32), ps,
-                                                   self.downscale, self.h, self.w, canvas=canvas)
-        if cmap is None:
-            return np.zeros((self.h // self.downscale, self.w // self.downscale), dtype=np.int64)
-        return cmap.cpu().numpy()
+        self._cached_runs = [(ps, np.asarray(origins, dtype=np.int32), torch.cat(logit_rows).to(self.device).contiguous())
+                             for ps, origins, logit_rows in runs]
+        return self._cached_runs
 
 
 def batch_predictor(patches: list[Patch], model, device) -> np.ndarray:
@@ -191,7 +215,7 @@ def exchange_logits(local: torch.Tensor, n_unique: int, group=None) -> torch.Ten
 def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
                          downscale: int = 16, micro_batch: int | None = None, group=None,
                          return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None,
-                         tissue: TissueFilter | None = None, tissue_info: dict | None = None):
+                         tissue: TissueFilter | None = None, tissue_info: dict | None = None, return_proba: bool = False):
     """Device-resident whole-slide prediction (rows a1-a8 end to end).
 
     `model`: ResNet18HIP or ResNet50HIP; it names its own fused entry (`tiles_entry`) and launch size
@@ -213,6 +237,12 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     `tissue.fill_class`.  The result is the unmasked computation with the rejected tiles' logits left out.  Needs a resident
     dense sampler.  `tissue_info`: a dict that receives threshold, min_pixels, n_tiles, n_kept, kept (int64 indices into the
     unique tiles) and, after Otsu, histogram.
+    `return_proba=True` appends a tiles.SlideProbabilities to what is returned: per-cell mean softmax probability, hit
+    count, argmax of the mean and confidence, from the same logits and the same tile list as the
+    class map (so sharded, streamed and `dedupe_padding` runs give it too).  By default the corner tile's padding duplicates
+    are added and counted like every other list entry, which weights the corner tile 1 + pad times in its footprint;
+    `dedupe_padding=True` removes that.  With `tissue` it runs over the kept tiles only (a rejected tile's NaN row never
+    enters a softmax) and uncovered cells get `tissue.fill_class`.
     Returns int64[h//d, w//d] on the device (and the float32[n_padded, n_cls] logits; rows of rejected tiles are NaN).
     """
     import torch.distributed as dist
@@ -291,22 +321,26 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     pad = n_padded - n_unique
     if kept is not None:
         return _finish_masked(sampler, logits_unique, kept, kept_yx_dev, n_classes, downscale, dedupe_padding, tissue,
-                              return_logits)
+                              return_logits, return_proba)
     logits = torch.cat([logits_unique, logits_unique[-1:].expand(pad, -1)]) if pad else logits_unique
-    if dedupe_padding:
-        _, cmap = tiles.accumulate_logits(logits_unique.contiguous(), origins[:n_unique], P, downscale, sampler.h, sampler.w)
-    else:
-        _, cmap = tiles.accumulate_logits(logits.contiguous(), origins, P, downscale, sampler.h, sampler.w)
-    return (cmap, logits) if return_logits else cmap
+    acc, yx = (logits_unique.contiguous(), origins[:n_unique]) if dedupe_padding else (logits.contiguous(), origins)
+    _, cmap = tiles.accumulate_logits(acc, yx, P, downscale, sampler.h, sampler.w)
+    out = (cmap, logits) if return_logits else (cmap,)
+    if return_proba:   # the same list right after the class map: the bin plan is reused
+        out += (tiles.accumulate_probabilities(acc, yx, P, downscale, sampler.h, sampler.w),)
+    return out if len(out) > 1 else cmap
 
 
-def _finish_masked(sampler, logits_kept, kept, kept_yx_dev, n_classes, downscale, dedupe_padding, tissue, return_logits):
+def _finish_masked(sampler, logits_kept, kept, kept_yx_dev, n_classes, downscale, dedupe_padding, tissue, return_logits,
+                   return_proba=False):
     """The tissue-filtered tail of predict_full_patched: ordered accumulation over the kept tiles (plus the corner's padding
-    duplicates when the corner is kept), argmax, fill of the uncovered cells; logits scattered back to the padded list."""
+    duplicates when the corner is kept), argmax, fill of the uncovered cells; logits scattered back to the padded list.
+    The probabilities run over the same kept list; cells it does not cover have count 0 and the fill class."""
     origins, n_unique, P = sampler.origins, sampler.n_tiles, sampler.patch_size
     h, w, dev = sampler.h, sampler.w, logits_kept.device
     pad = len(origins) - n_unique
     k = len(kept)
+    acc, yx = logits_kept[:0].reshape(0, n_classes), origins[:0]
     if k == 0:   # all glass: no forward ran, every cell is uncovered
         cmap = torch.zeros((h // downscale, w // downscale), dtype=torch.int64, device=dev)
     else:
@@ -316,18 +350,20 @@ def _finish_masked(sampler, logits_kept, kept, kept_yx_dev, n_classes, downscale
             yx = np.concatenate([yx, origins[n_unique:]])
         _, cmap = tiles.accumulate_logits(acc.contiguous(), yx, P, downscale, h, w)
     fill_uncovered(cmap, kept_yx_dev, P, downscale, h, w, tissue.fill_class)
+    proba = ((tiles.accumulate_probabilities(acc.contiguous(), yx, P, downscale, h, w, fill_class=tissue.fill_class),)
+             if return_proba else ())
     if not return_logits:
-        return cmap
+        return (cmap, *proba) if proba else cmap
     logits = torch.full((len(origins), n_classes), float("nan"), dtype=torch.float32, device=dev)
     if k:
         logits[torch.from_numpy(kept).to(dev)] = logits_kept
     if pad:
         logits[n_unique:] = logits[n_unique - 1]
-    return cmap, logits
+    return (cmap, logits, *proba)
 
 
 def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
-                           return_canvas: bool = False, timing: dict | None = None):
+                           return_canvas: bool = False, timing: dict | None = None, return_proba: bool = False):
     """The reference's default branch (FullImageRndSampler through ImagePredictorPatched.process(),
     predict_full_patched.py:40-63, 150-162) with the random sampler's device index logic and large forward launches.
 
@@ -338,6 +374,9 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     accumulated in sampler order with ONE ordered accumulate at the end.  Large and small launches give identical
     logits, so the class map and canvas are bit-identical to the callback path under the same NumPy seed.
     `timing` (a dict) receives n_batches, n_tiles, host_s (planning + stepping wall time) and wall_s.
+    `return_proba=True` appends a tiles.SlideProbabilities built from the same logits and origin
+    sequence: under this sampler a cell is covered anything from `dense_level` to dozens of times, and `count` is what makes
+    its probabilities comparable from cell to cell.
     Returns int64[h//d, w//d] on the device (and the float32 canvas when `return_canvas`)."""
     import time
 
@@ -394,10 +433,14 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     with torch.cuda.stream(main):
         lg = torch.cat(logits) if len(logits) > 1 else logits[0]
         canvas, cmap = tiles.accumulate_logits(lg.contiguous(), origins, P, downscale, sampler.h, sampler.w)
+        proba = tiles.accumulate_probabilities(lg.contiguous(), origins, P, downscale, sampler.h, sampler.w) if return_proba else None
     if timing is not None:
         torch.cuda.synchronize(dev)
         timing.update(n_batches=n_batches, n_tiles=int(origins.shape[0]), host_s=host_s, wall_s=time.perf_counter() - t0)
-    return (cmap, canvas) if return_canvas else cmap
+    out = (cmap, canvas) if return_canvas else (cmap,)
+    if return_proba:
+        out += (proba,)
+    return out if len(out) > 1 else cmap
 
 
 def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor, n_classes: int, micro_batch: int, model):
@@ -450,15 +493,22 @@ def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor,
 
 
 def perform_and_save_visualizations(img, anno_dsc, pred, out_dir: Path = Path("."), stem: str | None = None,
-                                    alpha: float = 0.6, save: bool = True, device="cuda"):
+                                    alpha: float = 0.6, save: bool = True, device="cuda", proba=None, heat_classes=()):
     """Colourised class mask, the slide at the map's resolution and their overlay -- predict_full_patched.py:81-113.
 
     `img`: path (psimage, when installed: `get_region(..., target_hw)` as the reference) or a uint8[H,W,3]
     array / GPU tensor, which is sampled at the map's resolution by nearest source pixel (psimage's own
     resampler is third-party and unknown here).  The colour lookup and the float64 blend run on the GPU
     (`dh_colorize_map`, `dh_overlay_blend`) and are bit-identical to the reference's NumPy lines.
+    `proba`: the run's tiles.SlideProbabilities; with `save`, `{stem}_confidence.jpg` (the confidence in white over the slide)
+    and one `{stem}_heat_{label}.jpg` per label of `heat_classes` (that class's mean probability in the class colour) are
+    written as well (`dh_heatmap_blend`, float64 like the overlay).
     Returns (mask, image, overlay) as uint8[h, w, 3] NumPy arrays; JPEGs are written when `save`."""
     dev = torch.device(device)
+    by_label = {a.label: a for a in anno_dsc.anno_classes}
+    unknown = [lb for lb in heat_classes if lb not in by_label]
+    if unknown or (heat_classes and proba is None):
+        raise ValueError(f"heat_classes {list(heat_classes)}: needs proba and labels out of {', '.join(by_label)}")
     pred_t = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred))
     pred_t = pred_t.to(dev, torch.int64).contiguous()
     h, w = int(pred_t.shape[0]), int(pred_t.shape[1])
@@ -487,6 +537,12 @@ def perform_and_save_visualizations(img, anno_dsc, pred, out_dir: Path = Path(".
         Image.fromarray(mask_np).save(out_dir / f"{stem}_mask.jpg", quality=95)
         Image.fromarray(img_np).save(out_dir / f"{stem}.jpg", quality=95)
         Image.fromarray(ov_np).save(out_dir / f"{stem}_overlay.jpg", quality=95)
+        if proba is not None:
+            heat = tiles.heatmap_blend(small, proba.confidence.to(dev), (255, 255, 255), alpha)
+            Image.fromarray(heat.cpu().numpy()).save(out_dir / f"{stem}_confidence.jpg", quality=95)
+            for lb in heat_classes:
+                heat = tiles.heatmap_blend(small, proba.proba.to(dev)[..., by_label[lb].id], by_label[lb].color, alpha)
+                Image.fromarray(heat.cpu().numpy()).save(out_dir / f"{stem}_heat_{lb}.jpg", quality=95)
     return mask_np, img_np, ov_np
 
 
@@ -526,6 +582,29 @@ def _tissue_from_args(ap, args) -> TissueFilter | None:
         ap.error(f"--tissue {args.tissue} / --tissue_min_fraction {args.tissue_min_fraction}: {e}")
 
 
+def _proba_from_args(ap, args) -> None:
+    """Checks the --proba flags; a bad combination or an unknown class label is an argparse error."""
+    if args.heat and not args.proba:
+        ap.error("--heat needs --proba")
+    if args.save_proba and not args.proba:
+        ap.error("--save_proba needs --proba")
+    for lb in args.heat:
+        if lb not in KNOWN_COLORS:
+            ap.error(f"--heat labels must be out of {', '.join(KNOWN_COLORS)}, not {lb!r}")
+
+
+def save_proba(path, proba) -> tuple[Path, Path]:
+    """Writes `proba.proba` as float16 to `path` (.npy) and `proba.count` to the same name with `_count` before the suffix."""
+    path = Path(path)
+    if path.suffix != ".npy":
+        path = path.with_name(path.name + ".npy")
+    path.parent.mkdir(exist_ok=True, parents=True)
+    count_path = path.with_name(path.stem + "_count.npy")
+    np.save(path, proba.proba.cpu().numpy().astype(np.float16))
+    np.save(count_path, proba.count.cpu().numpy())
+    return path, count_path
+
+
 def main(argv=None, model=None):
     """The reference's `__main__` (predict_full_patched.py:128-177) as a per-rank program.
 
@@ -540,6 +619,9 @@ def main(argv=None, model=None):
     `--arch auto` reads the backbone from the checkpoint (ResNet-50 when it has `layer1.0.conv3.weight`).
     `--tissue otsu|<0..255>` classifies only the tiles that hold tissue (dense branch, resident slide; TissueFilter), with
     `--tissue_min_fraction` and `--tissue_fill` (a class label, or -1 for no class) for the cells no kept tile covers.
+    `--proba` also computes the per-cell mean softmax probabilities (DESIGN.md section 4.8) and writes the confidence JPEG;
+    `--heat LABEL ...` adds one heat map per class label; `--save_proba PATH` writes the probabilities as float16 PATH(.npy) and
+    the hit counts as PATH_count.npy (rank 0).  The returned class map stays the argmax of the logit sums.
     `model`: an injected module (tests)."""
     import argparse
 
@@ -569,8 +651,14 @@ def main(argv=None, model=None):
     ap.add_argument("--tissue_min_fraction", type=float, default=0.25,
                     help="share of a tile's pixels that must be tissue (0.25: a conventional default, not validated here)")
     ap.add_argument("--tissue_fill", default="-1", help="class label for cells no kept tile covers, or -1 (no class)")
+    ap.add_argument("--proba", action="store_true", help="per-cell mean softmax probabilities; writes {stem}_confidence.jpg")
+    ap.add_argument("--heat", nargs="+", default=[], metavar="LABEL",
+                    help=f"with --proba: one {{stem}}_heat_LABEL.jpg per class label ({', '.join(KNOWN_COLORS)})")
+    ap.add_argument("--save_proba", default=None, metavar="PATH",
+                    help="with --proba: probabilities as float16 PATH(.npy), hit counts as PATH_count.npy (rank 0)")
     args = ap.parse_args(argv)
     tissue = _tissue_from_args(ap, args)
+    _proba_from_args(ap, args)
 
     rank, world, _dev_index, owned = init_from_env()   # binds the rank's GPU before any other GPU call
     ok = False
@@ -601,24 +689,36 @@ def main(argv=None, model=None):
                                    "the dense sampler is the multi-GPU path")
             smp = FullImageRndSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                       mode=mode, device=device)
+            proba = None
             if smp.resident and smp.index_logic == "device" and isinstance(model, ResNetHIP):
-                pred = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis).cpu().numpy()
+                pred = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis, return_proba=args.proba)
+                if args.proba:
+                    pred, proba = pred
+                pred = pred.cpu().numpy()
             else:   # a foreign module or a slide streamed from disk: the reference's callback loop
-                pred = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),
-                                             batch_predictor=lambda patches: batch_predictor(patches, model, device),
-                                             anno=anno_dsc, layer=args.layer, downscale=args.downscale_vis,
-                                             device=device).process()
+                predictor = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),
+                                                  batch_predictor=lambda patches: batch_predictor(patches, model, device),
+                                                  anno=anno_dsc, layer=args.layer, downscale=args.downscale_vis, device=device)
+                pred = predictor.process()
+                if args.proba:
+                    proba = predictor.process_proba()
         else:
             smp = FullImageDenseSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                         mode=mode, stride=args.stride, device=device)
             info: dict = {}
             pred = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
-                                        tissue=tissue, tissue_info=info)
+                                        tissue=tissue, tissue_info=info, return_proba=args.proba)
+            proba = None
+            if args.proba:
+                pred, proba = pred
             if tissue is not None and rank == 0:
                 print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
         if rank == 0 and not args.no_visualizations:
             src = img if isinstance(img, torch.Tensor) or not smp.resident else smp.data_device
-            perform_and_save_visualizations(src, anno_dsc, pred, out_dir=Path(args.out_dir), stem=stem, device=device)
+            perform_and_save_visualizations(src, anno_dsc, pred, out_dir=Path(args.out_dir), stem=stem, device=device,
+                                            proba=proba, heat_classes=args.heat)
+        if rank == 0 and args.save_proba:
+            save_proba(args.save_proba, proba)
         if world > 1:
             dist.barrier()
         ok = True

@@ -224,6 +224,116 @@ def overlay_blend(img: torch.Tensor, colored: torch.Tensor, alpha: float = 0.6) 
     return out
 
 
+def softmax_rows(logits: torch.Tensor) -> torch.Tensor:
+    """float32[n, n_cls] per-row softmax (dh_softmax_rows): m = max_c x_c, e_c = expf(x_c - m), s = e_0 + e_1 + ... in class
+    order, p_c = e_c / s; n_cls <= 64."""
+    _require_cuda(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError("logits must be float32[n, n_cls]")
+    out = torch.empty_like(logits)
+    check(lib().dh_softmax_rows(logits.data_ptr(), int(logits.shape[0]), int(logits.shape[1]), out.data_ptr(),
+                                _stream(logits.device)), "dh_softmax_rows")
+    return out
+
+
+class SlideProbabilities:
+    """Per-cell mean softmax probability of a whole-slide prediction, on the device:
+    `proba` f32[dh, dw, n_cls], `count` i32[dh, dw] (tiles that covered the cell), `class_map` i64[dh, dw] (first maximum of
+    `proba`; `fill_class` where count == 0) and `confidence` f32[dh, dw] (= proba[class_map]; 0 where count == 0).
+    While `finished` is False (accumulate_probabilities(..., finish=False)) `proba` holds the running SUMS and `class_map` /
+    `confidence` are None: the state to continue from with `state=`; `finish()` ends it in place."""
+
+    def __init__(self, proba: torch.Tensor, count: torch.Tensor, class_map: torch.Tensor | None = None,
+                 confidence: torch.Tensor | None = None, fill_class: int = -1):
+        self.proba, self.count, self.class_map, self.confidence = proba, count, class_map, confidence
+        self.fill_class = int(fill_class)
+
+    @property
+    def finished(self) -> bool:
+        return self.class_map is not None
+
+    def _outputs(self):
+        self.class_map = torch.empty(tuple(self.count.shape), dtype=torch.int64, device=self.count.device)
+        self.confidence = torch.empty(tuple(self.count.shape), dtype=torch.float32, device=self.count.device)
+
+    def finish(self, fill_class: int = -1) -> "SlideProbabilities":
+        """sums -> mean probabilities in place, class map, confidence (dh_finish_mean)."""
+        if self.finished:
+            raise ValueError("state is already finished: its sums have been divided by the counts")
+        self._outputs()
+        self.fill_class = int(fill_class)
+        check(lib().dh_finish_mean(self.proba.data_ptr(), self.count.data_ptr(), self.count.numel(), int(self.proba.shape[2]),
+                                   self.fill_class, self.proba.data_ptr(), self.class_map.data_ptr(),
+                                   self.confidence.data_ptr(), _stream(self.proba.device)), "dh_finish_mean")
+        return self
+
+
+def accumulate_probabilities(logits: torch.Tensor, origins_host: np.ndarray, patch: int, downscale: int, h: int, w: int,
+                             state: SlideProbabilities | None = None, fill_class: int = -1,
+                             finish: bool = True) -> SlideProbabilities:
+    """Softmax of every tile's logits, ordered per-cell sums and hit counts over the footprints of `accumulate_logits` (same
+    list, same order, padding duplicates included), then mean = sum / count, its first-maximum class and the confidence
+    (dh_softmax_rows, dh_accumulate_mean with the finish fused in).  `state`: an unfinished SlideProbabilities to continue
+    from (runs of different patch size chain: all but the last call with finish=False).  An empty list is allowed."""
+    _require_cuda(logits, "logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise ValueError("logits must be float32[n, n_cls]")
+    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
+    n, n_cls = int(logits.shape[0]), int(logits.shape[1])
+    if yx.shape[0] != n:
+        raise ValueError(f"{n} logit rows but {yx.shape[0]} origins")
+    if not 1 <= n_cls <= 64:
+        raise ValueError(f"n_cls = {n_cls}: the probability kernels take 1 to 64 classes")
+    dh_, dw_ = h // downscale, w // downscale
+    if state is None:
+        state = SlideProbabilities(torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=logits.device),
+                                   torch.zeros((dh_, dw_), dtype=torch.int32, device=logits.device))
+    else:
+        if not isinstance(state, SlideProbabilities):
+            raise ValueError("state must be a SlideProbabilities")
+        if state.finished:
+            raise ValueError("state is already finished (its sums were divided): continue from finish=False results only")
+        for t, what, dt, shape in ((state.proba, "state.proba", torch.float32, (dh_, dw_, n_cls)),
+                                   (state.count, "state.count", torch.int32, (dh_, dw_))):
+            _require_cuda(t, what)
+            if t.dtype != dt or tuple(t.shape) != shape:
+                raise ValueError(f"{what} must be {str(dt).replace('torch.', '')}{list(shape)} "
+                                 f"(canvas h//d x w//d of this call), not {str(t.dtype).replace('torch.', '')}{list(t.shape)}")
+    probs = softmax_rows(logits)
+    if finish:
+        state._outputs()
+        state.fill_class = int(fill_class)
+    check(lib().dh_accumulate_mean(probs.data_ptr() if n else None, yx.ctypes.data_as(C.c_void_p) if n else None, n, patch,
+                                   downscale, n_cls, h, w, state.proba.data_ptr(), state.count.data_ptr(),
+                                   state.class_map.data_ptr() if finish else None,
+                                   state.confidence.data_ptr() if finish else None, int(fill_class),
+                                   _stream(logits.device)), "dh_accumulate_mean")
+    return state
+
+
+def heatmap_blend(img: torch.Tensor, field: torch.Tensor, color, alpha: float = 0.6) -> torch.Tensor:
+    """`(img * alpha + (float64(field)[..., None] * color) * (1 - alpha)).astype(uint8)` in float64 (dh_heatmap_blend).
+    `img` uint8[h, w, 3]; `field` float32[h, w]: one class of the probabilities (`proba[..., k]`, read in place) or the
+    confidence; `color`: three values 0..255."""
+    _require_cuda(img, "img")
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError("img must be uint8[h, w, 3]")
+    if not field.is_cuda or field.dtype != torch.float32 or tuple(field.shape) != tuple(img.shape[:2]):
+        raise ValueError("field must be a float32[h, w] GPU tensor of img's height and width")
+    col = np.asarray(color)
+    if col.shape != (3,) or (col < 0).any() or (col > 255).any() or (col != np.floor(col)).any():
+        raise ValueError(f"color must be three integers in [0, 255], not {color!r}")
+    col = np.ascontiguousarray(col, dtype=np.uint8)
+    h, w = int(field.shape[0]), int(field.shape[1])
+    step = field.stride(1) if w > 1 else 1
+    if h * w and (step < 1 or (h > 1 and field.stride(0) != step * w)):   # one class of [h, w, n] is evenly spaced: no copy
+        field, step = field.contiguous(), 1
+    out = torch.empty_like(img)
+    check(lib().dh_heatmap_blend(img.data_ptr(), field.data_ptr(), step, h * w, col.ctypes.data_as(C.c_void_p), float(alpha),
+                                 out.data_ptr(), _stream(img.device)), "dh_heatmap_blend")
+    return out
+
+
 class CoverageMap:
     """The device coverage map of FullImageRndSampler (`dh_coverage_*`, csrc/coverage.hip): int32 hit counts [dh, dw]
     at 1/speedup scale, rank -> cell -> origin -> hits per batch.  The narrow interface of coverage.CoveragePlanner:

@@ -138,6 +138,33 @@ int dh_colorize_map(const int64_t* map_dev, int64_t n_cells, const uint8_t* lut_
 int dh_overlay_blend(const uint8_t* img_dev, const uint8_t* colored_dev, int64_t n_bytes, double alpha,
                      uint8_t* out_dev, void* stream);
 
+/* ---- whole-slide probability maps ---------------------------------
+ * The `count` array and the `prediction /= count` line that examples/predict_full_patched.py:45, 55-58, 61 carry commented
+ * out, over per-tile softmax probabilities instead of raw logits.  All float32; tile list, footprints
+ * (rows y/d .. (y+P)/d, columns x/d .. (x+P)/d, clipped) and order are those of dh_accumulate_logits, one writer per cell,
+ * no atomics: every output is bit-identical to the sequential NumPy loop.
+ * dh_softmax_rows: probs[i][c] = e_c / s with m = max_c x_c, e_c = expf(x_c - m), s = e_0 + e_1 + ... in class order;
+ *   logits_dev, probs_dev: float32[n][n_cls], n_cls <= 64; probs_dev may be logits_dev.
+ * dh_accumulate_mean: sum_dev[cell][:] += probs[t][:] and count_dev[cell] += 1 for every tile t covering the cell, in list
+ *   order (duplicates included).  sum_dev float32[dh][dw][n_cls] and count_dev int32[dh][dw] are accumulated into (zero both
+ *   for a fresh slide), so runs of different patch size chain.  map_dev / confidence_dev (both or neither, may be NULL):
+ *   when given, the finish below runs in the same pass, in place: sum_dev then holds the probabilities.  Shares the cached
+ *   bin plan of dh_accumulate_logits (the same origins right after it cost no rebuild).  n = 0 is allowed.
+ * dh_finish_mean: where count > 0: proba = sum / float32(count), map = first index of the maximum of proba (NumPy argmax
+ *   tie/NaN rule), confidence = proba[map]; where count == 0: proba = 0, confidence = 0, map = fill_class.
+ *   proba_dev may be sum_dev.  map_dev int64[n_cells], confidence_dev float32[n_cells].
+ * dh_heatmap_blend: out[i][c] = uint8(img[i][c] * alpha + (float64(field[i * field_stride]) * color[c]) * (1 - alpha)) in
+ *   float64, truncating like NumPy's cast; img_dev, out_dev: uint8[n_cells][3]; field_dev: float32, one value per cell,
+ *   field_stride elements apart (n_cls for one class of the probabilities, 1 for the confidence); color_host: uint8[3]. */
+int dh_softmax_rows(const float* logits_dev, int64_t n, int32_t n_cls, float* probs_dev, void* stream);
+int dh_accumulate_mean(const float* probs_dev, const int32_t* yx_host, int64_t n, int32_t patch, int32_t downscale,
+                       int32_t n_cls, int64_t h, int64_t w, float* sum_dev, int32_t* count_dev, int64_t* map_dev,
+                       float* confidence_dev, int32_t fill_class, void* stream);
+int dh_finish_mean(const float* sum_dev, const int32_t* count_dev, int64_t n_cells, int32_t n_cls, int32_t fill_class,
+                   float* proba_dev, int64_t* map_dev, float* confidence_dev, void* stream);
+int dh_heatmap_blend(const uint8_t* img_dev, const float* field_dev, int64_t field_stride, int64_t n_cells,
+                     const uint8_t* color_host, double alpha, uint8_t* out_dev, void* stream);
+
 /* ---- a6: ResNet-18 patch classifier forward ---------------------------------
  * Replaces `model(features)` for the network built by get_model
  * (models/patch_cls_simple/model.py:5-11: torchvision resnet18 + fc[n_cls,512])
