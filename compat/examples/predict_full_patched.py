@@ -2,6 +2,8 @@
 from deephisto_amd.examples.predict_full_patched import (ImagePredictorPatched, batch_predictor, load_model, main,  # noqa: F401
                                                          perform_and_save_visualizations, predict_full_patched,
                                                          predict_random_patched, save_proba)
+from deephisto_amd.examples.predict_full_patched import (SlideScore, confusion, rasterize_annotation, save_score,  # noqa: F401
+                                                         score_prediction)
 
 if __name__ == "__main__":
     main()

@@ -11,6 +11,8 @@ all-gathered, and the ordered accumulation + argmax run once; and
 coverage map, large forward launches, one ordered accumulation).  With `return_proba=True` both also return
 the per-cell mean softmax probabilities, hit counts, their class map and confidence (`tiles.SlideProbabilities`,
 DESIGN.md section 4.8); `ImagePredictorPatched.process_proba()` is the same for the callback route.
+`score_prediction(pred, anno, ...)` (deephisto_amd.scoring) scores any of these maps against the
+slide's polygon annotation; the CLI does so with `--anno PATH [--score_json PATH]`.
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..psimage_compat import Patch, open_slide
+from ..scoring import SlideScore, confusion, rasterize_annotation, save_score, score_prediction  # noqa: F401  (exported here)
 from ..tissue import TissueFilter, fill_uncovered, score_tiles
 
 
@@ -493,7 +496,8 @@ def _forward_streamed(sampler, handle, origins: np.ndarray, local: torch.Tensor,
 
 
 def perform_and_save_visualizations(img, anno_dsc, pred, out_dir: Path = Path("."), stem: str | None = None,
-                                    alpha: float = 0.6, save: bool = True, device="cuda", proba=None, heat_classes=()):
+                                    alpha: float = 0.6, save: bool = True, device="cuda", proba=None, heat_classes=(),
+                                    truth=None, outcome=None):
     """Colourised class mask, the slide at the map's resolution and their overlay -- predict_full_patched.py:81-113.
 
     `img`: path (psimage, when installed: `get_region(..., target_hw)` as the reference) or a uint8[H,W,3]
@@ -503,6 +507,9 @@ def perform_and_save_visualizations(img, anno_dsc, pred, out_dir: Path = Path(".
     `proba`: the run's tiles.SlideProbabilities; with `save`, `{stem}_confidence.jpg` (the confidence in white over the slide)
     and one `{stem}_heat_{label}.jpg` per label of `heat_classes` (that class's mean probability in the class colour) are
     written as well (`dh_heatmap_blend`, float64 like the overlay).
+    `truth` / `outcome`: the label map and the outcome map of a scored run (`scoring.score_prediction(..., return_maps=True)`);
+    with `save`, `{stem}_truth.jpg` (the labels in the class colours, unlabelled cells black) and `{stem}_errors.jpg` (correct
+    cells green, wrong cells red, blended over the slide with `alpha` like the overlay; unlabelled cells black) are written.
     Returns (mask, image, overlay) as uint8[h, w, 3] NumPy arrays; JPEGs are written when `save`."""
     dev = torch.device(device)
     by_label = {a.label: a for a in anno_dsc.anno_classes}
@@ -543,6 +550,13 @@ def perform_and_save_visualizations(img, anno_dsc, pred, out_dir: Path = Path(".
             for lb in heat_classes:
                 heat = tiles.heatmap_blend(small, proba.proba.to(dev)[..., by_label[lb].id], by_label[lb].color, alpha)
                 Image.fromarray(heat.cpu().numpy()).save(out_dir / f"{stem}_heat_{lb}.jpg", quality=95)
+        if truth is not None:
+            truth_rgb = tiles.colorize_map(truth.to(dev, torch.int64).contiguous(), lut)
+            Image.fromarray(truth_rgb.cpu().numpy()).save(out_dir / f"{stem}_truth.jpg", quality=95)
+        if outcome is not None:
+            two = torch.tensor([ERROR_COLORS["correct"], ERROR_COLORS["wrong"]], dtype=torch.uint8)
+            errors = tiles.overlay_blend(small, tiles.colorize_map(outcome.to(dev, torch.int64).contiguous(), two), alpha)
+            Image.fromarray(errors.cpu().numpy()).save(out_dir / f"{stem}_errors.jpg", quality=95)
     return mask_np, img_np, ov_np
 
 
@@ -553,6 +567,30 @@ KNOWN_COLORS = {   # predict_full_patched.py:139-148
     "MM": (255, 0, 0),       # red
     "TUM": (33, 67, 156),    # blue
 }
+
+
+ERROR_COLORS = {"correct": (0, 255, 0), "wrong": (255, 0, 0)}   # the 2-row LUT of the outcome map (0, 1)
+
+
+def _anno_from_args(ap, args):
+    """The records of --anno (None without it); a missing file, an annotation without a region of a known class and
+    --score_json without --anno are argparse errors."""
+    import json
+
+    if args.score_json and not args.anno:
+        ap.error("--score_json needs --anno")
+    if not args.anno:
+        return None
+    if not Path(args.anno).is_file():
+        ap.error(f"--anno {args.anno}: no such file")
+    try:
+        records = json.loads(Path(args.anno).read_text())
+        known = [a for a in records if a["class"] in KNOWN_COLORS]
+    except (ValueError, TypeError, KeyError) as e:
+        ap.error(f"--anno {args.anno}: not a JSON list of {{class, vertices}} records ({e!r})")
+    if not known:
+        ap.error(f"--anno {args.anno}: none of its {len(records)} regions belongs to a known class ({', '.join(KNOWN_COLORS)})")
+    return records
 
 
 def _tissue_from_args(ap, args) -> TissueFilter | None:
@@ -622,6 +660,8 @@ def main(argv=None, model=None):
     `--proba` also computes the per-cell mean softmax probabilities (DESIGN.md section 4.8) and writes the confidence JPEG;
     `--heat LABEL ...` adds one heat map per class label; `--save_proba PATH` writes the probabilities as float16 PATH(.npy) and
     the hit counts as PATH_count.npy (rank 0).  The returned class map stays the argmax of the logit sums.
+    `--anno PATH` scores the class map against the slide's polygon annotation (rank 0): prints the table
+    and writes `{stem}_truth.jpg` and `{stem}_errors.jpg`; `--score_json PATH` writes the figures and the annotation's counts.
     `model`: an injected module (tests)."""
     import argparse
 
@@ -656,8 +696,12 @@ def main(argv=None, model=None):
                     help=f"with --proba: one {{stem}}_heat_LABEL.jpg per class label ({', '.join(KNOWN_COLORS)})")
     ap.add_argument("--save_proba", default=None, metavar="PATH",
                     help="with --proba: probabilities as float16 PATH(.npy), hit counts as PATH_count.npy (rank 0)")
+    ap.add_argument("--anno", default=None, metavar="PATH",
+                    help="the slide's annotation JSON: score the class map against it; writes {stem}_truth.jpg, {stem}_errors.jpg")
+    ap.add_argument("--score_json", default=None, metavar="PATH", help="with --anno: the score and the annotation's counts as JSON")
     args = ap.parse_args(argv)
     tissue = _tissue_from_args(ap, args)
+    anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
 
     rank, world, _dev_index, owned = init_from_env()   # binds the rank's GPU before any other GPU call
@@ -713,10 +757,19 @@ def main(argv=None, model=None):
                 pred, proba = pred
             if tissue is not None and rank == 0:
                 print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
+        truth = outcome = None
+        if rank == 0 and anno_records is not None:   # the map is whole on rank 0
+            score, truth, outcome, anno_info = score_prediction(pred, anno_records, anno_dsc, args.layer, smp.h, smp.w,
+                                                                args.downscale_vis, return_maps=True, device=device)
+            print(score, flush=True)
+            print(f"annotation: {anno_info['n_rings']} rings of {anno_info['n_regions']} regions, "
+                  f"{anno_info['skipped_class']} of unknown class, {anno_info['failed']} failed to parse", flush=True)
+            if args.score_json:
+                save_score(args.score_json, score, anno_info)
         if rank == 0 and not args.no_visualizations:
             src = img if isinstance(img, torch.Tensor) or not smp.resident else smp.data_device
             perform_and_save_visualizations(src, anno_dsc, pred, out_dir=Path(args.out_dir), stem=stem, device=device,
-                                            proba=proba, heat_classes=args.heat)
+                                            proba=proba, heat_classes=args.heat, truth=truth, outcome=outcome)
         if rank == 0 and args.save_proba:
             save_proba(args.save_proba, proba)
         if world > 1:

@@ -165,6 +165,26 @@ int dh_finish_mean(const float* sum_dev, const int32_t* count_dev, int64_t n_cel
 int dh_heatmap_blend(const uint8_t* img_dev, const float* field_dev, int64_t field_stride, int64_t n_cells,
                      const uint8_t* color_host, double alpha, uint8_t* out_dev, void* stream);
 
+/* ---- scoring a class map against a polygon annotation (no counterpart in the reference) --------
+ * dh_rasterize_regions: labels_dev int32[dh][dw] from n_rings polygon rings.  xy_host float64[n_vertices][2] (x, y) in layer
+ *   coordinates; ring r owns the vertices ring_start_host[r] .. ring_start_host[r + 1] (int64[n_rings + 1], first entry 0; the
+ *   closing edge last -> first is implied) and has class ring_class_host[r] in [0, n_cls), n_cls <= 64.  Cell (cy, cx) is its
+ *   centre p = ((cx + 0.5) * d, (cy + 0.5) * d).  p is inside a ring when an odd number of its edges a -> b have
+ *   (a.y > p.y) != (b.y > p.y) and p.x < a.x + (p.y - a.y) * (b.x - a.x) / (b.y - a.y), evaluated in float64 in that order,
+ *   one rounding per operation.  A cell inside rings of exactly one class gets that class id; of none, or of several
+ *   different classes, -1.  n_rings = 0 gives all -1.  A ring with fewer than 3 vertices, a class id outside [0, n_cls), a
+ *   coordinate that is not finite (or beyond 1e15), n_cls > 64 and non-positive dh / dw / d are refused before any GPU call.
+ *   The ring data and the per-bin ring lists stay on the device for the next call with the same arguments.
+ * dh_confusion_matrix: counts_host int64[n_cls][n_cls + 1], HOST memory: counts[t][p] = cells with truth t and prediction p;
+ *   the last column counts cells with truth t and prediction -1 (no prediction).  Cells with truth -1 are not counted.
+ *   pred_dev int64[n_cells], truth_dev int32[n_cells]; outcome_dev int64[n_cells] or NULL: -1 where truth is -1, 0 where
+ *   the prediction equals the truth, 1 elsewhere.  The entry waits for the stream: a prediction outside [-1, n_cls)
+ *   anywhere in pred_dev makes it return DH_EINVAL (counts_host is then all zero). */
+int dh_rasterize_regions(const double* xy_host, const int64_t* ring_start_host, const int32_t* ring_class_host, int64_t n_rings,
+                         int32_t n_cls, int64_t dh, int64_t dw, int32_t d, int32_t* labels_dev, void* stream);
+int dh_confusion_matrix(const int64_t* pred_dev, const int32_t* truth_dev, int64_t n_cells, int32_t n_cls, int64_t* counts_host,
+                        int64_t* outcome_dev, void* stream);
+
 /* ---- a6: ResNet-18 patch classifier forward ---------------------------------
  * Replaces `model(features)` for the network built by get_model
  * (models/patch_cls_simple/model.py:5-11: torchvision resnet18 + fc[n_cls,512])
