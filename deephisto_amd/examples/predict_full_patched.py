@@ -13,6 +13,8 @@ the per-cell mean softmax probabilities, hit counts, their class map and confide
 DESIGN.md section 4.8); `ImagePredictorPatched.process_proba()` is the same for the callback route.
 `score_prediction(pred, anno, ...)` (deephisto_amd.scoring) scores any of these maps against the
 slide's polygon annotation; the CLI does so with `--anno PATH [--score_json PATH]`.
+`extract_regions(pred, ...)` (deephisto_amd.regions) lists a map's connected regions, removes the small
+ones and traces them into polygons; the CLI does so with `--regions_json`, `--min_region [--clean_rounds]`, `--export_anno`.
 """
 from __future__ import annotations
 
@@ -31,6 +33,8 @@ from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..psimage_compat import Patch, open_slide
+from ..regions import (SlideRegions, clean_map, export_annotation, extract_regions, label_components,  # noqa: F401  (exported here)
+                       region_table, save_regions, trace_polygons)
 from ..scoring import SlideScore, confusion, rasterize_annotation, save_score, score_prediction  # noqa: F401  (exported here)
 from ..tissue import TissueFilter, fill_uncovered, score_tiles
 
@@ -631,6 +635,16 @@ def _proba_from_args(ap, args) -> None:
             ap.error(f"--heat labels must be out of {', '.join(KNOWN_COLORS)}, not {lb!r}")
 
 
+def _regions_from_args(ap, args) -> None:
+    """Checks the region flags; a bad combination is an argparse error."""
+    if args.clean_rounds is not None and args.min_region is None:
+        ap.error("--clean_rounds needs --min_region")
+    if args.min_region is not None and args.min_region < 1:
+        ap.error(f"--min_region must be >= 1, not {args.min_region}")
+    if args.clean_rounds is not None and args.clean_rounds < 1:
+        ap.error(f"--clean_rounds must be >= 1, not {args.clean_rounds}")
+
+
 def save_proba(path, proba) -> tuple[Path, Path]:
     """Writes `proba.proba` as float16 to `path` (.npy) and `proba.count` to the same name with `_count` before the suffix."""
     path = Path(path)
@@ -662,6 +676,11 @@ def main(argv=None, model=None):
     the hit counts as PATH_count.npy (rank 0).  The returned class map stays the argmax of the logit sums.
     `--anno PATH` scores the class map against the slide's polygon annotation (rank 0): prints the table
     and writes `{stem}_truth.jpg` and `{stem}_errors.jpg`; `--score_json PATH` writes the figures and the annotation's counts.
+    `--regions_json PATH` writes the table of the map's connected regions (rank 0); `--min_region CELLS
+    [--clean_rounds R]` first gives regions below CELLS cells the class of their large neighbours and writes
+    `{stem}_clean_mask.jpg` and `{stem}_clean_overlay.jpg`; `--export_anno PATH` writes the regions as polygons in the
+    annotation's JSON format.  The returned map and the three standard JPEGs are those of a run without these flags, and
+    `--anno` keeps scoring the uncleaned map (the cleaned one gets a second score).
     `model`: an injected module (tests)."""
     import argparse
 
@@ -699,7 +718,13 @@ def main(argv=None, model=None):
     ap.add_argument("--anno", default=None, metavar="PATH",
                     help="the slide's annotation JSON: score the class map against it; writes {stem}_truth.jpg, {stem}_errors.jpg")
     ap.add_argument("--score_json", default=None, metavar="PATH", help="with --anno: the score and the annotation's counts as JSON")
+    ap.add_argument("--regions_json", default=None, metavar="PATH", help="the table of the map's connected regions as JSON (rank 0)")
+    ap.add_argument("--min_region", type=int, default=None, metavar="CELLS",
+                    help="regions below CELLS cells take their large neighbours' class; writes {stem}_clean_mask.jpg, {stem}_clean_overlay.jpg")
+    ap.add_argument("--clean_rounds", type=int, default=None, metavar="R", help="with --min_region: cleanup rounds (default 1)")
+    ap.add_argument("--export_anno", default=None, metavar="PATH", help="the regions as polygons in the annotation's JSON format (rank 0)")
     args = ap.parse_args(argv)
+    _regions_from_args(ap, args)
     tissue = _tissue_from_args(ap, args)
     anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
@@ -772,6 +797,28 @@ def main(argv=None, model=None):
                                             proba=proba, heat_classes=args.heat, truth=truth, outcome=outcome)
         if rank == 0 and args.save_proba:
             save_proba(args.save_proba, proba)
+        if rank == 0 and (args.regions_json or args.min_region is not None or args.export_anno):   # the map is whole on rank 0
+            from PIL import Image
+            res = extract_regions(pred, anno_dsc, args.layer, args.downscale_vis, min_cells=args.min_region or 0,
+                                  rounds=args.clean_rounds or 1, polygons=bool(args.export_anno), device=device,
+                                  confidence=proba.confidence if proba is not None else None)
+            print(f"regions: {res.k}" + (f", cleanup below {args.min_region} cells changed {res.n_changed} cells" if args.min_region else "")
+                  + (f", traced in {res.trace_s:.3f} s" if args.export_anno else ""), flush=True)
+            if args.regions_json:
+                save_regions(args.regions_json, res.regions, anno_dsc, args.downscale_vis, args.layer,
+                             dict(min_region=args.min_region, clean_rounds=args.clean_rounds, n_changed=res.n_changed))
+            if args.export_anno:
+                export_annotation(args.export_anno, res.regions, res.polygons, anno_dsc)
+            if args.min_region is not None and anno_records is not None:
+                print("cleaned map:", flush=True)
+                print(score_prediction(res.class_map, anno_records, anno_dsc, args.layer, smp.h, smp.w, args.downscale_vis,
+                                       device=device), flush=True)
+            if args.min_region is not None and not args.no_visualizations:
+                src_img = img if isinstance(img, torch.Tensor) or not smp.resident else smp.data_device
+                mask, _, overlay = perform_and_save_visualizations(src_img, anno_dsc, res.class_map, stem=stem, save=False, device=device)
+                Path(args.out_dir).mkdir(exist_ok=True, parents=True)
+                Image.fromarray(mask).save(Path(args.out_dir) / f"{stem}_clean_mask.jpg", quality=95)
+                Image.fromarray(overlay).save(Path(args.out_dir) / f"{stem}_clean_overlay.jpg", quality=95)
         if world > 1:
             dist.barrier()
         ok = True

@@ -185,6 +185,34 @@ int dh_rasterize_regions(const double* xy_host, const int64_t* ring_start_host, 
 int dh_confusion_matrix(const int64_t* pred_dev, const int32_t* truth_dev, int64_t n_cells, int32_t n_cls, int64_t* counts_host,
                         int64_t* outcome_dev, void* stream);
 
+/* ---- regions of a class map: connected components, table, cleanup (no counterpart in the reference) --
+ * dh_label_components: labels_dev int32[dh][dw] from map_dev int64[dh][dw] with values in [-1, n_cls), n_cls <= 64, fewer than
+ *   2^31 - 2048 cells.  Two cells belong to one component when they have the same class >= 0 and a path of 4-neighbours of that
+ *   class joins them.  labels is 0 where the class is -1, else the component's id in 1..K, ids ascending with the component's
+ *   smallest linear cell index cy * dw + cx: the numbering is unique.  work_dev: int32[dh_label_work_size(dh * dw)], scratch.
+ *   *n_components_host = K.  The entry waits for the stream; a class outside [-1, n_cls) anywhere in map_dev makes it return
+ *   DH_EINVAL (labels_dev is then undefined).
+ * dh_label_work_size: the number of int32 elements of work_dev for a canvas of n_cells cells.
+ * dh_region_stats: table_dev int64[n_components][10], one row per id (row id - 1), all integers, so exact whatever the order:
+ *   0 class, 1 area in cells, 2..5 bounding box y0, x0, y1, x1 in cells (half-open), 6 sum of cy, 7 sum of cx, 8 the smallest
+ *   linear cell index, 9 conf_q = the sum over the cells, modulo 2^64, of rint(float64(confidence) * 2^32) (round half to
+ *   even); 0 when confidence_dev (float32[dh][dw]) is NULL.  labels_dev and n_components as dh_label_components gave them for
+ *   map_dev.  Asynchronous on the stream.
+ * dh_clean_small_regions: one cleanup round.  A component is small when its area < min_cells (>= 1).  Every pair (cell of a
+ *   small component s, 4-neighbour cell in a component that is not small) casts one vote for the neighbour's class; s takes
+ *   the class with the most votes, the lowest class id on a tie, and stays as it is without a vote.  All small components are
+ *   decided from the one labelling, then out_map_dev int64[dh][dw] (not map_dev) = the map with them rewritten; cells of
+ *   class -1 neither vote nor change.  votes_dev: int32[n_components][n_cls], scratch.  *n_changed_host = cells whose class
+ *   changed; the entry waits for the stream. */
+int dh_label_components(const int64_t* map_dev, int64_t dh, int64_t dw, int32_t n_cls, int32_t* labels_dev, int32_t* work_dev,
+                        int64_t* n_components_host, void* stream);
+int64_t dh_label_work_size(int64_t n_cells);
+int dh_region_stats(const int64_t* map_dev, const int32_t* labels_dev, const float* confidence_dev, int64_t dh, int64_t dw,
+                    int64_t n_components, int64_t* table_dev, void* stream);
+int dh_clean_small_regions(const int64_t* map_dev, const int32_t* labels_dev, const int64_t* table_dev, int64_t n_components,
+                           int64_t dh, int64_t dw, int32_t n_cls, int64_t min_cells, int32_t* votes_dev, int64_t* out_map_dev,
+                           int64_t* n_changed_host, void* stream);
+
 /* ---- a6: ResNet-18 patch classifier forward ---------------------------------
  * Replaces `model(features)` for the network built by get_model
  * (models/patch_cls_simple/model.py:5-11: torchvision resnet18 + fc[n_cls,512])
