@@ -7,11 +7,13 @@ cd $GRAFT_REPO_ROOT
 A=$1; shift
 O=gpurun_out/abl_train_$A.txt; : > $O
 cp deephisto_amd/libdeephisto_hip.so /tmp/dh_keep.so
+restore() { cp /tmp/dh_keep.so deephisto_amd/libdeephisto_hip.so; }
+trap restore EXIT   # the shipped library comes back however the script ends
 echo "== base" >> $O; python3 tools/train_time.py $A --steps 40 2>/dev/null >> $O
 for v in "$@"; do
   cp deephisto_amd/libdeephisto_hip_${PFX:-abl}$v.so deephisto_amd/libdeephisto_hip.so
   echo "== -DDH_T2_ABL=$v" >> $O; python3 tools/train_time.py $A --steps 40 2>/dev/null >> $O
 done
-cp /tmp/dh_keep.so deephisto_amd/libdeephisto_hip.so
+restore
 echo "== base" >> $O; python3 tools/train_time.py $A --steps 40 2>/dev/null >> $O
 cat $O

@@ -17,37 +17,15 @@ predict_full_patched (bf16 ResNet-18, 224 / 112, synthetic slide) with and witho
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
-import sys
 import time
-from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
 
 D, N_CLS = 16, 5
 BYTES_PER_CELL = {"parent": 68, "fused": 60, "unfused": 104}
 
 
-def median_ms(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return statistics.median(times), min(times)
-
-
 def main():
     import torch
+    from _timing import Rows, median_ms, whole_slide_case
 
     from deephisto_amd import tiles
 
@@ -60,12 +38,8 @@ def main():
     if args.reps < 20:
         ap.error("--reps must be at least 20")
     dev = torch.device("cuda:0")
-    side, rows = args.side, []
+    side, rows = args.side, Rows()
     cells = (side // D) ** 2
-
-    def emit(**kw):
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
 
     for P, S in ((256, 256), (224, 112)):
         o, n_unique = tiles.tile_grid(side, side, P, S, 64)
@@ -79,29 +53,23 @@ def main():
         a, b = ways["fused"](), ways["unfused"]()
         assert torch.equal(a.proba, b.proba) and torch.equal(a.class_map, b.class_map) and torch.equal(a.count, b.count)
         for k, (med, best) in ms.items():
-            emit(way=k, side=side, patch=P, stride=S, downscale=D, rows=len(o), unique_rows=n_unique, cells=cells, reps=args.reps,
-                 median_ms=round(med, 4), min_ms=round(best, 4), ratio_to_parent=round(med / ms["parent"][0], 3),
-                 bytes_per_cell=BYTES_PER_CELL[k], gb_per_s=round(BYTES_PER_CELL[k] * cells / (med / 1e3) / 1e9, 1))
+            rows.emit(way=k, side=side, patch=P, stride=S, downscale=D, rows=len(o), unique_rows=n_unique, cells=cells, reps=args.reps,
+                      median_ms=round(med, 4), min_ms=round(best, 4), ratio_to_parent=round(med / ms["parent"][0], 3),
+                      bytes_per_cell=BYTES_PER_CELL[k], gb_per_s=round(BYTES_PER_CELL[k] * cells / (med / 1e3) / 1e9, 1))
         del logits
     if args.whole:
         from deephisto_amd.examples.predict_full_patched import predict_full_patched
-        from deephisto_amd.models.patch_cls_simple.model import get_model
-        from deephisto_amd.patch_samplers.full_samplers import FullImageDenseSampler
-        slide = tiles.synth_slide(side, side, 0, dev)
-        smp = FullImageDenseSampler(slide, layer=1, patch_size=224, batch_size=64, stride=112, device=dev)
-        torch.manual_seed(0)
-        model = get_model(5, "bf16").to(dev).eval()
+        _slide, smp, model = whole_slide_case(dev, side)
         wall = {}
         for flag in (False, True, False, True):   # alternated; the first pair is the warm-up
             t0 = time.perf_counter()
             predict_full_patched(smp, model, 5, downscale=D, return_proba=flag)
             torch.cuda.synchronize()
             wall[flag] = time.perf_counter() - t0
-        emit(step="predict_full_patched wall", arch="resnet18", dtype="bf16", side=side, patch=224, stride=112,
-             without_proba_s=round(wall[False], 4), with_proba_s=round(wall[True], 4),
-             difference_ms=round((wall[True] - wall[False]) * 1e3, 2))
-    if args.out:
-        Path(args.out).write_text("".join(json.dumps(r) + "\n" for r in rows))
+        rows.emit(step="predict_full_patched wall", arch="resnet18", dtype="bf16", side=side, patch=224, stride=112,
+                  without_proba_s=round(wall[False], 4), with_proba_s=round(wall[True], 4),
+                  difference_ms=round((wall[True] - wall[False]) * 1e3, 2))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":

@@ -12,13 +12,7 @@ the fc, counted from the topology).  One JSON line per measurement.
 from __future__ import annotations
 
 import argparse
-import json
-import sys
 import time
-from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
 
 PEAK_BF16 = 2.5e15
 
@@ -42,10 +36,9 @@ def resnet50_macs(P: int, n_cls: int = 5) -> int:
 def main():
     import numpy as np
     import torch
+    from _timing import Rows, best_of, whole_slide_case
 
-    from deephisto_amd import tiles
     from deephisto_amd.examples.predict_full_patched import ImagePredictorPatched, batch_predictor, predict_full_patched
-    from deephisto_amd.models.patch_cls_simple.model import get_model
     from deephisto_amd.patch_samplers.full_samplers import FullImageDenseSampler
 
     ap = argparse.ArgumentParser()
@@ -56,32 +49,18 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    torch.manual_seed(0)
-    model = get_model(5, arch="resnet50").to(dev).eval()
-    slide = tiles.synth_slide(args.side, args.side, 0, dev)
+    slide, _smp, model = whole_slide_case(dev, args.side, arch="resnet50")
     torch.cuda.synchronize()
-    rows = []
-
-    def emit(**kw):
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
+    rows = Rows()
 
     for P, S in ((224, 112), (256, 256)):
         smp = FullImageDenseSampler(slide, layer=1, patch_size=P, batch_size=64, stride=S, device=dev)
-        predict_full_patched(smp, model, 5, downscale=16)   # warm-up: handles, workspaces, kernels
-        torch.cuda.synchronize()
-        best = None
-        for _ in range(args.reps):
-            t0 = time.perf_counter()
-            predict_full_patched(smp, model, 5, downscale=16)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            best = dt if best is None else min(best, dt)
+        best = best_of(lambda: predict_full_patched(smp, model, 5, downscale=16), args.reps)   # warm-up: handles, workspaces, kernels
         n = len(smp.origins)
         pps = n / best
-        emit(route="predict_full_patched", arch="resnet50", side=args.side, patch=P, stride=S, tiles=n, seconds=round(best, 4),
-             patches_per_s=round(pps, 1), gflop_per_tile=round(2 * resnet50_macs(P) / 1e9, 3),
-             fraction_of_bf16_peak=round(pps * 2 * resnet50_macs(P) / PEAK_BF16, 4))
+        rows.emit(route="predict_full_patched", arch="resnet50", side=args.side, patch=P, stride=S, tiles=n, seconds=round(best, 4),
+                  patches_per_s=round(pps, 1), gflop_per_tile=round(2 * resnet50_macs(P) / 1e9, 3),
+                  fraction_of_bf16_peak=round(pps * 2 * resnet50_macs(P) / PEAK_BF16, 4))
     if not args.skip_callback:
         P, S, s = 224, 112, args.cb_side
         sub = slide[:s, :s].contiguous()
@@ -98,13 +77,12 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         n = len(smp.origins)
-        emit(route="ImagePredictorPatched+batch_predictor (training-engine eval)", arch="resnet50", side=s, patch=P, stride=S, tiles=n,
-             seconds=round(dt, 4), patches_per_s=round(n / dt, 1), fraction_of_bf16_peak=round(n / dt * 2 * resnet50_macs(P) / PEAK_BF16, 4))
+        rows.emit(route="ImagePredictorPatched+batch_predictor (training-engine eval)", arch="resnet50", side=s, patch=P, stride=S, tiles=n,
+                  seconds=round(dt, 4), patches_per_s=round(n / dt, 1), fraction_of_bf16_peak=round(n / dt * 2 * resnet50_macs(P) / PEAK_BF16, 4))
         smp2 = FullImageDenseSampler(sub, layer=1, patch_size=P, batch_size=64, stride=S, device=dev)
         fast = predict_full_patched(smp2, model, 5, downscale=16).cpu().numpy()
-        emit(route="agreement on the slice", class_map_agreement=float((fast == np.asarray(pred)).mean()))
-    if args.out:
-        Path(args.out).write_text("".join(json.dumps(r) + "\n" for r in rows))
+        rows.emit(route="agreement on the slice", class_map_agreement=float((fast == np.asarray(pred)).mean()))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":

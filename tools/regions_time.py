@@ -20,38 +20,17 @@ The device results are compared with the restatement's before anything is timed.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 import time
-from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
-sys.path.insert(0, str(REPO / "tests"))
 
 D, N_CLS, SIDE = 16, 5, 50000
-
-
-def median_ms(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return statistics.median(times), min(times)
 
 
 def main():
     import numpy as np
     import torch
+    from _timing import REPO, Rows, median_ms, whole_slide_case
+    sys.path.insert(0, str(REPO / "tests"))
     from test_regions_host import canvas, clean_round_np, label_np, table_np
 
     from deephisto_amd import regions, tiles
@@ -64,21 +43,12 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     dh = SIDE // D
-    rows = []
-
-    def emit(**kw):
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
+    rows = Rows()
 
     maps, predict_s = {}, None
     if not args.no_whole:
         from deephisto_amd.examples.predict_full_patched import predict_full_patched
-        from deephisto_amd.models.patch_cls_simple.model import get_model
-        from deephisto_amd.patch_samplers.full_samplers import FullImageDenseSampler
-        slide = tiles.synth_slide(SIDE, SIDE, 0, dev)
-        smp = FullImageDenseSampler(slide, layer=1, patch_size=224, batch_size=64, stride=112, device=dev)
-        torch.manual_seed(0)
-        model = get_model(5, "bf16").to(dev).eval()
+        slide, smp, model = whole_slide_case(dev, SIDE)
         for _ in range(3):   # the first round is the warm-up
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -90,8 +60,8 @@ def main():
             torch.cuda.synchronize()
             predict_s = time.perf_counter() - t0
         maps["prediction"] = (cmap, proba.confidence)
-        emit(step="predict_full_patched wall", arch="resnet18", dtype="bf16", side=SIDE, patch=224, stride=112,
-             predict_s=round(predict_s, 4), with_proba_s=round(with_proba_s, 4))
+        rows.emit(step="predict_full_patched wall", arch="resnet18", dtype="bf16", side=SIDE, patch=224, stride=112,
+                  predict_s=round(predict_s, 4), with_proba_s=round(with_proba_s, 4))
         del slide, smp, model, proba
     m14, _ = canvas("patch14", (dh, dh))
     conf14 = torch.rand((dh, dh), generator=torch.Generator(device="cpu").manual_seed(5)).to(dev)
@@ -100,7 +70,7 @@ def main():
     o, _ = tiles.tile_grid(SIDE, SIDE, 256, 256, 64)
     logits = torch.randn((len(o), N_CLS), generator=torch.Generator(device=dev).manual_seed(256), device=dev) * 3
     acc_ms = median_ms(lambda: tiles.accumulate_logits(logits, o, 256, D, SIDE, SIDE), args.reps)
-    emit(way="accumulate", cells=dh * dh, reps=args.reps, median_ms=round(acc_ms[0], 4), min_ms=round(acc_ms[1], 4))
+    rows.emit(way="accumulate", cells=dh * dh, reps=args.reps, median_ms=round(acc_ms[0], 4), min_ms=round(acc_ms[1], 4))
 
     for name, (pred, conf) in maps.items():
         m = pred.cpu().numpy()
@@ -147,21 +117,20 @@ def main():
             extra = {}
             if w == "budget" and predict_s:
                 extra = dict(share_of_predict=round(med / 1e3 / predict_s, 5), limit=0.03, within=bool(med / 1e3 / predict_s < 0.03))
-            emit(way=w, **common, reps=args.reps, median_ms=round(med, 4), min_ms=round(best, 4),
-                 ratio_to_accumulate=round(med / acc_ms[0], 2), **extra)
-        emit(way="numpy", **common, label_wall_s=round(np_label, 3), table_wall_s=round(np_table, 3), clean_round_wall_s=round(np_clean, 3),
-             scipy_label_per_class_wall_s=None if scipy_s is None else round(scipy_s, 3))
+            rows.emit(way=w, **common, reps=args.reps, median_ms=round(med, 4), min_ms=round(best, 4),
+                      ratio_to_accumulate=round(med / acc_ms[0], 2), **extra)
+        rows.emit(way="numpy", **common, label_wall_s=round(np_label, 3), table_wall_s=round(np_table, 3), clean_round_wall_s=round(np_clean, 3),
+                  scipy_label_per_class_wall_s=None if scipy_s is None else round(scipy_s, 3))
         if k_c > 300000:   # a speckled map: the per-ring Python loop takes minutes; not a case a user traces
-            emit(way="trace", **common, wall_s=None, note="not measured: more than 300 000 regions")
+            rows.emit(way="trace", **common, wall_s=None, note="not measured: more than 300 000 regions")
             continue
         host = labels_c.cpu().numpy()
         t0 = time.perf_counter()
         polys = regions.trace_polygons(host, range(1, k_c + 1), D, 1)
         trace_s = time.perf_counter() - t0
-        emit(way="trace", **common, wall_s=round(trace_s, 3), rings=sum(1 + len(h) for _, h in polys.values()),
-             vertices=int(sum(len(o_) + sum(len(x) for x in h) for o_, h in polys.values())))
-    if args.out:
-        Path(args.out).write_text("".join(json.dumps(r) + "\n" for r in rows))
+        rows.emit(way="trace", **common, wall_s=round(trace_s, 3), rings=sum(1 + len(h) for _, h in polys.values()),
+                  vertices=int(sum(len(o_) + sum(len(x) for x in h) for o_, h in polys.values())))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":

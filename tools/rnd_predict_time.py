@@ -11,18 +11,13 @@ time), and the NumPy index logic's cost per batch over its first 5 batches.  One
 from __future__ import annotations
 
 import argparse
-import json
-import sys
 import time
-from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
 
 
 def main():
     import numpy as np
     import torch
+    from _timing import Rows
 
     from deephisto_amd import tiles
     from deephisto_amd.examples.predict_full_patched import predict_random_patched
@@ -40,12 +35,7 @@ def main():
     side, P, B, dl, d = args.side, args.patch, args.batch, 2, 16
     slide = tiles.synth_slide(side, side, 0, dev)
     torch.cuda.synchronize()
-    rows = []
-
-    def emit(**kw):
-        kw = {"side": side, "patch": P, "batch": B, "dense_level": dl, "speedup": d, **kw}
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
+    rows = Rows(side=side, patch=P, batch=B, dense_level=dl, speedup=d)
 
     def mk(logic):
         return FullImageRndSampler(slide, layer=1, patch_size=P, batch_size=B, dense_level=dl, speedup=d, index_logic=logic)
@@ -75,9 +65,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gpu_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    emit(what="sampler_only", batches=n, tiles=n * B, filled=smp._filled_ratio[-1], seconds=round(dt, 3),
-         patches_per_s=round(n * B / dt), host_ms_per_batch=round(1e3 * host_plan / n, 4),
-         gpu_ms_per_batch_span=round(gpu_ms, 4), stats=repr(smp.planner.stats))
+    rows.emit(what="sampler_only", batches=n, tiles=n * B, filled=smp._filled_ratio[-1], seconds=round(dt, 3),
+              patches_per_s=round(n * B / dt), host_ms_per_batch=round(1e3 * host_plan / n, 4),
+              gpu_ms_per_batch_span=round(gpu_ms, 4), stats=repr(smp.planner.stats))
     n_batches = n
 
     # end to end
@@ -93,8 +83,8 @@ def main():
         predict_random_patched(mk("device"), model, 5, d, timing=timing)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        emit(what=f"predict_random_patched_{dtype}", batches=timing["n_batches"], tiles=timing["n_tiles"], seconds=round(dt, 3),
-             patches_per_s=round(timing["n_tiles"] / dt), host_loop_s=round(timing["host_s"], 3))
+        rows.emit(what=f"predict_random_patched_{dtype}", batches=timing["n_batches"], tiles=timing["n_tiles"], seconds=round(dt, 3),
+                  patches_per_s=round(timing["n_tiles"] / dt), host_loop_s=round(timing["host_s"], 3))
         assert timing["n_batches"] == n_batches
         del model
         torch.cuda.empty_cache()
@@ -108,11 +98,9 @@ def main():
         t0 = time.perf_counter()
         next(it)
         t.append(time.perf_counter() - t0)
-    emit(what="numpy_index_logic_first5", ms_per_batch=[round(1e3 * x, 1) for x in t],
-         patches_per_s=round(5 * B / sum(t), 1))
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text("\n".join(json.dumps(r) for r in rows) + "\n")
+    rows.emit(what="numpy_index_logic_first5", ms_per_batch=[round(1e3 * x, 1) for x in t],
+              patches_per_s=round(5 * B / sum(t), 1))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":

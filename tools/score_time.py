@@ -17,39 +17,18 @@ predict_full_patched (bf16 ResNet-18, 224 / 112, synthetic slide) and of score_p
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
 import sys
 import time
-from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
-sys.path.insert(0, str(REPO / "tests"))
 
 D, N_CLS = 16, 5
 LABELS = ["AT", "BG", "LP", "MM", "TUM"]
 
 
-def median_ms(fn, reps):
-    import torch
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return statistics.median(times), min(times)
-
-
 def main():
     import numpy as np
     import torch
+    from _timing import REPO, Rows, median_ms, whole_slide_case
+    sys.path.insert(0, str(REPO / "tests"))
     from test_score_host import confusion_np, rasterize_np
 
     from deephisto_amd import scoring, tiles
@@ -66,13 +45,9 @@ def main():
     if args.reps < 20:
         ap.error("--reps must be at least 20")
     dev = torch.device("cuda:0")
-    side, rows = args.side, []
+    side, rows = args.side, Rows()
     dh = side // D
     cells = dh * dh
-
-    def emit(**kw):
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
 
     dsc = AnnoDescription.with_known_colors({lb: (0, 0, 0) for lb in LABELS})
     records = scoring.synthetic_annotation(side, side, args.rings, args.vertices, LABELS, seed=11)
@@ -113,20 +88,15 @@ def main():
     }
     ms = {k: median_ms(fn, args.reps) for k, fn in ways.items()}
     for k, (med, best) in ms.items():
-        emit(way=k, **common, reps=args.reps, median_ms=round(med, 4), min_ms=round(best, 4),
-             ratio_to_accumulate=round(med / ms["accumulate"][0], 3))
-    emit(way="rasterize_cold", **common, wall_ms=round(cold * 1e3, 2))
-    emit(way="numpy", **common, rasterize_wall_s=round(np_raster, 3), confusion_wall_s=round(np_conf, 3),
-         labelled_fraction=round(float((truth_np >= 0).mean()), 4))
+        rows.emit(way=k, **common, reps=args.reps, median_ms=round(med, 4), min_ms=round(best, 4),
+                  ratio_to_accumulate=round(med / ms["accumulate"][0], 3))
+    rows.emit(way="rasterize_cold", **common, wall_ms=round(cold * 1e3, 2))
+    rows.emit(way="numpy", **common, rasterize_wall_s=round(np_raster, 3), confusion_wall_s=round(np_conf, 3),
+              labelled_fraction=round(float((truth_np >= 0).mean()), 4))
     if args.whole:
         from deephisto_amd.examples.predict_full_patched import predict_full_patched
-        from deephisto_amd.models.patch_cls_simple.model import get_model
-        from deephisto_amd.patch_samplers.full_samplers import FullImageDenseSampler
         del logits
-        slide = tiles.synth_slide(side, side, 0, dev)
-        smp = FullImageDenseSampler(slide, layer=1, patch_size=224, batch_size=64, stride=112, device=dev)
-        torch.manual_seed(0)
-        model = get_model(5, "bf16").to(dev).eval()
+        _slide, smp, model = whole_slide_case(dev, side)
         wall = {}
         for k in range(3):   # the first round is the warm-up
             torch.cuda.synchronize()
@@ -140,12 +110,11 @@ def main():
         t0 = time.perf_counter()
         scoring.annotation_rings(records, dsc, 1, side, side)
         parse_s = time.perf_counter() - t0
-        emit(step="predict_full_patched + score_prediction wall", arch="resnet18", dtype="bf16", side=side, patch=224, stride=112,
-             predict_s=round(wall["predict_s"], 4), score_s=round(wall["score_s"], 4), of_which_parsing_s=round(parse_s, 4),
-             device_part_ms=round(ms["rasterize"][0] + ms["confusion"][0], 4),
-             device_part_of_predict=round((ms["rasterize"][0] + ms["confusion"][0]) / 1e3 / wall["predict_s"], 5))
-    if args.out:
-        Path(args.out).write_text("".join(json.dumps(r) + "\n" for r in rows))
+        rows.emit(step="predict_full_patched + score_prediction wall", arch="resnet18", dtype="bf16", side=side, patch=224, stride=112,
+                  predict_s=round(wall["predict_s"], 4), score_s=round(wall["score_s"], 4), of_which_parsing_s=round(parse_s, 4),
+                  device_part_ms=round(ms["rasterize"][0] + ms["confusion"][0], 4),
+                  device_part_of_predict=round((ms["rasterize"][0] + ms["confusion"][0]) / 1e3 / wall["predict_s"], 5))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":

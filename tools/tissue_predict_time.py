@@ -19,12 +19,7 @@ from __future__ import annotations
 import argparse
 import csv
 import json
-import sys
-import time
 from pathlib import Path
-
-REPO = Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(REPO))
 
 COPY_RATE = 6.29e12   # bytes/s, the float4 copy rate measured on the MI355X (6.3 TB/s)
 P, S, D = 224, 112, 16
@@ -50,20 +45,6 @@ def painted_slide(side: int, dev):
     return slide
 
 
-def best_of(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    best = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        best = dt if best is None else min(best, dt)
-    return best
-
-
 def score(slide, smp, filt, dev):
     import torch
 
@@ -77,6 +58,7 @@ def score(slide, smp, filt, dev):
 
 def main():
     import torch
+    from _timing import Rows, best_of
 
     from deephisto_amd.examples.predict_full_patched import predict_full_patched
     from deephisto_amd.models.patch_cls_simple.model import get_model
@@ -90,11 +72,7 @@ def main():
     ap.add_argument("--stats", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    rows = []
-
-    def emit(**kw):
-        rows.append(kw)
-        print(json.dumps(kw), flush=True)
+    rows = Rows()
 
     if args.mode == "merge":
         side = args.side
@@ -121,12 +99,10 @@ def main():
                 ms = float(r["AverageNs"]) / 1e6
                 total_ms += ms
                 gbs = need[name] / (ms / 1e3) / 1e9
-                emit(kernel=name, calls=int(r["Calls"]), avg_ms=round(ms, 4), bytes_needed=need[name], gb_per_s=round(gbs, 1),
-                     fraction_of_copy_rate=round(gbs * 1e9 / COPY_RATE, 3))
-        emit(kernel="all scoring passes", avg_ms=round(total_ms, 4))
-        if args.out:
-            with open(args.out, "a") as f:
-                f.write("".join(json.dumps(r) + "\n" for r in rows))
+                rows.emit(kernel=name, calls=int(r["Calls"]), avg_ms=round(ms, 4), bytes_needed=need[name], gb_per_s=round(gbs, 1),
+                          fraction_of_copy_rate=round(gbs * 1e9 / COPY_RATE, 3))
+        rows.emit(kernel="all scoring passes", avg_ms=round(total_ms, 4))
+        rows.write(args.out, "a")
         return
 
     dev = torch.device("cuda:0")
@@ -141,23 +117,22 @@ def main():
     info: dict = {}
     score_s = best_of(lambda: info.update(score(slide, smp, filt, dev)), args.reps)
     kept_frac = info["n_kept"] / info["n_tiles"]
-    emit(step="scoring (histogram, Otsu, counts, compaction, fill; wall)", side=args.side, patch=P, stride=S,
-         n_tiles=info["n_tiles"], n_kept=info["n_kept"], kept_fraction=round(kept_frac, 4), threshold=info["threshold"],
-         min_pixels=info["min_pixels"], seconds=round(score_s, 5))
+    rows.emit(step="scoring (histogram, Otsu, counts, compaction, fill; wall)", side=args.side, patch=P, stride=S,
+              n_tiles=info["n_tiles"], n_kept=info["n_kept"], kept_fraction=round(kept_frac, 4), threshold=info["threshold"],
+              min_pixels=info["min_pixels"], seconds=round(score_s, 5))
     for arch, dtype in (("resnet18", "bf16"), ("resnet50", "bf16")):
         torch.manual_seed(0)
         model = get_model(5, dtype, arch=arch).to(dev).eval()
         full_s = best_of(lambda: predict_full_patched(smp, model, 5, downscale=D), args.reps)
         masked_s = best_of(lambda: predict_full_patched(smp, model, 5, downscale=D, tissue=filt), args.reps)
         bound = kept_frac * full_s + score_s + 0.05 * full_s
-        emit(arch=arch, dtype=dtype, side=args.side, patch=P, stride=S, n_tiles=info["n_tiles"], n_kept=info["n_kept"],
-             kept_fraction=round(kept_frac, 4), unmasked_s=round(full_s, 4), masked_s=round(masked_s, 4),
-             ratio=round(masked_s / full_s, 4), scoring_s=round(score_s, 5),
-             scoring_fraction_of_unmasked=round(score_s / full_s, 4), scoring_within_3pct=score_s <= 0.03 * full_s,
-             masked_bound_s=round(bound, 4), masked_within_bound=masked_s <= bound)
+        rows.emit(arch=arch, dtype=dtype, side=args.side, patch=P, stride=S, n_tiles=info["n_tiles"], n_kept=info["n_kept"],
+                  kept_fraction=round(kept_frac, 4), unmasked_s=round(full_s, 4), masked_s=round(masked_s, 4),
+                  ratio=round(masked_s / full_s, 4), scoring_s=round(score_s, 5),
+                  scoring_fraction_of_unmasked=round(score_s / full_s, 4), scoring_within_3pct=score_s <= 0.03 * full_s,
+                  masked_bound_s=round(bound, 4), masked_within_bound=masked_s <= bound)
         del model
-    if args.out:
-        Path(args.out).write_text("".join(json.dumps(r) + "\n" for r in rows))
+    rows.write(args.out)
 
 
 if __name__ == "__main__":
