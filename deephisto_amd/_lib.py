@@ -116,7 +116,8 @@ DEBUG_SIGNATURES = {
     "dh_debug_upsample2_add_bf16": (C.c_int, [_p, _p] + [_i32] * 6 + [_p]),
     "dh_debug_avgpool_fc_dgrad2": (C.c_int, [_p, _p, _p] + [_i32] * 4 + [_p]),
     "dh_debug_wgrad_bf16": (C.c_int, [_p, _p, _p] + [_i32] * 8 + [_p]),
-    "dh_debug_conv_bn_act": (C.c_int, [_p, _p, _p, _p, _p, _p] + [_i32] * 9 + [_p]),
+    "dh_debug_conv_bf16": (C.c_int, [_p, _p, _p, _p] + [_i32] * 8 + [_p]),
+    "dh_debug_conv_bn_act":(C.c_int, [_p, _p, _p, _p, _p, _p] + [_i32] * 9 + [_p]),
     "dh_debug_stem_out": (C.c_int, [_p, _i64, _i32, _p, _p]),
     "dh_debug_stem_pool_bf16": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p]),
     "dh_debug_wgrad_f32": (C.c_int, [_p, _p, _p] + [_i32] * 8 + [_p]),

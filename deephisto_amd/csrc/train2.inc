@@ -1338,6 +1338,64 @@ extern "C" int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float*
   return dbg_finish(st, "debug avgpool fc");
 }
 
+// One convolution of the bf16 engine on caller data, forward or data gradient, through the step's own launch code: the operands are
+// packed from float32 w[cout][cin][ks][ks] by pack_all_kernel (3x3: fragment order and its flipped / transposed twin; 1x1: W and Wt),
+// then t2_conv_fwd (t2_conv3 / t2_gemm) or t2_conv_dgrad runs on a scratch engine object and picks tile and variant as in a step.
+//   dgrad = 0 : in = x [B][Hi][Wi][cin], out = Z [B][Ho][Wo][cout] (raw, no epilogue); res must be null
+//   dgrad = 1 : in = dZ [B][Ho][Wo][cout], out = dX [B][Hi][Wi][cin] (+ res, the joining gradient, may be null); 1x1 / stride 2 is the
+//               engine's accumulate contract: out starts from res (or zero) and the low-resolution product (bf16 scratch) is added into it
+// Hi x Wi is always the convolution's INPUT size.
+extern "C" int dh_debug_conv_bf16(const uint16_t* in_dev, const float* w_dev, const uint16_t* res_dev, uint16_t* out_dev, int32_t B,
+                                  int32_t Hi, int32_t Wi, int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t dgrad,
+                                  void* stream) {
+  DH_REQUIRE(in_dev && w_dev && out_dev, "debug conv bf16: in, w and out must be given");
+  DH_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "debug conv bf16: B=%d Hi=%d Wi=%d must be positive", B, Hi, Wi);
+  DH_REQUIRE(ks == 1 || ks == 3, "debug conv bf16: ks=%d is not 1 or 3", ks);
+  DH_REQUIRE(stride == 1 || stride == 2, "debug conv bf16: stride=%d is not 1 or 2", stride);
+  DH_REQUIRE(cin > 0 && cin % 64 == 0, "debug conv bf16: cin=%d is not a multiple of 64", cin);
+  DH_REQUIRE(cout > 0 && cout % 64 == 0, "debug conv bf16: cout=%d is not a multiple of 64", cout);
+  DH_REQUIRE(stride == 1 || Hi % 2 == 0, "debug conv bf16: Hi=%d is odd at stride 2 (the engine's maps are even: P %% 32 == 0)", Hi);
+  DH_REQUIRE(stride == 1 || Wi % 2 == 0, "debug conv bf16: Wi=%d is odd at stride 2 (the engine's maps are even: P %% 32 == 0)", Wi);
+  DH_REQUIRE(dgrad == 0 || dgrad == 1, "debug conv bf16: dgrad=%d is not 0 or 1", dgrad);
+  DH_REQUIRE(dgrad == 1 || !res_dev, "debug conv bf16: res belongs to the data gradient (dgrad = 1); the forward conv is raw Z");
+  hipStream_t st = dh::as_stream(stream);
+  DbgScratch sc;
+  dh_train2 t;
+  t.B = B;
+  T2Conv c;
+  c.name = "dbg"; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
+  c.Hi = Hi; c.Wi = Wi; c.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; c.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
+  const int64_t nw = (int64_t)cout * cin * ks * ks, nx = (int64_t)B * Hi * Wi * cin, nz = (int64_t)B * c.Ho * c.Wo * cout;
+  DH_REQUIRE(std::max(nx, nz) * 2 < ((int64_t)1 << 32), "debug conv bf16: B=%d makes a tensor of 4 GiB or more", B);
+  bf16_t *wf, *wd, *scratch = nullptr;
+  PackDesc* dd;
+  int rc;
+  if ((rc = sc.get(&wf, nw)) || (rc = sc.get(&wd, nw)) || (rc = sc.get(&dd, 1)) || (rc = sc.get(&t.ones, 2048)) || (rc = sc.get(&t.zeros, 2048))) return rc;
+  DH_HIP(hipMemsetAsync(t.zeros, 0, 2048 * sizeof(float), st));
+  hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, st, t.ones, (int64_t)2048, 1.0f);
+  const PackDesc hd{w_dev, wf, wd, cout, cin, ks, 0};
+  DH_HIP(hipMemcpyAsync(dd, &hd, sizeof hd, hipMemcpyHostToDevice, st));
+  DH_HIP(hipStreamSynchronize(st));   // `hd` is a stack object
+  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&pack_all_kernel), PACK3_LDS))) return rc;
+  const int tiles = (cout / 64) * (cin / 64);   // workgroups as t2_pack counts them
+  hipLaunchKernelGGL(pack_all_kernel, dim3(ks == 3 ? tiles : std::min(64, tiles)), dim3(256), PACK3_LDS, st, dd, 1, 0);
+  DH_LAUNCH_CHECK();
+  c.wp_f = wf; c.wp_d = wd;
+  if (!dgrad) {
+    c.Z = out_dev;
+    rc = t2_conv_fwd(&t, c, in_dev, st);
+  } else if (ks == 1 && stride == 2) {   // a downsample branch: the step has already written the other branch's gradient into dX
+    if ((rc = sc.get(&scratch, nz / cout * cin))) return rc;
+    if (res_dev) DH_HIP(hipMemcpyAsync(out_dev, res_dev, nx * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
+    else DH_HIP(hipMemsetAsync(out_dev, 0, nx * sizeof(bf16_t), st));
+    rc = t2_conv_dgrad(&t, c, in_dev, nullptr, out_dev, scratch, true, st);
+  } else {
+    rc = t2_conv_dgrad(&t, c, in_dev, res_dev, out_dev, nullptr, false, st);
+  }
+  if (rc) { (void)hipStreamSynchronize(st); return rc; }
+  return dbg_finish(st, "debug conv bf16");
+}
+
 extern "C" int dh_debug_wgrad_bf16(const uint16_t* dz_dev, const uint16_t* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi,
                                    int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t repeat, void* stream) {
   DH_REQUIRE(dz_dev && x_dev && dw_dev && (ks == 1 || ks == 3) && cin % 64 == 0 && cout % 64 == 0 && repeat >= 1, "debug wgrad bf16: bad arguments");

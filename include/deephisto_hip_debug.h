@@ -61,6 +61,18 @@ int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float* w_dev, uin
 int dh_debug_stem_wgrad_bf16(const uint16_t* dz_dev, const float* x_nchw_dev, float* dw_dev, int32_t B, int32_t P, void* stream);
 int dh_debug_wgrad_bf16(const uint16_t* dz_dev, const uint16_t* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi,
                         int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t repeat, void* stream);
+/* dh_debug_conv_bf16: ONE convolution of the bf16 training engine on caller data (bf16 bits, NHWC), forward or data gradient, exactly as a
+ * step launches it: both operands are packed from float32 w[cout][cin][ks][ks] by the step's packer, and the step's own dispatch picks the
+ * tile and the variant (nothing of that choice is restated in the hook).  Hi x Wi is always the convolution's INPUT size.
+ *   dgrad = 0: in = x [B][Hi][Wi][cin],   out = Z [B][Ho][Wo][cout], raw (no epilogue); res must be null
+ *   dgrad = 1: in = dZ [B][Ho][Wo][cout], out = dX [B][Hi][Wi][cin] (+ res, the gradient joining from another branch; may be null).
+ *              1x1 / stride 2 follows the engine's accumulate contract: out starts from res (or zero), the low-resolution product is
+ *              stored as bf16 and then added into it (two stored roundings).
+ * Refused (dh_last_error names the argument): ks outside {1, 3}, stride outside {1, 2}, cin / cout not multiples of 64, and an odd Hi or
+ * Wi at stride 2 -- the engine requires P % 32 == 0, so every map in front of a stride-2 convolution is even and odd ones are
+ * unreachable in bf16 (the float32 engine's odd maps: dh_debug_dgrad_f32).  Synchronises. */
+int dh_debug_conv_bf16(const uint16_t* in_dev, const float* w_dev, const uint16_t* res_dev, uint16_t* out_dev, int32_t B, int32_t Hi,
+                       int32_t Wi, int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t dgrad, void* stream);
 
 /* ---- debug / test hooks (not part of the drop-in boundary) ---------------------
  * dh_debug_conv_bn_act: one conv (ks in {1,3}, pad ks/2) + per-channel scale/shift

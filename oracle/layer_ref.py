@@ -61,6 +61,62 @@ def conv_epilogue(x, w, scale, shift, stride: int, res=None, relu: bool = True, 
     return y, a.numpy()
 
 
+def conv_dgrad(dz, w, stride: int, Hi: int, Wi: int, res=None, fmt: str = "bf16", exact: bool = False):
+    """Data gradient of y = conv(x, w) (pad ks // 2) in float64: dz [N][cout][Ho][Wo], w [cout][cin][ks][ks], res (the gradient joining
+    from another branch) [N][cin][Hi][Wi] or None.  Hi x Wi is the convolution's INPUT size: at stride 2 an even map and an odd one
+    give the same Ho, and the transposed convolution needs the output padding that tells them apart.  Returns (want, A):
+
+      want = conv_transpose(dz, w) (+ res) rounded ONCE to `fmt` (exact=True: the unrounded float64 value);
+      A    = conv_transpose(|dz|, |w|) (+ |res|).
+
+    The contraction runs over cout * ks * ks terms: K of the gate is rounding_count(cout, ks, fmt, res is not None) -- the engine's
+    multiply by ones and add of zeros are exact and stay under the two roundings that count keeps for the epilogue."""
+    d = lambda t: torch.as_tensor(np.asarray(t), dtype=torch.float64)  # noqa: E731
+    dz, w = d(dz), d(w)
+    ks, pad = w.shape[-1], w.shape[-1] // 2
+    Ho, Wo = (Hi + 2 * pad - ks) // stride + 1, (Wi + 2 * pad - ks) // stride + 1
+    assert tuple(dz.shape[2:]) == (Ho, Wo), f"dz is {tuple(dz.shape[2:])}, the conv of a {Hi} x {Wi} map gives {Ho} x {Wo}"
+    op = (Hi - ((Ho - 1) * stride - 2 * pad + ks), Wi - ((Wo - 1) * stride - 2 * pad + ks))   # rows / columns no output pixel reaches from
+    y = F.conv_transpose2d(dz, w, None, stride, pad, output_padding=op)
+    a = F.conv_transpose2d(dz.abs(), w.abs(), None, stride, pad, output_padding=op)
+    if res is not None:
+        r = d(res)
+        y, a = y + r, a + r.abs()
+    y = y.numpy()
+    return (y if exact else round_to(y, fmt)), a.numpy()
+
+
+def stored_product_sum(prod, res, fmt: str = "bf16") -> np.ndarray:
+    """The value the accumulate contract DEFINES for an exact product: the product is stored in `fmt`, then added to `res` (None: zero)
+    and stored again -- round(res + round(prod)), two roundings of exact float64 values."""
+    t = round_to(prod, fmt)
+    return t if res is None else round_to(np.asarray(res, np.float64) + t, fmt)
+
+
+def stored_product_gate_mask(got, want, A, K: int, prod, A_prod, fmt: str = "bf16") -> np.ndarray:
+    """Gate of a data gradient that reaches memory in TWO stored roundings (the strided 1x1 convolution of a downsample branch: the
+    low-resolution product goes to bf16 scratch, then it is added into dX, which already holds the other branch's gradient `res`).
+
+    With p the exact product, p_c the engine's f32 accumulation of it, T = rn(p_c) the stored product, s = fl32(res + T) and
+    got = rn(s), against y = res + p and want = rn(y):
+
+      |p_c - p|       <= gamma_{cout - 1} A_prod                               (f32 dot product of exact bf16 x bf16 products)
+      |T - p_c|       <= ulp(p_c) / 2 <= quantum(|p| + gamma_K A_prod) / 2     (the extra stored rounding; quantum is monotone)
+      |s - (res + T)| <= u (|res| + |T|) <= 2 u (|res| + A_prod)               (|T| <= |p| (1 + 2^-8) + gamma_K A_prod <= 2 A_prod)
+
+    so |s - y| <= gamma_K A + quantum(|p| + gamma_K A_prod) / 2 with A = A_prod + |res| and K = rounding_count(cout, 1, fmt, True) =
+    (cout - 1) + 3: the dot product's additions, and three for the one f32 addition (bounded by 2 u above; the GEMM has no other
+    epilogue arithmetic).  The final rounding of s against that of y adds at most one unit of the format, as in `gate_mask`:
+
+      |got - want| <= ulp(want) + gamma_K A + quantum(|p| + gamma_K A_prod) / 2.
+
+    `prod`, `A_prod`: conv_dgrad(..., res=None, exact=True) of the same operands; want, A: conv_dgrad with res."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    g = gamma(K)
+    extra = 0.5 * quantum(np.abs(np.asarray(prod, np.float64)) + g * np.asarray(A_prod, np.float64), fmt)
+    return np.abs(got - want) <= quantum(want, fmt) + g * np.asarray(A, np.float64) + extra
+
+
 def gamma(K: int) -> float:
     u = 2.0 ** -24
     return K * u / (1 - K * u)

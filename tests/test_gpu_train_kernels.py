@@ -260,6 +260,12 @@ def test_gemm1x1_bf16_kernel(dev, M, N, K, stride):
     got = out.float().cpu().double()
     assert float((got - want).abs().max()) <= 2 ** -8 * max(1.0, float(want.abs().max()))
     assert _rel(got, want) <= 3e-3
+    # element by element: |got - round(want)| <= ulp + gamma_K A (oracle/layer_ref.py); the maximum above lets a small element be anything
+    from oracle import layer_ref as lr
+    A = rows.double().abs() @ w.double().abs().T + res.double().abs()
+    ok = lr.gate_mask(got.numpy(), lr.round_to(want.numpy(), "bf16"), A.numpy(), lr.rounding_count(K, 1, "bf16", True), "bf16")
+    bad = np.argwhere(~ok)
+    assert ok.all(), f"{len(bad)} of {ok.size} elements outside the gate, first (row, channel) {bad[:8].tolist()}, rows {np.unique(bad[:, 0])[:16].tolist()}"
 
 
 @pytest.mark.parametrize("ks,stride,cin,cout,B,H", [
@@ -569,3 +575,25 @@ def test_pack_bf16_tiles_match_the_elementwise_form(dev, cout, cin):
     check(lib().dh_debug_pack_bf16(w.data_ptr(), cout, cin, *[o.data_ptr() for o in outs], None), "dh_debug_pack_bf16")
     assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[3])
     assert int((outs[0] == 0x7FC0).sum()) == 0 and int((outs[1] == 0x7FC0).sum()) == 0
+    if (cout, cin) != (128, 64):
+        return
+    # ... and to ground truth, not only to each other: the packed operands decoded by the kernels that read them (dh_debug_conv_bf16, which
+    # packs with the same kernel).  Image b of a one-hot batch holds a single 1.0 at the centre of a 5 x 5 map in channel b, so every
+    # output is one weight times one (exact) plus zeros.  Forward: Z[b][co] around the centre is w[co][b] flipped; data gradient:
+    # dX[b][ci] around the centre is w[b][ci] as it stands -- the flipped and transposed operand undoes the forward's flip.
+    wb = w.bfloat16().view(torch.int16).cpu()
+    for dgrad, n_in, n_out in ((0, cin, cout), (1, cout, cin)):
+        hot = torch.zeros(n_in, 5, 5, n_in, dtype=torch.bfloat16, device=dev)
+        b = torch.arange(n_in, device=dev)
+        hot[b, 2, 2, b] = 1.0
+        out = torch.full((n_in, 5, 5, n_out), 0x7FC0, dtype=torch.int16, device=dev)
+        check(lib().dh_debug_conv_bf16(hot.data_ptr(), w.data_ptr(), None, out.data_ptr(), n_in, 5, 5, cin, cout, 3, 1, dgrad, None), "one-hot conv")
+        got = out.cpu()[:, 1:4, 1:4, :]                                   # [b][y][x][channel]
+        if dgrad:
+            want = wb.permute(0, 2, 3, 1)                                 # [co = b][ky][kx][ci]
+        else:
+            want = wb.flip(2, 3).permute(1, 2, 3, 0)                      # [ci = b][2 - ky][2 - kx][co]
+        assert torch.equal(got, want), ("dgrad" if dgrad else "forward", int((got != want).sum()))
+        ring = out.cpu().clone()
+        ring[:, 1:4, 1:4, :] = 0
+        assert int((ring & 0x7FFF).abs().sum()) == 0, "weights leaked outside the 3 x 3 neighbourhood"
