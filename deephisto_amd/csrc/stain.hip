@@ -18,18 +18,17 @@
 #include <algorithm>
 
 #include "dh_common.h"
+#include "stain_fixed.h"
 
 namespace {
+using namespace dh_stain;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int64_t kMaxGrid = 256 * 8;      // as tissue.hip: 8 workgroups per CU on 256 CUs
-constexpr int kOdMax = 22713;              // round(ln(256) * 2^12): the largest table value the entries accept
 constexpr int64_t kMaxPixels = INT64_MAX / ((int64_t)kOdMax * kOdMax);   // a product sum of all-black pixels stays below 2^63
 constexpr int kAngleBins = 1024;
 constexpr int kConcBins = 2048;
-constexpr int kLutMax = 24576;
-constexpr int kCoefMax = 1 << 19;          // |fixed-point matrix entry|: 3 * 2^19 * kOdMax < 2^36
 constexpr int kEvecMax = 1 << 14;          // |eigenvector component|: the projections stay inside int32
 
 struct Vec23 { int32_t m[2][3]; };

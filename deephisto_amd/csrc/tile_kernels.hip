@@ -15,6 +15,7 @@
 
 #include "dh_common.h"
 #include "env_knobs.h"
+#include "stain_fixed.h"
 
 namespace dh {
 static thread_local std::string g_err;
@@ -400,6 +401,119 @@ extern "C" int dh_tile_gather_aug(const uint8_t* slide, int64_t h, int64_t w, co
     if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL((gather_aug_kernel<false, false>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
     else hipLaunchKernelGGL((gather_aug_kernel<true, false>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
   }
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// Gather with the flips above and a per-tile stain jitter, integer-exact: a pixel inside the slide goes
+// bytes -> optical densities T (the 256-entry table) -> o_c = A_c . T + b_c in int64 with the tile's fixed-point matrix and bias
+// -> v'_c = lut[clamp(o_c >> shift, 0, lut_n - 1)] -> v'_c / 255; a pixel outside the slide is 0 as above, not transformed.
+// One thread per output PIXEL (all three channels need all three inputs), in output order, so NCHW is three coalesced plane
+// writes and NHWC 3 consecutive elements per lane.  Both tables live in LDS (1 KiB + lut_n bytes); a workgroup covers
+// kStainPxPerWg pixels of one tile, which amortises loading them, and reads the tile's 12 parameters once (uniform loads).
+constexpr int kStainPxPerWg = 4096;   // 16 pixels per thread: 12 KiB of slide bytes and 24-48 KiB of output per 25 KiB of tables
+
+template <bool BF16>
+__device__ __forceinline__ void st_elem(void* outv, int64_t o, float f) {
+  if constexpr (BF16) static_cast<uint16_t*>(outv)[o] = (uint16_t)f32_to_bf16_bits(f);
+  else static_cast<float*>(outv)[o] = f;
+}
+
+template <bool BF16, bool NCHW>
+__global__ __launch_bounds__(256) void gather_stain_aug_kernel(const uint8_t* __restrict__ slide, int64_t row_bytes, int h, int w,
+                                                               const int32_t* __restrict__ yx, const int32_t* __restrict__ params,
+                                                               int P, int flip_h, int flip_v, const int32_t* __restrict__ od,
+                                                               int shift, const uint8_t* __restrict__ lut, int lut_n,
+                                                               void* __restrict__ outv) {
+  __shared__ int32_t s_od[256];
+  __shared__ __attribute__((aligned(16))) uint8_t s_lut[dh_stain::kLutMax];
+  s_od[threadIdx.x] = od[threadIdx.x];   // 256 threads, 256 entries
+  const int lut16 = lut_n >> 4;          // lut is 16-byte aligned (checked by the entry)
+  for (int i = threadIdx.x; i < lut16; i += 256) reinterpret_cast<uint4*>(s_lut)[i] = reinterpret_cast<const uint4*>(lut)[i];
+  for (int i = (lut16 << 4) + threadIdx.x; i < lut_n; i += 256) s_lut[i] = lut[i];
+  const int t = blockIdx.y;
+  const int y0 = yx[2 * t], x0 = yx[2 * t + 1];
+  int32_t A[3][3], b[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) A[k / 3][k % 3] = params[12 * (int64_t)t + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) b[k] = params[12 * (int64_t)t + 9 + k];
+  __syncthreads();
+  const int64_t plane = (int64_t)P * P;
+  const int64_t p0 = (int64_t)blockIdx.x * kStainPxPerWg;   // first output pixel of this workgroup: row r0, column c0 (uniform)
+  const int r0 = (int)(p0 / P), c0 = (int)(p0 - (int64_t)r0 * P);
+  const int live = (int)std::min<int64_t>(plane - p0, kStainPxPerWg);
+  for (int q = threadIdx.x; q < live; q += 256) {
+    const uint32_t lin = (uint32_t)c0 + (uint32_t)q;        // < P + kStainPxPerWg: no overflow (checked by the entry)
+    const int dr = (int)(lin / (uint32_t)P);
+    const int r = r0 + dr, px = (int)(lin - (uint32_t)dr * (uint32_t)P);
+    const int yy = y0 + (flip_v ? P - 1 - r : r), xx = x0 + (flip_h ? P - 1 - px : px);
+    float f[3] = {0.f, 0.f, 0.f};
+    if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
+      const uint8_t* src = slide + (int64_t)yy * row_bytes + (int64_t)xx * 3;
+      const int32_t tr = s_od[src[0]], tg = s_od[src[1]], tb = s_od[src[2]];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int64_t o = (int64_t)A[c][0] * tr + (int64_t)A[c][1] * tg + (int64_t)A[c][2] * tb + b[c];
+        const int k = (int)std::min<int64_t>(std::max<int64_t>(o >> shift, 0), lut_n - 1);   // arithmetic shift: floor
+        f[c] = div255(s_lut[k]);
+      }
+    }
+    const int64_t p = p0 + q;
+    if (NCHW) {
+      const int64_t o = (int64_t)t * 3 * plane + p;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) st_elem<BF16>(outv, o + c * plane, f[c]);
+    } else {
+      const int64_t o = ((int64_t)t * plane + p) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) st_elem<BF16>(outv, o + c, f[c]);
+    }
+  }
+}
+
+extern "C" int dh_tile_gather_stain_aug(const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, const int32_t* params_dev,
+                                        const int32_t* params_host_check, int64_t n, int32_t P, int32_t layout, int32_t dtype,
+                                        int32_t flip_h, int32_t flip_v, const int32_t* od_dev, const int32_t* od_host, int32_t shift,
+                                        const uint8_t* lut_dev, int32_t lut_n, void* out, void* stream) {
+  using namespace dh_stain;
+  DH_REQUIRE(n >= 0 && n <= 65535, "tile gather stain aug: n=%lld out of range [0, 65535]", (long long)n);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(slide && yx_dev && params_dev && od_dev && od_host && lut_dev && out, "tile gather stain aug: null pointer");
+  DH_REQUIRE(h > 0 && w > 0 && h <= INT32_MAX && w <= INT32_MAX, "tile gather stain aug: bad slide size %lld x %lld", (long long)h,
+             (long long)w);
+  DH_REQUIRE(P > 0 && h >= P && w >= P && P <= INT32_MAX - kStainPxPerWg, "tile gather stain aug: patch %d does not fit %lldx%lld", P,
+             (long long)h, (long long)w);
+  DH_REQUIRE(layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW, "tile gather stain aug: bad layout %d", layout);
+  DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "tile gather stain aug: bad dtype %d", dtype);
+  DH_REQUIRE(lut_n > 0 && lut_n <= kLutMax, "tile gather stain aug: lut_n = %d, an output table has 1 to %d entries", lut_n, kLutMax);
+  DH_REQUIRE(((uintptr_t)lut_dev & 15) == 0, "tile gather stain aug: lut_dev must be 16-byte aligned");
+  DH_REQUIRE(shift >= 0 && shift < 40, "tile gather stain aug: shift %d outside [0, 40)", shift);
+  for (int i = 0; i < 256; ++i)
+    DH_REQUIRE(od_host[i] >= 0 && od_host[i] <= kOdMax, "tile gather stain aug: od table entry %d = %d outside [0, %d]", i, od_host[i],
+               kOdMax);
+  if (params_host_check)
+    for (int64_t i = 0; i < 12 * n; ++i) {
+      const int32_t v = params_host_check[i], lim = i % 12 < 9 ? kCoefMax : kBiasMax;
+      DH_REQUIRE(v >= -lim && v <= lim, "tile gather stain aug: params row %lld, %s entry %d = %d outside +-%d", (long long)(i / 12),
+                 i % 12 < 9 ? "matrix" : "bias", (int)(i % 12 < 9 ? i % 12 : i % 12 - 9), v, lim);
+    }
+  const int64_t blocks = ((int64_t)P * P + kStainPxPerWg - 1) / kStainPxPerWg;
+  DH_REQUIRE(blocks <= INT32_MAX, "tile gather stain aug: patch %d too large", P);
+  hipStream_t st = dh::as_stream(stream);
+  dim3 grid((unsigned)blocks, (unsigned)n), block(256);
+  const int64_t rb = w * 3;
+#define DH_STAIN_AUG_LAUNCH(BF, NC)                                                                                              \
+  hipLaunchKernelGGL((gather_stain_aug_kernel<BF, NC>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, params_dev, P, flip_h, \
+                     flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out)
+  if (layout == DH_LAYOUT_NCHW) {
+    if (dtype == DH_DTYPE_F32) DH_STAIN_AUG_LAUNCH(false, true);
+    else DH_STAIN_AUG_LAUNCH(true, true);
+  } else {
+    if (dtype == DH_DTYPE_F32) DH_STAIN_AUG_LAUNCH(false, false);
+    else DH_STAIN_AUG_LAUNCH(true, false);
+  }
+#undef DH_STAIN_AUG_LAUNCH
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -8,7 +8,8 @@ holding `model.state_dict()` (train.py:244-249).
 
 What moved to the GPU: the step itself (forward, CrossEntropy, backward, Adam: HIP kernels,
 `ResNet18HIP.train_step`), batch assembly (gather + /255 + NCHW + batch-level flips in
-`dh_tile_gather_aug`), and the running loss / accuracy sums (accumulated on the device, read
+`dh_tile_gather_aug`; with `dataset.stain_augment` the training batches also get a per-patch stain jitter,
+`dh_tile_gather_stain_aug`), and the running loss / accuracy sums (accumulated on the device, read
 once per epoch instead of four host syncs per step, train.py:174-180).
 
 The test set is the reference's: `--extract_test` cuts `test.samples_per_class` JPEG patches per class
@@ -53,6 +54,28 @@ def _stain_from_cfg(cfg):
     return StainNormalizer(name)
 
 
+def _stain_aug_from_cfg(cfg, rank: int = 0):
+    """The StainAugmenter of the optional `dataset.stain_augment: {sigma_alpha, sigma_beta, seed}` (absent: None).  Every key is
+    optional; an unknown key or a bad value is refused by name.  Data parallel: rank r draws from seed + r, like the samplers'
+    rank-seeded streams, so the replicas see different jitter."""
+    entry = cfg.get("dataset", {}).get("stain_augment")
+    if entry is None:
+        return None
+    from ...stain import StainAugmenter
+    if not isinstance(entry, dict):
+        raise ValueError(f"dataset.stain_augment must be a mapping with the keys sigma_alpha, sigma_beta, seed, not {entry!r}")
+    unknown = sorted(set(entry) - {"sigma_alpha", "sigma_beta", "seed"})
+    if unknown:
+        raise ValueError(f"dataset.stain_augment: unknown key(s) {unknown} (known: sigma_alpha, sigma_beta, seed)")
+    seed = entry.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"dataset.stain_augment.seed must be a non-negative integer, not {seed!r}")
+    try:
+        return StainAugmenter(entry.get("sigma_alpha", 0.2), entry.get("sigma_beta", 0.0), seed + rank)
+    except ValueError as e:
+        raise ValueError(f"dataset.stain_augment.{e}") from None
+
+
 def _synthetic_sampler(cfg, device):
     from ... import tiles
 
@@ -61,7 +84,8 @@ def _synthetic_sampler(cfg, device):
     regions = synthetic_regions(side, side, cfg["model"]["n_classes"], seed=0)
     return RectRegionRndSampler(slide, regions, layer=cfg["dataset"]["layer"], patch_size=cfg["dataset"]["patch_size"],
                                 patches_from_one_region=cfg["dataset"]["patches_from_one_region"], seed=_rank_world()[0],
-                                device=device, stain=_stain_from_cfg(cfg))   # data parallel: every rank draws its own stream of patches
+                                device=device, stain=_stain_from_cfg(cfg),   # data parallel: every rank draws its own stream of patches
+                                stain_aug=_stain_aug_from_cfg(cfg, _rank_world()[0]))
 
 
 def prepare_test_patches(cfg, img_anno_paths=None, device="cuda"):
@@ -192,9 +216,15 @@ def train(cfg, sampler=None, epochs=None, steps_per_epoch=200, log=print, model=
                                            patch_size=cfg["dataset"]["patch_size"], layer=cfg["dataset"]["layer"],
                                            patches_from_one_region=cfg["dataset"]["patches_from_one_region"],
                                            one_image_for_batch=cfg["training"].get("one_image_for_batch", False),
-                                           device=device, stain=_stain_from_cfg(cfg))
+                                           device=device, stain=_stain_from_cfg(cfg), stain_aug=_stain_aug_from_cfg(cfg, rank))
         else:
             sampler = _synthetic_sampler(cfg, device)
+
+    elif _stain_aug_from_cfg(cfg, rank) is not None and getattr(sampler, "stain_aug", False) is None:
+        sampler.stain_aug = _stain_aug_from_cfg(cfg, rank)   # an injected sampler that can jitter and was given no augmenter of its own
+    # stain jitter is for the training batches only: a sampler that has an augmenter is told to leave it
+    # out of the validation batches; samplers without one are called as before
+    no_jitter = {"stain_aug": False} if getattr(sampler, "stain_aug", None) is not None else {}
 
     bs = cfg["training"]["batch_size"]
     # `model.arch: resnet50` selects the backbone of BASELINE configs[4] (bf16 engine); under torchrun (one process per GPU)
@@ -233,7 +263,7 @@ def train(cfg, sampler=None, epochs=None, steps_per_epoch=200, log=print, model=
         val_steps = cfg["training"]["val_steps"]
         vloss = torch.zeros((), device=device)
         vcorrect, vtotal = torch.zeros((), device=device, dtype=torch.int64), 0
-        for x, labels, _ in sampler.device_batches(bs, val_steps, flips=True):
+        for x, labels, _ in sampler.device_batches(bs, val_steps, flips=True, **no_jitter):
             logits = model(x)
             vloss += ce_loss(logits, labels)                          # dh_ce_loss: CrossEntropyLoss(mean), train.py:117
             vcorrect += (logits.argmax(1) == labels).sum()

@@ -16,7 +16,8 @@ That OUTPUT CONTRACT is the hot-path boundary.  Two pr
   shapely geometry restated in `polygon.py`.
 
 In both, pixels never leave HBM: batches are cut, normalised (k/255), laid out and flipped by
-`dh_tile_gather` / `dh_tile_gather_aug`.
+`dh_tile_gather` / `dh_tile_gather_aug`, or, with a `stain_aug=StainAugmenter(...)`, by `dh_tile_gather_stain_aug`, which also
+jitters every patch's stain concentrations (`device_batches` only).
 """
 from __future__ import annotations
 
@@ -33,6 +34,16 @@ from . import polygon as _pg
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, DH_LAYOUT_NHWC
 from ..psimage_compat import Patch, open_slide
+
+
+def _gather_jittered(slide, basis, o_dev, patch, layout, dtype, flip_h, flip_v, alpha, beta, uploader):
+    """One slide's share of a batch: the plain flipped gather when the slide has no stain basis (or no jitter was drawn), else
+    the jitter gather with the parameter rows built from the slide's basis and uploaded through `uploader`."""
+    if basis is None or alpha is None:
+        return tiles.gather_tiles_aug(slide, o_dev, patch, layout, dtype, flip_h, flip_v)
+    from ..stain import jitter_params
+    params = jitter_params(basis, alpha, beta)
+    return tiles.gather_tiles_stain_aug(slide, o_dev, patch, layout, dtype, uploader.upload(params), flip_h, flip_v, params_host=params)
 
 
 @dataclass
@@ -54,14 +65,17 @@ class RectRegionRndSampler:
     def __init__(self, slide, regions: Sequence[RectRegion], layer: int, patch_size: int,
                  region_intersection: float = 0.75, patches_from_one_region: int = 4,
                  region_area_influence: float = 0.5, classes: list[str] | None = None, seed: int = 0, device="cuda",
-                 stain=None):
+                 stain=None, stain_aug=None):
         if isinstance(slide, np.ndarray):
             slide = torch.from_numpy(np.ascontiguousarray(slide))
         if slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
             raise ValueError("slide must be uint8[h, w, 3]")
         self.slide = slide.to(device).contiguous()
+        info = {}
         if stain is not None:   # a StainNormalizer: the resident copy is the normalised slide
-            self.slide = stain.normalize(self.slide)
+            self.slide = stain.normalize(self.slide, info)
+        self.stain_aug = stain_aug   # a StainAugmenter: device_batches jitters every patch's stains
+        self._stain, self._stain_fit, self._basis = stain, info.get("fit"), False   # the basis is fitted at the first jittered batch
         self.h, self.w = int(slide.shape[0]), int(slide.shape[1])
         self.layer, self.patch_size = layer, int(patch_size)
         self.region_intersection = float(region_intersection)
@@ -131,11 +145,16 @@ class RectRegionRndSampler:
                 features = transforms(features)
             yield features, torch.from_numpy(lab).to(dev), tiles.tile_coords(o_dev)
 
-    def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32
+    def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32, stain_aug: bool = True
                        ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """Fast path of the training loop: [B,3,P,P] batches with train.py:71-81's
-        permute + batch-level random flips fused into the gather kernel."""
+        permute + batch-level random flips fused into the gather kernel; with a `stain_aug` augmenter (and `stain_aug=True`)
+        every patch's stains are jittered in the same kernel."""
         dev = self.slide.device
+        aug = self.stain_aug if stain_aug else None
+        if aug is not None and self._basis is False:
+            from ..stain import stain_basis
+            self._basis = stain_basis(self.slide, self._stain, self._stain_fit)
         up = getattr(self, "_uploader", None)
         if up is None:
             up = self._uploader = tiles.PinnedUploader(dev)   # origins / labels through pinned staging: the host never waits for the GPU
@@ -144,7 +163,9 @@ class RectRegionRndSampler:
             fh = bool(flips and self._rng.random() < 0.5)
             fv = bool(flips and self._rng.random() < 0.5)
             o_dev, lab_dev, coords = up.upload_batch(yx, lab)   # one staged copy per batch (origins, labels, float coordinates)
-            x = tiles.gather_tiles_aug(self.slide, o_dev, self.patch_size, DH_LAYOUT_NCHW, dtype, fh, fv)
+            alpha, beta = aug.draw(batch_size) if aug is not None else (None, None)
+            x = _gather_jittered(self.slide, self._basis if aug is not None else None, o_dev, self.patch_size, DH_LAYOUT_NCHW, dtype,
+                                 fh, fv, alpha, beta, up)
             yield x, lab_dev, coords
 
 
@@ -286,7 +307,7 @@ def _parse_annotations(img_anno_paths, layer: int, classes: list[str] | None = N
 class _SlideBank:
     """The images of a sampler: PSImage-like host readers + their layers resident in HBM (uploaded on first use)."""
 
-    def __init__(self, sources, layer: int, device, stain=None):
+    def __init__(self, sources, layer: int, device, stain=None, stain_aug=None):
         self._readers = [open_slide(s) if not isinstance(s, torch.Tensor) else None for s in sources]
         self._dev = [s.to(device).contiguous() if isinstance(s, torch.Tensor) else None for s in sources]
         self.layer, self.device = layer, torch.device(device)
@@ -294,6 +315,12 @@ class _SlideBank:
         # that copy, so host-assembled and device-assembled patches show the same pixels
         self.stain = stain
         self._normalised = [False] * len(sources)
+        # a StainAugmenter: each resident slide's stain basis is learnt once, at its first jittered batch:
+        # the normaliser's target when the slide was just mapped onto it, else one default Macenko fit; None: an identity fit
+        # (all glass, degenerate plane), that slide's patches are gathered un-jittered
+        self.stain_aug = stain_aug
+        self._fit = [None] * len(sources)
+        self._basis = [False] * len(sources)
 
     def size(self, j: int) -> tuple[int, int]:
         if self._readers[j] is None:
@@ -325,9 +352,18 @@ class _SlideBank:
             h, w = r.layer_size(self.layer)
             self._dev[j] = torch.from_numpy(np.ascontiguousarray(r.get_region_from_layer(self.layer, (0, 0), (h, w)))).to(self.device)
         if self.stain is not None and not self._normalised[j]:
-            self._dev[j] = self.stain.normalize(self._dev[j])   # a new tensor: a caller's own slide is left as it is
-            self._normalised[j] = True
+            info = {}
+            self._dev[j] = self.stain.normalize(self._dev[j], info)   # a new tensor: a caller's own slide is left as it is
+            self._normalised[j], self._fit[j] = True, info["fit"]
         return self._dev[j]
+
+    def basis(self, j: int):
+        """float64[3, 2] stain basis of the resident slide j, fitted at the first call (None: identity fit, or no augmenter)."""
+        slide = self.slide(j)
+        if self.stain_aug is not None and self._basis[j] is False:
+            from ..stain import stain_basis
+            self._basis[j] = stain_basis(slide, self.stain, self._fit[j])
+        return None if self._basis[j] is False else self._basis[j]
 
 
 class AnnoRegionRndSampler:
@@ -339,7 +375,7 @@ class AnnoRegionRndSampler:
 
     def __init__(self, img_anno_paths, layer: int, patch_size: int, region_intersection: float = 0.75,
                  patches_from_one_region: int = 4, region_area_influence: float = 0.5, classes: list[str] = None,
-                 one_image_for_batch: bool = False, device="cuda", stain=None):
+                 one_image_for_batch: bool = False, device="cuda", stain=None, stain_aug=None):
         self.img_anno_paths = img_anno_paths
         self.layer = layer
         self.patch_size = patch_size
@@ -353,7 +389,16 @@ class AnnoRegionRndSampler:
             raise ValueError("no usable annotated regions")
         self._reg_w_all, self._reg_w_per_img, self._img_w, self._img_w_all = self._calc_weights(
             self.regions, self.regions_per_image)
-        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain)
+        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug)
+
+    @property
+    def stain_aug(self):
+        """The StainAugmenter of `device_batches` (None: no stain jitter); DESIGN.md section 4.12."""
+        return self._bank.stain_aug
+
+    @stain_aug.setter
+    def stain_aug(self, aug):
+        self._bank.stain_aug = aug
 
     # ---- weights (region_samplers.py:339-482) ------------------------------------------------------------
     def _calc_area_weights(self, areas, area_influence: float):
@@ -439,21 +484,27 @@ class AnnoRegionRndSampler:
                 yield lst[k:k + batch_size]
 
     # ---- device batches --------------------------------------------------------------------------------
-    def _assemble(self, recs, layout: int, dtype, flip_h: bool = False, flip_v: bool = False):
-        """Cut the records' patches from the HBM-resident slides into one batch tensor (+ labels, coords)."""
+    def _assemble(self, recs, layout: int, dtype, flip_h: bool = False, flip_v: bool = False, aug=None):
+        """Cut the records' patches from the HBM-resident slides into one batch tensor (+ labels, coords).  `aug`: a
+        StainAugmenter; one (alpha, beta) row per record, drawn in record order before the batch is split by slide, so the draw
+        does not depend on how the records group."""
         dev, ps = self._bank.device, self.patch_size
         arr = np.array(recs, dtype=np.int64).reshape(-1, 4)
         out = None
         up = getattr(self, "_uploader", None)
         if up is None:
             up = self._uploader = tiles.PinnedUploader(dev, depth=8)   # non-blocking uploads (tiles.PinnedUploader)
+        alpha, beta = aug.draw(len(arr)) if aug is not None else (None, None)
         if (arr[:, 0] == arr[0, 0]).all():   # the whole batch from one slide (always so with one_image_for_batch): one staged copy
             o_dev, labels, coords = up.upload_batch(arr[:, 1:3].astype(np.int32), arr[:, 3].copy())
-            return tiles.gather_tiles_aug(self._bank.slide(int(arr[0, 0])), o_dev, ps, layout, dtype, flip_h, flip_v), labels, coords
+            j = int(arr[0, 0])
+            return _gather_jittered(self._bank.slide(j), self._bank.basis(j) if aug is not None else None, o_dev, ps, layout, dtype,
+                                    flip_h, flip_v, alpha, beta, up), labels, coords
         for j in np.unique(arr[:, 0]):
             sel = np.nonzero(arr[:, 0] == j)[0]
             o_dev = up.upload(arr[sel, 1:3].astype(np.int32))
-            part = tiles.gather_tiles_aug(self._bank.slide(int(j)), o_dev, ps, layout, dtype, flip_h, flip_v)
+            part = _gather_jittered(self._bank.slide(int(j)), self._bank.basis(int(j)) if aug is not None else None, o_dev, ps, layout,
+                                    dtype, flip_h, flip_v, None if aug is None else alpha[sel], None if aug is None else beta[sel], up)
             if len(sel) == len(arr):
                 out = part
             else:
@@ -480,15 +531,19 @@ class AnnoRegionRndSampler:
                 yield features, labels, coords
 
     def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32,
-                       batches_per_worker: int = 2) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+                       batches_per_worker: int = 2, stain_aug: bool = True
+                       ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """Training fast path: [B,3,P,P] batches with train.py:69-81's permute + RandomHorizontalFlip +
-        RandomVerticalFlip (one torch coin each per batch, in that order) fused into the gather kernel."""
+        RandomVerticalFlip (one torch coin each per batch, in that order) fused into the gather kernel.  With a `stain_aug`
+        augmenter (and `stain_aug=True`) every patch's stains are jittered in the same kernel; the augmenter draws from its own
+        stream, so records and coins are what they are without it."""
+        aug = self._bank.stain_aug if stain_aug else None
         for i in self._split_chunks(n_batches, batches_per_worker):
             recs = self._records(batch_size * i)
             for k in range(0, len(recs), batch_size):
                 fh = bool(flips and torch.rand(1).item() < 0.5)
                 fv = bool(flips and torch.rand(1).item() < 0.5)
-                yield self._assemble(recs[k:k + batch_size], DH_LAYOUT_NCHW, dtype, fh, fv)
+                yield self._assemble(recs[k:k + batch_size], DH_LAYOUT_NCHW, dtype, fh, fv, aug)
 
 
     def torch_iterable_dataset(self):
@@ -515,7 +570,7 @@ class AnnoRegionDenseSampler:
     """Every grid patch of every annotated region, class by class (region_samplers.py:799-871)."""
 
     def __init__(self, img_anno_paths, layer: int, patch_size: int, stride: int, region_intersection: float = 0.75,
-                 classes: list[str] = None, device="cuda", stain=None):
+                 classes: list[str] = None, device="cuda", stain=None, stain_aug=None):
         self.img_anno_paths = img_anno_paths
         self.layer = layer
         self.patch_size = patch_size
@@ -523,7 +578,16 @@ class AnnoRegionDenseSampler:
         self.region_intersection = region_intersection
         self.regions, _ = _parse_annotations(img_anno_paths, layer=layer, classes=classes)
         self.classes = sorted(list(self.regions.keys()))
-        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain)
+        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug)
+
+    @property
+    def stain_aug(self):
+        """The StainAugmenter of `device_batches` (None: no stain jitter); DESIGN.md section 4.12."""
+        return self._bank.stain_aug
+
+    @stain_aug.setter
+    def stain_aug(self, aug):
+        self._bank.stain_aug = aug
 
     def _patches_one_region(self, region: RegionAnnotation) -> list[Patch]:
         ps = self.patch_size
@@ -538,10 +602,13 @@ class AnnoRegionDenseSampler:
                 for p in self._patches_one_region(region):
                     yield p, cls_idx
 
-    def device_batches(self, batch_size: int, layout: int = DH_LAYOUT_NCHW, dtype=torch.float32
+    def device_batches(self, batch_size: int, layout: int = DH_LAYOUT_NCHW, dtype=torch.float32, stain_aug: bool = True
                        ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        """The same patches in the same order as device tensors (tiles cut on the GPU), `batch_size` at a time."""
+        """The same patches in the same order as device tensors (tiles cut on the GPU), `batch_size` at a time; with a
+        `stain_aug` augmenter (and `stain_aug=True`) every patch's stains are jittered, one draw per batch."""
         dev, ps = self._bank.device, self.patch_size
+        aug = self._bank.stain_aug if stain_aug else None
+        up = None
         for cls_idx, cls in enumerate(self.classes):
             for region in self.regions[cls]:
                 coords = region._extract_patch_coords_dense(patch_size=ps, stride=self.stride,
@@ -551,7 +618,14 @@ class AnnoRegionDenseSampler:
                     o_dev = torch.from_numpy(o).to(dev)
                     # bounds-safe gather (zero outside the image): dense origins of a region that touches or leaves
                     # the image border can be negative or hang over it (region_samplers.py:160-166)
-                    x = tiles.gather_tiles_aug(self._bank.slide(region.image_index), o_dev, ps, layout, dtype)
+                    j = region.image_index
+                    if aug is None:
+                        x = tiles.gather_tiles_aug(self._bank.slide(j), o_dev, ps, layout, dtype)
+                    else:
+                        up = up or tiles.PinnedUploader(dev)
+                        alpha, beta = aug.draw(len(o))
+                        x = _gather_jittered(self._bank.slide(j), self._bank.basis(j), o_dev, ps, layout, dtype, False, False,
+                                             alpha, beta, up)
                     yield x, torch.full((len(o),), cls_idx, dtype=torch.int64, device=dev), tiles.tile_coords(o_dev)
 
 

@@ -31,6 +31,8 @@ CONC_BINS = 2048                # per stain
 CONC_SHIFT = OD_BITS + COEF_BITS - 8    # bin width 2^-8 = 0.0039; the last bin collects c >= 8 - 2^-8, the first c < 2^-8
 CONC_WIDTH = 2.0 ** -8
 APPLY_SHIFT = COEF_BITS         # OD' index in units of 2^-12
+BIAS_BITS = OD_BITS + COEF_BITS # the jitter's bias, in the units of matrix x table
+BIAS_MAX = 1 << 30              # |fixed-point bias| the jitter gather accepts (|b| <= 64 in optical density)
 LUT_SIZE = 24576                # OD' in [0, 6): v' = 0 from OD' = ln(512 / 3) = 5.14 on
 MIN_STAINED = 16                # fewer stained pixels: identity fit
 MAX_PIXELS = (2 ** 63 - 1) // (OD_MAX * OD_MAX)   # 17 878 897 106 pixels: the 64-bit product sums cannot overflow below it
@@ -86,6 +88,7 @@ def overflow_bounds(npix: int = MAX_PIXELS) -> dict:
         "cross_product": (2 * (1 << DIR_BITS) * proj, 2 ** 63),
         "concentration": (3 * COEF_MAX * OD_MAX, 2 ** 63),
         "applied_od": (3 * COEF_MAX * OD_MAX, 2 ** 63),
+        "jittered_od": (3 * COEF_MAX * OD_MAX + BIAS_MAX, 2 ** 63),   # the jitter gather: matrix . T + bias (section 4.12)
         "histogram_bin": (npix, 2 ** 64),
         # an LDS copy is shared by at most one workgroup of a grid of 2 048 (or every lane has one group of 16 pixels)
         "lds_bin": (npix // 2048 + 16 * 256 + 16, 2 ** 32),
@@ -199,6 +202,64 @@ def quantize_coef(m, what: str) -> np.ndarray:
     if not np.all(np.isfinite(q)) or np.abs(q).max() > COEF_MAX:
         raise ValueError(f"{what}: an entry exceeds {COEF_MAX >> COEF_BITS} in magnitude (stain vectors too close to parallel?)")
     return q.astype(np.int32)
+
+
+def jitter_params(he, alpha, beta) -> np.ndarray:
+    """int32[n, 12]: per tile the fixed-point matrix A = I + HE diag(alpha - 1) pinv(HE) (9 entries, row-major, 2^COEF_BITS) and
+    bias b = HE beta (3 entries, 2^BIAS_BITS) of the stain jitter OD' = A OD + b = OD + HE ((alpha - 1) * c + beta) with
+    c = pinv(HE) OD the pixel's two concentrations.  `he`: the slide's 3 x 2 stain basis, haematoxylin
+    first; `alpha`, `beta`: float64[n, 2].  alpha = 1, beta = 0 gives exactly (2^COEF_BITS I, 0)."""
+    he = np.asarray(he, dtype=np.float64)
+    alpha, beta = np.asarray(alpha, dtype=np.float64), np.asarray(beta, dtype=np.float64)
+    if he.shape != (3, 2) or not np.all(np.isfinite(he)):
+        raise ValueError("he must be a finite 3 x 2 stain basis")
+    if alpha.ndim != 2 or alpha.shape[1] != 2 or beta.shape != alpha.shape:
+        raise ValueError(f"alpha and beta must both be float64[n, 2], not {list(alpha.shape)} and {list(beta.shape)}")
+    n = alpha.shape[0]
+    out = np.empty((n, 12), dtype=np.int32)
+    if n == 0:
+        return out
+    pinv = pinv32(he)
+    a = np.eye(3)[None] + np.einsum("ck,nk,kd->ncd", he, alpha - 1.0, pinv)
+    out[:, :9] = quantize_coef(a, "jitter matrix").reshape(n, 9)
+    b = np.rint((beta @ he.T) * (1 << BIAS_BITS))
+    if not np.all(np.isfinite(b)) or np.abs(b).max() > BIAS_MAX:
+        raise ValueError(f"jitter bias: an entry exceeds {BIAS_MAX >> BIAS_BITS} in magnitude")
+    out[:, 9:] = b.astype(np.int32)
+    return out
+
+
+class StainAugmenter:
+    """Per-patch stain jitter for training (Tellez et al. 2018, in the slide's own Macenko basis): every patch's haematoxylin
+    and eosin concentrations c become alpha * c + beta with alpha ~ U(1 - sigma_alpha, 1 + sigma_alpha) and
+    beta ~ U(-sigma_beta, sigma_beta) per stain.  The draws come from a private PCG64 stream: NumPy's and torch's global
+    streams, which carry the samplers' reference-exact order and the flip coins, are never touched."""
+
+    def __init__(self, sigma_alpha: float = 0.2, sigma_beta: float = 0.0, seed: int = 0):
+        self.sigma_alpha = _real(sigma_alpha, "sigma_alpha", 0.0, 0.9)
+        self.sigma_beta = _real(sigma_beta, "sigma_beta", 0.0, 0.5)
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or seed < 0:
+            raise ValueError(f"seed must be a non-negative integer, not {seed!r}")
+        self.seed = int(seed)
+        self._rng = np.random.Generator(np.random.PCG64(self.seed))
+
+    def __repr__(self):
+        return f"StainAugmenter(sigma_alpha={self.sigma_alpha}, sigma_beta={self.sigma_beta}, seed={self.seed})"
+
+    def draw(self, n: int) -> tuple[np.ndarray, np.ndarray]:
+        """(alpha float64[n, 2], beta float64[n, 2]) from one uniform draw of n x 4 numbers, columns (aH, aE, bH, bE)."""
+        u = 2.0 * self._rng.uniform(size=(int(n), 4)) - 1.0
+        return 1.0 + self.sigma_alpha * u[:, :2], self.sigma_beta * u[:, 2:]
+
+
+def stain_basis(slide, stain=None, fit=None):
+    """float64[3, 2] basis in which `slide`'s patches are jittered, or None when the slide has none (identity fit: all glass, a
+    degenerate plane).  `slide` as it is resident: after `stain` (a StainNormalizer) mapped it, with `fit` the fit that
+    normalisation found, the basis is the normaliser's target; otherwise one default Macenko fit of the slide."""
+    if stain is not None:
+        return None if fit is None or fit.identity else np.array(stain.target_he, dtype=np.float64)
+    f = StainNormalizer().fit(slide)
+    return None if f.identity else np.array(f.HE, dtype=np.float64)
 
 
 @dataclass

@@ -94,6 +94,35 @@ def gather_tiles_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch: int,
     return out
 
 
+def gather_tiles_stain_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, layout: int, dtype, params_dev: torch.Tensor,
+                           flip_h: bool = False, flip_v: bool = False, params_host=None) -> torch.Tensor:
+    """gather_tiles_aug with a per-tile stain jitter fused in (dh_tile_gather_stain_aug).
+    `params_dev`: int32[n, 12] on the device, the rows of stain.jitter_params; `params_host`: the same rows on the host, checked
+    by the entry before the launch (None: not checked)."""
+    from . import stain as S
+    _require_cuda(slide, "slide")
+    _require_cuda(origins_dev, "origins")
+    _require_cuda(params_dev, "params")
+    n = int(origins_dev.shape[0])
+    if params_dev.dtype != torch.int32 or tuple(params_dev.shape) != (n, 12):
+        raise ValueError(f"params must be int32[{n}, 12], not {str(params_dev.dtype).replace('torch.', '')}{list(params_dev.shape)}")
+    host = None
+    if params_host is not None:
+        host = np.ascontiguousarray(params_host, dtype=np.int32)
+        if host.shape != (n, 12):
+            raise ValueError(f"params_host must be int32[{n}, 12], not {list(host.shape)}")
+    code = dtype_code(dtype)
+    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
+    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
+    od_dev, _, lut, od = S._tables(slide.device)
+    check(lib().dh_tile_gather_stain_aug(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(),
+                                         params_dev.data_ptr(), host.ctypes.data_as(C.c_void_p) if host is not None else None, n,
+                                         patch, layout, code, int(flip_h), int(flip_v), od_dev.data_ptr(),
+                                         od.ctypes.data_as(C.c_void_p), S.APPLY_SHIFT, lut.data_ptr(), S.LUT_SIZE, out.data_ptr(),
+                                         _stream(slide.device)), "dh_tile_gather_stain_aug")
+    return out
+
+
 class PinnedUploader:
     """Host -> device copies of small per-batch arrays (tile origins, labels) that do not stall the host.
 

@@ -84,6 +84,21 @@ int dh_tile_gather_aug(const uint8_t* slide_dev, int64_t h, int64_t w, const int
                        int64_t n, int32_t patch, int32_t layout, int32_t dtype, int32_t flip_h,
                        int32_t flip_v, void* out_dev, void* stream);
 
+/* dh_tile_gather_aug with a per-tile stain jitter fused in (no counterpart in the
+ * reference).  A source pixel inside the slide goes T_c = od[byte_c]; o_c = A[c][0] T_r + A[c][1] T_g +
+ * A[c][2] T_b + b_c in 64-bit integers; v'_c = lut_dev[clamp(o_c >> shift, 0, lut_n - 1)]; the output is
+ * float32(v'_c) / 255, correctly rounded, then rounded to nearest-even for bf16.  Pixels outside the slide are
+ * written as 0 and are not transformed.  params_dev: int32[n][12], per tile the matrix A row-major
+ * (|.| <= 2^19) then the bias b (|.| <= 2^30); params_host_check: the same values on the host, every one
+ * checked before the launch, or NULL.  od_dev / od_host, lut_dev (16-byte aligned) / lut_n <= 24576 and shift
+ * in [0, 40) as for dh_stain_apply.  Integer work up to the final division: the result is the same bits
+ * wherever it runs. */
+int dh_tile_gather_stain_aug(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                             const int32_t* params_dev, const int32_t* params_host_check, int64_t n, int32_t patch,
+                             int32_t layout, int32_t dtype, int32_t flip_h, int32_t flip_v, const int32_t* od_dev,
+                             const int32_t* od_host, int32_t shift, const uint8_t* lut_dev, int32_t lut_n,
+                             void* out_dev, void* stream);
+
 /* FullImageRndSampler.generator_torch (full_samplers.py:277-290) stacks the uint8 patches into a
  * float tensor WITHOUT dividing by 255: float32[n][P][P][3] with values 0..255 (0 outside the slide). */
 int dh_tile_gather_raw(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
