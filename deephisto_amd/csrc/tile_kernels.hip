@@ -518,6 +518,172 @@ extern "C" int dh_tile_gather_stain_aug(const uint8_t* slide, int64_t h, int64_t
   return DH_OK;
 }
 
+// Gather with the flips above, a per-tile rotation and scale about the patch centre, and optionally the stain jitter (DESIGN.md
+// section 4.13), integer-exact.  With (sr, sx) the flipped row and column of an output pixel, U2 = 2 sx + 1 - P, V2 = 2 sr + 1 - P and
+// the tile's row m = round(2^15 s [[cos, -sin], [sin, cos]]), the source point in Q16 is X = Cx + m00 U2 + m01 V2,
+// Y = Cy + m10 U2 + m11 V2 (int64; Cx = ((2 x0 + P) << 15) - 2^15), its taps (xi, yi) = (X >> 16, Y >> 16) and the three
+// neighbours, its weights fx = (X >> 8) & 255, fy likewise; a tap outside the slide reads as 0.  Per channel
+// v = ((a (256 - fx) + b fx)(256 - fy) + (c (256 - fx) + d fx) fy + 32768) >> 16, and v goes where the slide byte goes in the
+// kernels above: div255(v), or od -> matrix + bias -> lut -> div255 when STAIN.  A pixel none of whose taps of non-zero weight
+// lies inside the slide is written as 0 and not transformed, which for an identity row is the rule of gather_stain_aug_kernel.
+// One thread per output pixel in output order; the tile's 4 (+ 12) parameters are uniform loads; each lane reads two 6-byte row
+// pairs straight from the slide (neighbouring lanes walk a rotated line: a wave's taps stay within a few cache lines).
+constexpr int kAffineMaxPatch = 4096;   // |U2|, |V2| <= P - 1 < 2^12 and |m| <= 2^16: products below 2^28
+constexpr int kAffineCoefMax = 1 << 16;
+
+struct __attribute__((packed, aligned(1))) Px2 { uint32_t lo; uint16_t hi; };   // 2 RGB pixels
+
+template <bool BF16, bool NCHW, bool STAIN>
+__global__ __launch_bounds__(256) void gather_affine_aug_kernel(const uint8_t* __restrict__ slide, int64_t row_bytes, int h, int w,
+                                                                const int32_t* __restrict__ yx, const int32_t* __restrict__ affine,
+                                                                const int32_t* __restrict__ params, int P, int flip_h, int flip_v,
+                                                                const int32_t* __restrict__ od, int shift,
+                                                                const uint8_t* __restrict__ lut, int lut_n, void* __restrict__ outv) {
+  __shared__ int32_t s_od[STAIN ? 256 : 1];
+  __shared__ __attribute__((aligned(16))) uint8_t s_lut[STAIN ? dh_stain::kLutMax : 16];
+  const int t = blockIdx.y;
+  int32_t A[3][3] = {}, b[3] = {};
+  if constexpr (STAIN) {
+    s_od[threadIdx.x] = od[threadIdx.x];   // 256 threads, 256 entries
+    const int lut16 = lut_n >> 4;          // lut is 16-byte aligned (checked by the entry)
+    for (int i = threadIdx.x; i < lut16; i += 256) reinterpret_cast<uint4*>(s_lut)[i] = reinterpret_cast<const uint4*>(lut)[i];
+    for (int i = (lut16 << 4) + threadIdx.x; i < lut_n; i += 256) s_lut[i] = lut[i];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) A[k / 3][k % 3] = params[12 * (int64_t)t + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) b[k] = params[12 * (int64_t)t + 9 + k];
+    __syncthreads();
+  }
+  const int64_t cy = (((int64_t)2 * yx[2 * t] + P) << 15) - (1 << 15), cx = (((int64_t)2 * yx[2 * t + 1] + P) << 15) - (1 << 15);
+  const int64_t m00 = affine[4 * (int64_t)t], m01 = affine[4 * (int64_t)t + 1], m10 = affine[4 * (int64_t)t + 2],
+                m11 = affine[4 * (int64_t)t + 3];
+  const int64_t plane = (int64_t)P * P;
+  const int64_t p0 = (int64_t)blockIdx.x * kStainPxPerWg;   // first output pixel of this workgroup: row r0, column c0 (uniform)
+  const int r0 = (int)(p0 / P), c0 = (int)(p0 - (int64_t)r0 * P);
+  const int live = (int)std::min<int64_t>(plane - p0, kStainPxPerWg);
+  for (int q = threadIdx.x; q < live; q += 256) {
+    const uint32_t lin = (uint32_t)c0 + (uint32_t)q;        // < P + kStainPxPerWg
+    const int dr = (int)(lin / (uint32_t)P);
+    const int r = r0 + dr, px = (int)(lin - (uint32_t)dr * (uint32_t)P);
+    const int u2 = 2 * (flip_h ? P - 1 - px : px) + 1 - P, v2 = 2 * (flip_v ? P - 1 - r : r) + 1 - P;
+    const int64_t X = cx + m00 * u2 + m01 * v2, Y = cy + m10 * u2 + m11 * v2;
+    const int64_t xi = X >> 16, yi = Y >> 16;               // arithmetic shifts: floor; compared with h and w as int64
+    const uint32_t fx = (uint32_t)(X >> 8) & 255u, fy = (uint32_t)(Y >> 8) & 255u;
+    const bool x_in0 = xi >= 0 && xi < w, x_in1 = xi >= -1 && xi < (int64_t)w - 1;
+    const bool y_in0 = yi >= 0 && yi < h, y_in1 = yi >= -1 && yi < (int64_t)h - 1;
+    float f[3] = {0.f, 0.f, 0.f};
+    if ((x_in0 || (fx && x_in1)) && (y_in0 || (fy && y_in1))) {
+      uint32_t ta[3] = {0, 0, 0}, tb[3] = {0, 0, 0}, tc[3] = {0, 0, 0}, td[3] = {0, 0, 0};
+      if (x_in0 && x_in1 && y_in0 && y_in1) {               // all four taps inside: two 6-byte reads
+        const uint8_t* src = slide + yi * row_bytes + xi * 3;
+        const Px2 p = *reinterpret_cast<const Px2*>(src), s = *reinterpret_cast<const Px2*>(src + row_bytes);
+        ta[0] = p.lo & 0xFFu; ta[1] = (p.lo >> 8) & 0xFFu; ta[2] = (p.lo >> 16) & 0xFFu;
+        tb[0] = p.lo >> 24; tb[1] = p.hi & 0xFFu; tb[2] = p.hi >> 8;
+        tc[0] = s.lo & 0xFFu; tc[1] = (s.lo >> 8) & 0xFFu; tc[2] = (s.lo >> 16) & 0xFFu;
+        td[0] = s.lo >> 24; td[1] = s.hi & 0xFFu; td[2] = s.hi >> 8;
+      } else {                                              // at the border: every tap checked on its own, 0 outside
+        const uint8_t* src = slide + yi * row_bytes + xi * 3;   // formed, not read, where a tap is outside
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (y_in0 && x_in0) ta[c] = src[c];
+          if (y_in0 && x_in1) tb[c] = src[3 + c];
+          if (y_in1 && x_in0) tc[c] = src[row_bytes + c];
+          if (y_in1 && x_in1) td[c] = src[row_bytes + 3 + c];
+        }
+      }
+      uint32_t v[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint32_t top = ta[c] * (256u - fx) + tb[c] * fx, bot = tc[c] * (256u - fx) + td[c] * fx;
+        v[c] = (top * (256u - fy) + bot * fy + 32768u) >> 16;   // <= 255 * 2^16 + 2^15: fits 32 bits
+      }
+      if constexpr (STAIN) {
+        const int32_t tr = s_od[v[0]], tg = s_od[v[1]], tbl = s_od[v[2]];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int64_t o = (int64_t)A[c][0] * tr + (int64_t)A[c][1] * tg + (int64_t)A[c][2] * tbl + b[c];
+          const int k = (int)std::min<int64_t>(std::max<int64_t>(o >> shift, 0), lut_n - 1);   // arithmetic shift: floor
+          f[c] = div255(s_lut[k]);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[c] = div255(v[c]);
+      }
+    }
+    const int64_t p = p0 + q;
+    if (NCHW) {
+      const int64_t o = (int64_t)t * 3 * plane + p;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) st_elem<BF16>(outv, o + c * plane, f[c]);
+    } else {
+      const int64_t o = ((int64_t)t * plane + p) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) st_elem<BF16>(outv, o + c, f[c]);
+    }
+  }
+}
+
+extern "C" int dh_tile_gather_affine_aug(const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, const int32_t* params_dev,
+                                         const int32_t* params_host_check, const int32_t* affine_dev, const int32_t* affine_host_check,
+                                         int64_t n, int32_t P, int32_t layout, int32_t dtype, int32_t flip_h, int32_t flip_v,
+                                         const int32_t* od_dev, const int32_t* od_host, int32_t shift, const uint8_t* lut_dev,
+                                         int32_t lut_n, void* out, void* stream) {
+  using namespace dh_stain;
+  DH_REQUIRE(n >= 0 && n <= 65535, "tile gather affine aug: n=%lld out of range [0, 65535]", (long long)n);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(slide && yx_dev && affine_dev && out, "tile gather affine aug: null pointer");
+  const int n_stain = (params_dev != nullptr) + (od_dev != nullptr) + (od_host != nullptr) + (lut_dev != nullptr);
+  DH_REQUIRE(n_stain == 0 || n_stain == 4,
+             "tile gather affine aug: partial stain arguments: params_dev, od_dev, od_host and lut_dev must be all given or all null");
+  const bool stain = n_stain == 4;
+  DH_REQUIRE(stain || !params_host_check, "tile gather affine aug: partial stain arguments: params_host_check without params_dev");
+  DH_REQUIRE(h > 0 && w > 0 && h <= INT32_MAX && w <= INT32_MAX, "tile gather affine aug: bad slide size %lld x %lld", (long long)h,
+             (long long)w);
+  DH_REQUIRE(P >= 1 && P <= kAffineMaxPatch, "tile gather affine aug: patch %d outside [1, %d]", P, kAffineMaxPatch);
+  DH_REQUIRE(h >= P && w >= P, "tile gather affine aug: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
+  DH_REQUIRE(layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW, "tile gather affine aug: bad layout %d", layout);
+  DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "tile gather affine aug: bad dtype %d", dtype);
+  if (stain) {
+    DH_REQUIRE(lut_n > 0 && lut_n <= kLutMax, "tile gather affine aug: lut_n = %d, an output table has 1 to %d entries", lut_n, kLutMax);
+    DH_REQUIRE(((uintptr_t)lut_dev & 15) == 0, "tile gather affine aug: lut_dev must be 16-byte aligned");
+    DH_REQUIRE(shift >= 0 && shift < 40, "tile gather affine aug: shift %d outside [0, 40)", shift);
+    for (int i = 0; i < 256; ++i)
+      DH_REQUIRE(od_host[i] >= 0 && od_host[i] <= kOdMax, "tile gather affine aug: od table entry %d = %d outside [0, %d]", i,
+                 od_host[i], kOdMax);
+    if (params_host_check)
+      for (int64_t i = 0; i < 12 * n; ++i) {
+        const int32_t v = params_host_check[i], lim = i % 12 < 9 ? kCoefMax : kBiasMax;
+        DH_REQUIRE(v >= -lim && v <= lim, "tile gather affine aug: params row %lld, %s entry %d = %d outside +-%d", (long long)(i / 12),
+                   i % 12 < 9 ? "matrix" : "bias", (int)(i % 12 < 9 ? i % 12 : i % 12 - 9), v, lim);
+      }
+  }
+  if (affine_host_check)
+    for (int64_t i = 0; i < 4 * n; ++i)
+      DH_REQUIRE(affine_host_check[i] >= -kAffineCoefMax && affine_host_check[i] <= kAffineCoefMax,
+                 "tile gather affine aug: affine row %lld, entry %d = %d outside +-%d", (long long)(i / 4), (int)(i % 4),
+                 affine_host_check[i], kAffineCoefMax);
+  const int64_t blocks = ((int64_t)P * P + kStainPxPerWg - 1) / kStainPxPerWg;
+  hipStream_t st = dh::as_stream(stream);
+  dim3 grid((unsigned)blocks, (unsigned)n), block(256);
+  const int64_t rb = w * 3;
+#define DH_AFFINE_AUG_LAUNCH(BF, NC, ST)                                                                                            \
+  hipLaunchKernelGGL((gather_affine_aug_kernel<BF, NC, ST>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, affine_dev,    \
+                     params_dev, P, flip_h, flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out)
+#define DH_AFFINE_AUG_PICK(ST)                                  \
+  if (layout == DH_LAYOUT_NCHW) {                               \
+    if (dtype == DH_DTYPE_F32) DH_AFFINE_AUG_LAUNCH(false, true, ST);  \
+    else DH_AFFINE_AUG_LAUNCH(true, true, ST);                  \
+  } else {                                                      \
+    if (dtype == DH_DTYPE_F32) DH_AFFINE_AUG_LAUNCH(false, false, ST); \
+    else DH_AFFINE_AUG_LAUNCH(true, false, ST);                 \
+  }
+  if (stain) { DH_AFFINE_AUG_PICK(true) } else { DH_AFFINE_AUG_PICK(false) }
+#undef DH_AFFINE_AUG_PICK
+#undef DH_AFFINE_AUG_LAUNCH
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
 // NHWC float32 WITHOUT the /255 (FullImageRndSampler.generator_torch, full_samplers.py:286, yields the
 // raw 0..255 values as floats -- unlike the dense sampler).
 __global__ __launch_bounds__(256) void gather_raw_nhwc_kernel(const uint8_t* __restrict__ slide, int64_t row_bytes, int h, int w,

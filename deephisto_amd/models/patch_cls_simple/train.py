@@ -9,7 +9,7 @@ holding `model.state_dict()` (train.py:244-249).
 What moved to the GPU: the step itself (forward, CrossEntropy, backward, Adam: HIP kernels,
 `ResNet18HIP.train_step`), batch assembly (gather + /255 + NCHW + batch-level flips in
 `dh_tile_gather_aug`; with `dataset.stain_augment` the training batches also get a per-patch stain jitter,
-`dh_tile_gather_stain_aug`), and the running loss / accuracy sums (accumulated on the device, read
+`dh_tile_gather_stain_aug`, with `dataset.geom_augment` a per-patch rotation and scale, `dh_tile_gather_affine_aug`), and the running loss / accuracy sums (accumulated on the device, read
 once per epoch instead of four host syncs per step, train.py:174-180).
 
 The test set is the reference's: `--extract_test` cuts `test.samples_per_class` JPEG patches per class
@@ -76,6 +76,32 @@ def _stain_aug_from_cfg(cfg, rank: int = 0):
         raise ValueError(f"dataset.stain_augment.{e}") from None
 
 
+def _geom_aug_from_cfg(cfg, rank: int = 0):
+    """The GeometricAugmenter of the optional `dataset.geom_augment: {rotate_deg, scale_min, scale_max, seed}` (absent: None).
+    Every key is optional; an unknown key or a bad value is refused by name.  Data parallel: rank r draws from seed + r."""
+    entry = cfg.get("dataset", {}).get("geom_augment")
+    if entry is None:
+        return None
+    from ...geom_aug import GeometricAugmenter
+    known = ("rotate_deg", "scale_min", "scale_max", "seed")
+    if not isinstance(entry, dict):
+        raise ValueError(f"dataset.geom_augment must be a mapping with the keys {', '.join(known)}, not {entry!r}")
+    unknown = sorted(set(entry) - set(known))
+    if unknown:
+        raise ValueError(f"dataset.geom_augment: unknown key(s) {unknown} (known: {', '.join(known)})")
+    seed = entry.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError(f"dataset.geom_augment.seed must be a non-negative integer, not {seed!r}")
+    lo, hi = entry.get("scale_min", 1.0), entry.get("scale_max", 1.0)
+    try:
+        return GeometricAugmenter(entry.get("rotate_deg", 180.0), (lo, hi), seed + rank)
+    except ValueError as e:
+        msg = str(e).replace("scale[0]", "scale_min").replace("scale[1]", "scale_max")
+        if msg.startswith("scale must"):
+            msg = f"scale_min, scale_max must satisfy 0.5 <= scale_min <= scale_max <= 2.0, not {lo!r}, {hi!r}"
+        raise ValueError(f"dataset.geom_augment.{msg}") from None
+
+
 def _synthetic_sampler(cfg, device):
     from ... import tiles
 
@@ -85,7 +111,7 @@ def _synthetic_sampler(cfg, device):
     return RectRegionRndSampler(slide, regions, layer=cfg["dataset"]["layer"], patch_size=cfg["dataset"]["patch_size"],
                                 patches_from_one_region=cfg["dataset"]["patches_from_one_region"], seed=_rank_world()[0],
                                 device=device, stain=_stain_from_cfg(cfg),   # data parallel: every rank draws its own stream of patches
-                                stain_aug=_stain_aug_from_cfg(cfg, _rank_world()[0]))
+                                stain_aug=_stain_aug_from_cfg(cfg, _rank_world()[0]), geom_aug=_geom_aug_from_cfg(cfg, _rank_world()[0]))
 
 
 def prepare_test_patches(cfg, img_anno_paths=None, device="cuda"):
@@ -216,15 +242,21 @@ def train(cfg, sampler=None, epochs=None, steps_per_epoch=200, log=print, model=
                                            patch_size=cfg["dataset"]["patch_size"], layer=cfg["dataset"]["layer"],
                                            patches_from_one_region=cfg["dataset"]["patches_from_one_region"],
                                            one_image_for_batch=cfg["training"].get("one_image_for_batch", False),
-                                           device=device, stain=_stain_from_cfg(cfg), stain_aug=_stain_aug_from_cfg(cfg, rank))
+                                           device=device, stain=_stain_from_cfg(cfg), stain_aug=_stain_aug_from_cfg(cfg, rank),
+                                           geom_aug=_geom_aug_from_cfg(cfg, rank))
         else:
             sampler = _synthetic_sampler(cfg, device)
 
-    elif _stain_aug_from_cfg(cfg, rank) is not None and getattr(sampler, "stain_aug", False) is None:
-        sampler.stain_aug = _stain_aug_from_cfg(cfg, rank)   # an injected sampler that can jitter and was given no augmenter of its own
-    # stain jitter is for the training batches only: a sampler that has an augmenter is told to leave it
-    # out of the validation batches; samplers without one are called as before
+    else:   # an injected sampler that can augment and was given no augmenter of its own
+        if _stain_aug_from_cfg(cfg, rank) is not None and getattr(sampler, "stain_aug", False) is None:
+            sampler.stain_aug = _stain_aug_from_cfg(cfg, rank)
+        if _geom_aug_from_cfg(cfg, rank) is not None and getattr(sampler, "geom_aug", False) is None:
+            sampler.geom_aug = _geom_aug_from_cfg(cfg, rank)
+    # stain jitter and rotation / scale (section 4.13) are for the training batches only: a sampler that
+    # has an augmenter is told to leave it out of the validation batches; samplers without one are called as before
     no_jitter = {"stain_aug": False} if getattr(sampler, "stain_aug", None) is not None else {}
+    if getattr(sampler, "geom_aug", None) is not None:
+        no_jitter["geom_aug"] = False
 
     bs = cfg["training"]["batch_size"]
     # `model.arch: resnet50` selects the backbone of BASELINE configs[4] (bf16 engine); under torchrun (one process per GPU)

@@ -17,7 +17,11 @@ That OUTPUT CONTRACT is the hot-path boundary.  Two pr
 
 In both, pixels never leave HBM: batches are cut, normalised (k/255), laid out and flipped by
 `dh_tile_gather` / `dh_tile_gather_aug`, or, with a `stain_aug=StainAugmenter(...)`, by `dh_tile_gather_stain_aug`, which also
-jitters every patch's stain concentrations (`device_batches` only).
+jitters every patch's stain concentrations (`device_batches` only).  With a
+`geom_aug=GeometricAugmenter(...)` every patch is cut rotated and rescaled about its own centre by `dh_tile_gather_affine_aug`,
+with or without the stain jitter (`device_batches` only).  The origin and region checks stay those of
+the axis-aligned patch: the rotated window shares its centre and may reach up to s * P * sqrt(2) / 2 from it, past the region,
+or past the slide, where it reads 0.
 """
 from __future__ import annotations
 
@@ -36,13 +40,20 @@ from .._lib import DH_LAYOUT_NCHW, DH_LAYOUT_NHWC
 from ..psimage_compat import Patch, open_slide
 
 
-def _gather_jittered(slide, basis, o_dev, patch, layout, dtype, flip_h, flip_v, alpha, beta, uploader):
+def _gather_jittered(slide, basis, o_dev, patch, layout, dtype, flip_h, flip_v, alpha, beta, uploader, affine=None):
     """One slide's share of a batch: the plain flipped gather when the slide has no stain basis (or no jitter was drawn), else
-    the jitter gather with the parameter rows built from the slide's basis and uploaded through `uploader`."""
-    if basis is None or alpha is None:
+    the jitter gather with the parameter rows built from the slide's basis and uploaded through `uploader`.  `affine`: the
+    int32[n, 4] rows of a GeometricAugmenter (None: none); with them the rotated gather, with or without the stain rows."""
+    params = None
+    if basis is not None and alpha is not None:
+        from ..stain import jitter_params
+        params = jitter_params(basis, alpha, beta)
+    if affine is not None:
+        return tiles.gather_tiles_affine_aug(slide, o_dev, patch, layout, dtype, uploader.upload(affine), flip_h, flip_v,
+                                             affine_host=affine, params_dev=None if params is None else uploader.upload(params),
+                                             params_host=params)
+    if params is None:
         return tiles.gather_tiles_aug(slide, o_dev, patch, layout, dtype, flip_h, flip_v)
-    from ..stain import jitter_params
-    params = jitter_params(basis, alpha, beta)
     return tiles.gather_tiles_stain_aug(slide, o_dev, patch, layout, dtype, uploader.upload(params), flip_h, flip_v, params_host=params)
 
 
@@ -65,7 +76,7 @@ class RectRegionRndSampler:
     def __init__(self, slide, regions: Sequence[RectRegion], layer: int, patch_size: int,
                  region_intersection: float = 0.75, patches_from_one_region: int = 4,
                  region_area_influence: float = 0.5, classes: list[str] | None = None, seed: int = 0, device="cuda",
-                 stain=None, stain_aug=None):
+                 stain=None, stain_aug=None, geom_aug=None):
         if isinstance(slide, np.ndarray):
             slide = torch.from_numpy(np.ascontiguousarray(slide))
         if slide.dtype != torch.uint8 or slide.dim() != 3 or slide.shape[2] != 3:
@@ -76,6 +87,7 @@ class RectRegionRndSampler:
             self.slide = stain.normalize(self.slide, info)
         self.stain_aug = stain_aug   # a StainAugmenter: device_batches jitters every patch's stains
         self._stain, self._stain_fit, self._basis = stain, info.get("fit"), False   # the basis is fitted at the first jittered batch
+        self.geom_aug = geom_aug     # a GeometricAugmenter: device_batches rotates and rescales every patch
         self.h, self.w = int(slide.shape[0]), int(slide.shape[1])
         self.layer, self.patch_size = layer, int(patch_size)
         self.region_intersection = float(region_intersection)
@@ -145,13 +157,15 @@ class RectRegionRndSampler:
                 features = transforms(features)
             yield features, torch.from_numpy(lab).to(dev), tiles.tile_coords(o_dev)
 
-    def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32, stain_aug: bool = True
-                       ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+    def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32, stain_aug: bool = True,
+                       geom_aug: bool = True) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """Fast path of the training loop: [B,3,P,P] batches with train.py:71-81's
         permute + batch-level random flips fused into the gather kernel; with a `stain_aug` augmenter (and `stain_aug=True`)
-        every patch's stains are jittered in the same kernel."""
+        every patch's stains are jittered in the same kernel; with a `geom_aug` augmenter (and `geom_aug=True`) every patch is
+        cut rotated and rescaled about its centre (origins, labels and coordinates stay the axis-aligned patch's)."""
         dev = self.slide.device
         aug = self.stain_aug if stain_aug else None
+        geo = self.geom_aug if geom_aug else None
         if aug is not None and self._basis is False:
             from ..stain import stain_basis
             self._basis = stain_basis(self.slide, self._stain, self._stain_fit)
@@ -165,7 +179,7 @@ class RectRegionRndSampler:
             o_dev, lab_dev, coords = up.upload_batch(yx, lab)   # one staged copy per batch (origins, labels, float coordinates)
             alpha, beta = aug.draw(batch_size) if aug is not None else (None, None)
             x = _gather_jittered(self.slide, self._basis if aug is not None else None, o_dev, self.patch_size, DH_LAYOUT_NCHW, dtype,
-                                 fh, fv, alpha, beta, up)
+                                 fh, fv, alpha, beta, up, geo.rows(batch_size) if geo is not None else None)
             yield x, lab_dev, coords
 
 
@@ -307,7 +321,7 @@ def _parse_annotations(img_anno_paths, layer: int, classes: list[str] | None = N
 class _SlideBank:
     """The images of a sampler: PSImage-like host readers + their layers resident in HBM (uploaded on first use)."""
 
-    def __init__(self, sources, layer: int, device, stain=None, stain_aug=None):
+    def __init__(self, sources, layer: int, device, stain=None, stain_aug=None, geom_aug=None):
         self._readers = [open_slide(s) if not isinstance(s, torch.Tensor) else None for s in sources]
         self._dev = [s.to(device).contiguous() if isinstance(s, torch.Tensor) else None for s in sources]
         self.layer, self.device = layer, torch.device(device)
@@ -319,6 +333,7 @@ class _SlideBank:
         # the normaliser's target when the slide was just mapped onto it, else one default Macenko fit; None: an identity fit
         # (all glass, degenerate plane), that slide's patches are gathered un-jittered
         self.stain_aug = stain_aug
+        self.geom_aug = geom_aug   # a GeometricAugmenter; needs nothing per slide
         self._fit = [None] * len(sources)
         self._basis = [False] * len(sources)
 
@@ -375,7 +390,7 @@ class AnnoRegionRndSampler:
 
     def __init__(self, img_anno_paths, layer: int, patch_size: int, region_intersection: float = 0.75,
                  patches_from_one_region: int = 4, region_area_influence: float = 0.5, classes: list[str] = None,
-                 one_image_for_batch: bool = False, device="cuda", stain=None, stain_aug=None):
+                 one_image_for_batch: bool = False, device="cuda", stain=None, stain_aug=None, geom_aug=None):
         self.img_anno_paths = img_anno_paths
         self.layer = layer
         self.patch_size = patch_size
@@ -389,7 +404,7 @@ class AnnoRegionRndSampler:
             raise ValueError("no usable annotated regions")
         self._reg_w_all, self._reg_w_per_img, self._img_w, self._img_w_all = self._calc_weights(
             self.regions, self.regions_per_image)
-        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug)
+        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug, geom_aug)
 
     @property
     def stain_aug(self):
@@ -399,6 +414,15 @@ class AnnoRegionRndSampler:
     @stain_aug.setter
     def stain_aug(self, aug):
         self._bank.stain_aug = aug
+
+    @property
+    def geom_aug(self):
+        """The GeometricAugmenter of `device_batches` (None: no rotation or scale); DESIGN.md section 4.13."""
+        return self._bank.geom_aug
+
+    @geom_aug.setter
+    def geom_aug(self, aug):
+        self._bank.geom_aug = aug
 
     # ---- weights (region_samplers.py:339-482) ------------------------------------------------------------
     def _calc_area_weights(self, areas, area_influence: float):
@@ -484,10 +508,10 @@ class AnnoRegionRndSampler:
                 yield lst[k:k + batch_size]
 
     # ---- device batches --------------------------------------------------------------------------------
-    def _assemble(self, recs, layout: int, dtype, flip_h: bool = False, flip_v: bool = False, aug=None):
+    def _assemble(self, recs, layout: int, dtype, flip_h: bool = False, flip_v: bool = False, aug=None, geo=None):
         """Cut the records' patches from the HBM-resident slides into one batch tensor (+ labels, coords).  `aug`: a
         StainAugmenter; one (alpha, beta) row per record, drawn in record order before the batch is split by slide, so the draw
-        does not depend on how the records group."""
+        does not depend on how the records group.  `geo`: a GeometricAugmenter; its rows are drawn the same way."""
         dev, ps = self._bank.device, self.patch_size
         arr = np.array(recs, dtype=np.int64).reshape(-1, 4)
         out = None
@@ -495,16 +519,18 @@ class AnnoRegionRndSampler:
         if up is None:
             up = self._uploader = tiles.PinnedUploader(dev, depth=8)   # non-blocking uploads (tiles.PinnedUploader)
         alpha, beta = aug.draw(len(arr)) if aug is not None else (None, None)
+        affine = geo.rows(len(arr)) if geo is not None else None
         if (arr[:, 0] == arr[0, 0]).all():   # the whole batch from one slide (always so with one_image_for_batch): one staged copy
             o_dev, labels, coords = up.upload_batch(arr[:, 1:3].astype(np.int32), arr[:, 3].copy())
             j = int(arr[0, 0])
             return _gather_jittered(self._bank.slide(j), self._bank.basis(j) if aug is not None else None, o_dev, ps, layout, dtype,
-                                    flip_h, flip_v, alpha, beta, up), labels, coords
+                                    flip_h, flip_v, alpha, beta, up, affine), labels, coords
         for j in np.unique(arr[:, 0]):
             sel = np.nonzero(arr[:, 0] == j)[0]
             o_dev = up.upload(arr[sel, 1:3].astype(np.int32))
             part = _gather_jittered(self._bank.slide(int(j)), self._bank.basis(int(j)) if aug is not None else None, o_dev, ps, layout,
-                                    dtype, flip_h, flip_v, None if aug is None else alpha[sel], None if aug is None else beta[sel], up)
+                                    dtype, flip_h, flip_v, None if aug is None else alpha[sel], None if aug is None else beta[sel], up,
+                                    None if geo is None else affine[sel])
             if len(sel) == len(arr):
                 out = part
             else:
@@ -531,19 +557,22 @@ class AnnoRegionRndSampler:
                 yield features, labels, coords
 
     def device_batches(self, batch_size: int, n_batches: int, flips: bool = True, dtype=torch.float32,
-                       batches_per_worker: int = 2, stain_aug: bool = True
+                       batches_per_worker: int = 2, stain_aug: bool = True, geom_aug: bool = True
                        ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """Training fast path: [B,3,P,P] batches with train.py:69-81's permute + RandomHorizontalFlip +
         RandomVerticalFlip (one torch coin each per batch, in that order) fused into the gather kernel.  With a `stain_aug`
         augmenter (and `stain_aug=True`) every patch's stains are jittered in the same kernel; the augmenter draws from its own
-        stream, so records and coins are what they are without it."""
+        stream, so records and coins are what they are without it.  With a `geom_aug` augmenter (and `geom_aug=True`) every
+        patch is cut rotated and rescaled about its centre, from a third private stream; the records' origin and region checks
+        stay those of the axis-aligned patch."""
         aug = self._bank.stain_aug if stain_aug else None
+        geo = self._bank.geom_aug if geom_aug else None
         for i in self._split_chunks(n_batches, batches_per_worker):
             recs = self._records(batch_size * i)
             for k in range(0, len(recs), batch_size):
                 fh = bool(flips and torch.rand(1).item() < 0.5)
                 fv = bool(flips and torch.rand(1).item() < 0.5)
-                yield self._assemble(recs[k:k + batch_size], DH_LAYOUT_NCHW, dtype, fh, fv, aug)
+                yield self._assemble(recs[k:k + batch_size], DH_LAYOUT_NCHW, dtype, fh, fv, aug, geo)
 
 
     def torch_iterable_dataset(self):
@@ -570,7 +599,7 @@ class AnnoRegionDenseSampler:
     """Every grid patch of every annotated region, class by class (region_samplers.py:799-871)."""
 
     def __init__(self, img_anno_paths, layer: int, patch_size: int, stride: int, region_intersection: float = 0.75,
-                 classes: list[str] = None, device="cuda", stain=None, stain_aug=None):
+                 classes: list[str] = None, device="cuda", stain=None, stain_aug=None, geom_aug=None):
         self.img_anno_paths = img_anno_paths
         self.layer = layer
         self.patch_size = patch_size
@@ -578,7 +607,7 @@ class AnnoRegionDenseSampler:
         self.region_intersection = region_intersection
         self.regions, _ = _parse_annotations(img_anno_paths, layer=layer, classes=classes)
         self.classes = sorted(list(self.regions.keys()))
-        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug)
+        self._bank = _SlideBank([p[0] for p in img_anno_paths], layer, device, stain, stain_aug, geom_aug)
 
     @property
     def stain_aug(self):
@@ -588,6 +617,15 @@ class AnnoRegionDenseSampler:
     @stain_aug.setter
     def stain_aug(self, aug):
         self._bank.stain_aug = aug
+
+    @property
+    def geom_aug(self):
+        """The GeometricAugmenter of `device_batches` (None: no rotation or scale); DESIGN.md section 4.13."""
+        return self._bank.geom_aug
+
+    @geom_aug.setter
+    def geom_aug(self, aug):
+        self._bank.geom_aug = aug
 
     def _patches_one_region(self, region: RegionAnnotation) -> list[Patch]:
         ps = self.patch_size
@@ -602,12 +640,14 @@ class AnnoRegionDenseSampler:
                 for p in self._patches_one_region(region):
                     yield p, cls_idx
 
-    def device_batches(self, batch_size: int, layout: int = DH_LAYOUT_NCHW, dtype=torch.float32, stain_aug: bool = True
-                       ) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+    def device_batches(self, batch_size: int, layout: int = DH_LAYOUT_NCHW, dtype=torch.float32, stain_aug: bool = True,
+                       geom_aug: bool = True) -> Iterator[tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """The same patches in the same order as device tensors (tiles cut on the GPU), `batch_size` at a time; with a
-        `stain_aug` augmenter (and `stain_aug=True`) every patch's stains are jittered, one draw per batch."""
+        `stain_aug` augmenter (and `stain_aug=True`) every patch's stains are jittered, one draw per batch; with a `geom_aug`
+        augmenter (and `geom_aug=True`) every patch is cut rotated and rescaled about its centre, one draw per batch."""
         dev, ps = self._bank.device, self.patch_size
         aug = self._bank.stain_aug if stain_aug else None
+        geo = self._bank.geom_aug if geom_aug else None
         up = None
         for cls_idx, cls in enumerate(self.classes):
             for region in self.regions[cls]:
@@ -619,13 +659,13 @@ class AnnoRegionDenseSampler:
                     # bounds-safe gather (zero outside the image): dense origins of a region that touches or leaves
                     # the image border can be negative or hang over it (region_samplers.py:160-166)
                     j = region.image_index
-                    if aug is None:
+                    if aug is None and geo is None:
                         x = tiles.gather_tiles_aug(self._bank.slide(j), o_dev, ps, layout, dtype)
                     else:
                         up = up or tiles.PinnedUploader(dev)
-                        alpha, beta = aug.draw(len(o))
-                        x = _gather_jittered(self._bank.slide(j), self._bank.basis(j), o_dev, ps, layout, dtype, False, False,
-                                             alpha, beta, up)
+                        alpha, beta = aug.draw(len(o)) if aug is not None else (None, None)
+                        x = _gather_jittered(self._bank.slide(j), self._bank.basis(j) if aug is not None else None, o_dev, ps, layout,
+                                             dtype, False, False, alpha, beta, up, geo.rows(len(o)) if geo is not None else None)
                     yield x, torch.full((len(o),), cls_idx, dtype=torch.int64, device=dev), tiles.tile_coords(o_dev)
 
 

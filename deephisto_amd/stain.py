@@ -19,6 +19,8 @@ from fractions import Fraction
 
 import numpy as np
 
+from .geom_aug import overflow_bounds as _affine_overflow_bounds
+
 # ---- fixed-point widths and bin counts -------------------------------------------------------------
 OD_BITS = 12                    # optical density: T[v] = round(-ln((v + 1) / 256) * 2^12), 0 .. 22713
 OD_MAX = 22713                  # T[0] = round(ln(256) * 4096)
@@ -92,6 +94,8 @@ def overflow_bounds(npix: int = MAX_PIXELS) -> dict:
         "histogram_bin": (npix, 2 ** 64),
         # an LDS copy is shared by at most one workgroup of a grid of 2 048 (or every lane has one group of 16 pixels)
         "lds_bin": (npix // 2048 + 16 * 256 + 16, 2 ** 32),
+        # the rotated and rescaled gather in front of the jitter (section 4.13): coordinates and the bilinear blend
+        **{f"affine_{k}": v for k, v in _affine_overflow_bounds().items()},
     }
 
 

@@ -123,6 +123,53 @@ def gather_tiles_stain_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch
     return out
 
 
+def gather_tiles_affine_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, layout: int, dtype, affine_dev: torch.Tensor,
+                            flip_h: bool = False, flip_v: bool = False, affine_host=None, params_dev: torch.Tensor | None = None,
+                            params_host=None) -> torch.Tensor:
+    """gather_tiles_aug with a per-tile rotation and scale about the patch centre fused in, and with `params_dev` the stain
+    jitter of gather_tiles_stain_aug as well (dh_tile_gather_affine_aug).  `affine_dev`: int32[n, 4] on
+    the device, the rows of geom_aug.affine_params; `affine_host` / `params_host`: the same rows on the host, checked by the
+    entry before the launch (None: not checked).  The rotated window shares the patch's centre and reaches up to
+    s * P * sqrt(2) / 2 from it; where it leaves the slide it reads 0."""
+    _require_cuda(slide, "slide")
+    _require_cuda(origins_dev, "origins")
+    _require_cuda(affine_dev, "affine")
+    n = int(origins_dev.shape[0])
+
+    def rows(dev_t, host, k, what):
+        if dev_t.dtype != torch.int32 or tuple(dev_t.shape) != (n, k):
+            raise ValueError(f"{what} must be int32[{n}, {k}], not {str(dev_t.dtype).replace('torch.', '')}{list(dev_t.shape)}")
+        if host is None:
+            return None
+        host = np.ascontiguousarray(host, dtype=np.int32)
+        if host.shape != (n, k):
+            raise ValueError(f"{what}_host must be int32[{n}, {k}], not {list(host.shape)}")
+        return host
+
+    a_host = rows(affine_dev, affine_host, 4, "affine")
+    p_host = None
+    if params_dev is not None:
+        _require_cuda(params_dev, "params")
+        p_host = rows(params_dev, params_host, 12, "params")
+    elif params_host is not None:
+        raise ValueError("params_host without params_dev")
+    code = dtype_code(dtype)
+    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
+    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+    if params_dev is not None:
+        from . import stain as S
+        od_dev, _, lut, od = S._tables(slide.device)
+        stain_args = (od_dev.data_ptr(), ptr(od), S.APPLY_SHIFT, lut.data_ptr(), S.LUT_SIZE)
+    else:
+        stain_args = (None, None, 0, None, 0)
+    check(lib().dh_tile_gather_affine_aug(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(),
+                                          params_dev.data_ptr() if params_dev is not None else None, ptr(p_host),
+                                          affine_dev.data_ptr(), ptr(a_host), n, patch, layout, code, int(flip_h), int(flip_v),
+                                          *stain_args, out.data_ptr(), _stream(slide.device)), "dh_tile_gather_affine_aug")
+    return out
+
+
 class PinnedUploader:
     """Host -> device copies of small per-batch arrays (tile origins, labels) that do not stall the host.
 

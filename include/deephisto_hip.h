@@ -99,6 +99,26 @@ int dh_tile_gather_stain_aug(const uint8_t* slide_dev, int64_t h, int64_t w, con
                              const int32_t* od_host, int32_t shift, const uint8_t* lut_dev, int32_t lut_n,
                              void* out_dev, void* stream);
 
+/* dh_tile_gather_aug with a per-tile rotation and scale about the patch centre fused in, and optionally the
+ * stain jitter above (no counterpart in the reference).  affine_dev: int32[n][4], per
+ * tile m = round(2^15 s [[cos, -sin], [sin, cos]]) row-major, s = source pixels per output pixel (|.| <= 2^16);
+ * affine_host_check: the same values on the host, every one checked before the launch, or NULL.  With (sr, sx)
+ * the flipped row and column of an output pixel, U2 = 2 sx + 1 - patch, V2 = 2 sr + 1 - patch, the source
+ * point in Q16 is X = ((2 x0 + patch) << 15) - 2^15 + m00 U2 + m01 V2, Y likewise from y0, m10, m11 (64-bit);
+ * taps (X >> 16, Y >> 16) and its three neighbours, weights fx = (X >> 8) & 255, fy likewise, a tap outside
+ * the slide reads as 0; per channel v = ((a (256 - fx) + b fx)(256 - fy) + (c (256 - fx) + d fx) fy + 2^15) >> 16.
+ * v then goes where the slide byte goes in the entries above: float32(v) / 255, or, with the stain arguments,
+ * through od, matrix, bias and lut first.  params_dev, od_dev, od_host and lut_dev are all given or all NULL
+ * (NULL: no stain jitter; params_host_check, shift and lut_n are then unused).  A pixel none of whose taps of
+ * non-zero weight lies inside the slide is written as 0 and is not transformed.  patch in [1, 4096].  The
+ * identity row (32768, 0, 0, 32768) gives the bits of dh_tile_gather_aug / dh_tile_gather_stain_aug. */
+int dh_tile_gather_affine_aug(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                              const int32_t* params_dev, const int32_t* params_host_check, const int32_t* affine_dev,
+                              const int32_t* affine_host_check, int64_t n, int32_t patch, int32_t layout,
+                              int32_t dtype, int32_t flip_h, int32_t flip_v, const int32_t* od_dev,
+                              const int32_t* od_host, int32_t shift, const uint8_t* lut_dev, int32_t lut_n,
+                              void* out_dev, void* stream);
+
 /* FullImageRndSampler.generator_torch (full_samplers.py:277-290) stacks the uint8 patches into a
  * float tensor WITHOUT dividing by 255: float32[n][P][P][3] with values 0..255 (0 outside the slide). */
 int dh_tile_gather_raw(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
