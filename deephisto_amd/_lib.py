@@ -122,6 +122,7 @@ DEBUG_SIGNATURES = {
     "dh_debug_maxpool2_bf16": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "dh_debug_upsample2_add_bf16": (C.c_int, [_p, _p] + [_i32] * 6 + [_p]),
     "dh_debug_avgpool_fc_dgrad2": (C.c_int, [_p, _p, _p] + [_i32] * 4 + [_p]),
+    "dh_debug_head": (C.c_int, [_p, _i32] + [_p] * 8 + [_i32] * 4 + [_p]),
     "dh_debug_wgrad_bf16": (C.c_int, [_p, _p, _p] + [_i32] * 8 + [_p]),
     "dh_debug_conv_bf16": (C.c_int, [_p, _p, _p, _p] + [_i32] * 8 + [_p]),
     "dh_debug_conv_bn_act":(C.c_int, [_p, _p, _p, _p, _p, _p] + [_i32] * 9 + [_p]),

@@ -795,16 +795,20 @@ extern "C" int dh_train2_bucket(dh_train2* t, int32_t i, int64_t* offset, int64_
 // bf16 wire format for gradient buckets (both engines' arenas: offsets and counts are multiples of 4 elements, 16-byte aligned):
 // pack = float32 -> bf16 (RNE) before the all-reduce, unpack = bf16 sum -> float32 * scale (1 / world) after it.
 extern "C" int dh_grad_pack_bf16(const float* src_dev, uint16_t* dst_dev, int64_t n, void* stream) {
-  DH_REQUIRE(src_dev && dst_dev && n >= 0 && n % 4 == 0 && (reinterpret_cast<uintptr_t>(src_dev) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(dst_dev) & 7) == 0, "grad pack: need 4-element granules on aligned pointers");
+  DH_REQUIRE(src_dev && dst_dev, "grad pack: null src_dev or dst_dev");
+  DH_REQUIRE(n >= 0 && n % 4 == 0, "grad pack: n=%lld is not a whole number of 4-element granules", (long long)n);
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(src_dev) & 15) == 0, "grad pack: src_dev is not 16-byte aligned");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(dst_dev) & 7) == 0, "grad pack: dst_dev is not 8-byte aligned");
   if (n == 0) return DH_OK;
   hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, dh::as_stream(stream), src_dev, dst_dev, n / 4);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 extern "C" int dh_grad_unpack_bf16(const uint16_t* src_dev, float* dst_dev, int64_t n, float scale, void* stream) {
-  DH_REQUIRE(src_dev && dst_dev && n >= 0 && n % 4 == 0 && (reinterpret_cast<uintptr_t>(dst_dev) & 15) == 0 &&
-             (reinterpret_cast<uintptr_t>(src_dev) & 7) == 0, "grad unpack: need 4-element granules on aligned pointers");
+  DH_REQUIRE(src_dev && dst_dev, "grad unpack: null src_dev or dst_dev");
+  DH_REQUIRE(n >= 0 && n % 4 == 0, "grad unpack: n=%lld is not a whole number of 4-element granules", (long long)n);
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(src_dev) & 7) == 0, "grad unpack: src_dev is not 8-byte aligned");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(dst_dev) & 15) == 0, "grad unpack: dst_dev is not 16-byte aligned");
   if (n == 0) return DH_OK;
   hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(grid_for(n / 4)), dim3(256), 0, dh::as_stream(stream), src_dev, dst_dev, n / 4, scale);
   DH_LAUNCH_CHECK();
@@ -1336,6 +1340,30 @@ extern "C" int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float*
   hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, dx_dev);
   DH_LAUNCH_CHECK();
   return dbg_finish(st, "debug avgpool fc");
+}
+// The classifier head of both engines on caller data, in the order a step launches it: global average pool (x_bf16 = 0: avgpool_kernel on
+// float32 x, the float32 engine; 1: avgpool2_kernel on bf16 x, the bf16 engine), fc_fwd_kernel, fc_wgrad_kernel on the caller's dlogits and
+// the pooled features just made, and the matching avgpool_fc_dgrad kernel (float32 / bf16 dx).  x, dx [B][HW][C]; w [n_cls][C]; bias [n_cls];
+// dlogits, logits [B][n_cls]; pooled [B][C]; dw [n_cls][C]; db [n_cls].
+extern "C" int dh_debug_head(const void* x_dev, int32_t x_bf16, const float* w_dev, const float* bias_dev, const float* dlogits_dev,
+                             float* pooled_dev, float* logits_dev, float* dw_dev, float* db_dev, void* dx_dev, int32_t B, int32_t HW,
+                             int32_t C, int32_t n_cls, void* stream) {
+  DH_REQUIRE(x_dev && w_dev && bias_dev && dlogits_dev, "debug head: null input (x_dev, w_dev, bias_dev or dlogits_dev)");
+  DH_REQUIRE(pooled_dev && logits_dev && dw_dev && db_dev && dx_dev, "debug head: null output (pooled_dev, logits_dev, dw_dev, db_dev or dx_dev)");
+  DH_REQUIRE(x_bf16 == 0 || x_bf16 == 1, "debug head: x_bf16=%d (0 float32, 1 bf16)", x_bf16);
+  DH_REQUIRE(B > 0 && B <= 65535, "debug head: B=%d", B);
+  DH_REQUIRE(HW > 0, "debug head: HW=%d", HW);
+  DH_REQUIRE(C > 0 && C % 8 == 0, "debug head: C=%d (a positive multiple of 8)", C);
+  DH_REQUIRE(n_cls > 0 && n_cls <= 1024, "debug head: n_cls=%d", n_cls);
+  hipStream_t st = dh::as_stream(stream);
+  if (x_bf16) hipLaunchKernelGGL(avgpool2_kernel, dim3(B), dim3(256), 0, st, static_cast<const bf16_t*>(x_dev), HW, C, pooled_dev);
+  else hipLaunchKernelGGL(avgpool_kernel, dim3(B), dim3(256), 0, st, static_cast<const float*>(x_dev), HW, C, pooled_dev);
+  hipLaunchKernelGGL(fc_fwd_kernel, dim3((B * n_cls + 3) / 4), dim3(256), 0, st, pooled_dev, w_dev, bias_dev, B, C, n_cls, logits_dev);
+  hipLaunchKernelGGL(fc_wgrad_kernel, dim3((n_cls * C + 255) / 256), dim3(256), 0, st, dlogits_dev, pooled_dev, B, C, n_cls, dw_dev, db_dev);
+  if (x_bf16) hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, static_cast<bf16_t*>(dx_dev));
+  else hipLaunchKernelGGL(avgpool_fc_dgrad_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, static_cast<float*>(dx_dev));
+  DH_LAUNCH_CHECK();
+  return dbg_finish(st, "debug head");
 }
 
 // One convolution of the bf16 engine on caller data, forward or data gradient, through the step's own launch code: the operands are

@@ -820,10 +820,18 @@ __global__ __launch_bounds__(SWG_T, 4) void stem_wgrad_bf16_kernel(const bf16_t*
 
 // gradient wire format of the data-parallel exchange (optional): float32 arena slice -> bf16 (round to nearest even) and back with the
 // 1 / world factor; 4 elements per thread (arena offsets and counts are multiples of 4)
+// A NaN gradient must reach every rank as a NaN: the rounding add of f32_to_bf16 carries out of a NaN's mantissa (0x7F80xxxx with a small
+// payload came out as infinity, 0x7FFF8000 and above as a signed zero), so NaNs are truncated and made quiet here.  Finite values and
+// infinities round as everywhere else (to nearest even; past the largest bf16 to infinity).
+__device__ __forceinline__ uint32_t f32_to_bf16_wire(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x7FFFFFFFu) > 0x7F800000u ? ((u >> 16) | 0x0040u) : f32_to_bf16(f);
+}
 __global__ __launch_bounds__(256) void grad_pack_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int64_t n4) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4*>(src)[i];
-    reinterpret_cast<uint2*>(dst)[i] = make_uint2(f32_to_bf16(v.x) | (f32_to_bf16(v.y) << 16), f32_to_bf16(v.z) | (f32_to_bf16(v.w) << 16));
+    reinterpret_cast<uint2*>(dst)[i] = make_uint2(f32_to_bf16_wire(v.x) | (f32_to_bf16_wire(v.y) << 16),
+                                                  f32_to_bf16_wire(v.z) | (f32_to_bf16_wire(v.w) << 16));
   }
 }
 __global__ __launch_bounds__(256) void grad_unpack_bf16_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, int64_t n4, float scale) {

@@ -370,7 +370,9 @@ int dh_train2_flat(dh_train2* net, int32_t kind, void** ptr_out, int64_t* n_out)
 int dh_train2_set_buckets(dh_train2* net, int64_t bucket_bytes, dh_bucket_cb cb, void* user, int32_t* n_buckets_out);
 int dh_train2_bucket(dh_train2* net, int32_t i, int64_t* offset, int64_t* count);
 /* optional bf16 wire format of the gradient exchange (either engine's arena; n % 4 == 0): float32 -> bf16 (round to nearest even)
- * before a bucket's all-reduce, bf16 sums -> float32 * scale (1 / world) after it.  Halves the bytes on xGMI. */
+ * before a bucket's all-reduce, bf16 sums -> float32 * scale (1 / world) after it.  Halves the bytes on xGMI.  A finite value past the
+ * largest bf16 packs to infinity, infinities are kept, and every NaN stays a (quiet) NaN.  Refused with DH_EINVAL, dh_last_error
+ * naming the argument: n not a multiple of 4, a float32 pointer not 16-byte aligned, a bf16 pointer not 8-byte aligned. */
 int dh_grad_pack_bf16(const float* src_dev, uint16_t* dst_dev, int64_t n, void* stream);
 int dh_grad_unpack_bf16(const uint16_t* src_dev, float* dst_dev, int64_t n, float scale, void* stream);
 int dh_train2_forward(dh_train2* net, const float* x_dev, int64_t n, int32_t patch, float* logits_dev,

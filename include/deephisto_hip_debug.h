@@ -59,6 +59,15 @@ int dh_debug_upsample2_add_bf16(const uint16_t* t_dev, uint16_t* dx_dev, int32_t
 int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float* w_dev, uint16_t* dx_dev, int32_t B, int32_t HW, int32_t C,
                                int32_t n_cls, void* stream);
 int dh_debug_stem_wgrad_bf16(const uint16_t* dz_dev, const float* x_nchw_dev, float* dw_dev, int32_t B, int32_t P, void* stream);
+/* dh_debug_head: the classifier head of both training engines on caller data, in the order a step launches it: global average pool
+ * (x_bf16 = 0: the float32 engine's kernel on float32 x; 1: the bf16 engine's on bf16 bits), fc forward, fc weight / bias gradient from
+ * the caller's dlogits and the pooled features just made, and the matching average-pool + fc data gradient (dx float32 / bf16 bits).
+ * x, dx [B][HW][C]; w [n_cls][C]; bias [n_cls]; dlogits, logits [B][n_cls]; pooled [B][C]; dw [n_cls][C]; db [n_cls].  Every output is
+ * written in full.  Refused (DH_EINVAL, dh_last_error names the argument): a null pointer, x_bf16 outside {0, 1}, B, HW or n_cls < 1,
+ * C not a positive multiple of 8.  Synchronises. */
+int dh_debug_head(const void* x_dev, int32_t x_bf16, const float* w_dev, const float* bias_dev, const float* dlogits_dev,
+                  float* pooled_dev, float* logits_dev, float* dw_dev, float* db_dev, void* dx_dev, int32_t B, int32_t HW, int32_t C,
+                  int32_t n_cls, void* stream);
 int dh_debug_wgrad_bf16(const uint16_t* dz_dev, const uint16_t* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi,
                         int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t repeat, void* stream);
 /* dh_debug_conv_bf16: ONE convolution of the bf16 training engine on caller data (bf16 bits, NHWC), forward or data gradient, exactly as a
