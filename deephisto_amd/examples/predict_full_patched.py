@@ -241,6 +241,17 @@ def _stain_from_args(ap, args) -> StainNormalizer | None:
     return StainNormalizer(args.stain)
 
 
+def _pyramid_from_args(ap, args) -> None:
+    """Checks --pyramid; a bad combination is an argparse error."""
+    if not args.pyramid:
+        return
+    if args.ondisk:
+        ap.error("--pyramid holds the layer resident in HBM; it cannot be combined with --ondisk")
+    if args.synthetic is None and Path(args.image).suffix != ".npy":
+        ap.error(f"--pyramid serves the layers of a --synthetic slide or a .npy image; {args.image} goes to psimage, "
+                 "which has layers of its own")
+
+
 def _proba_from_args(ap, args) -> None:
     """Checks the --proba flags; a bad combination or an unknown class label is an argparse error."""
     if args.heat and not args.proba:
@@ -286,8 +297,12 @@ def _build_parser():
     ap.add_argument("--tissue_min_fraction", type=float, default=0.25,
                     help="share of a tile's pixels that must be tissue (0.25: a conventional default, not validated here)")
     ap.add_argument("--tissue_fill", default="-1", help="class label for cells no kept tile covers, or -1 (no class)")
+    ap.add_argument("--pyramid", action="store_true",
+                    help="--layer L of a --synthetic slide or a .npy image is the slide at 1/L of its resolution, area-averaged on the "
+                         "device (PyramidSlide); without it such a slide has one layer, whatever --layer says")
     ap.add_argument("--stain", choices=["off", "macenko"], default="off",
-                    help="normalise the slide's stain appearance on the device before anything reads it (resident slide)")
+                    help="normalise the slide's stain appearance on the device before anything reads it (resident slide); "
+                         "with --pyramid the layer is normalised, not the base")
     ap.add_argument("--stain_target", default=None, metavar="PATH", help="with --stain: a StainFit JSON (another slide's fit) as the target")
     ap.add_argument("--save_stain_fit", default=None, metavar="PATH", help="with --stain: this slide's StainFit as JSON (rank 0)")
     ap.add_argument("--proba", action="store_true", help="per-cell mean softmax probabilities; writes {stem}_confidence.jpg")
@@ -311,6 +326,7 @@ def _check_args(ap, args) -> None:
     `args.tissue_filter`, the StainNormalizer (or None) in `args.stain_norm` and the records of --anno (or None) in
     `args.anno_records`."""
     _regions_from_args(ap, args)
+    _pyramid_from_args(ap, args)
     args.stain_norm = _stain_from_args(ap, args)
     args.tissue_filter = _tissue_from_args(ap, args)
     args.anno_records = _anno_from_args(ap, args)
@@ -331,6 +347,11 @@ def _run(args, model, device, rank, world):
     else:
         img, stem = Path(args.image), Path(args.image).stem
     mode = SamplerExecutionMode.ONDISK_MULTIPROC if args.ondisk else SamplerExecutionMode.INMEMORY_SINGLEPROC
+    if args.pyramid:
+        # the layer takes the slide's place for every route below and for the overlays; --stain then
+        # normalises the layer.  A .npy image goes up in bands, so HBM holds the layer and one band, never the whole scan
+        from ..resample import PyramidSlide
+        img = PyramidSlide(img, device=device).layer_device(args.layer)
     if args.stain_norm is not None:
         # the normalised slide takes the raw one's place for every route below and for the overlays (the map and the picture
         # under it must agree); every rank normalises its own copy, integer-exact, so all hold the same pixels
@@ -441,6 +462,8 @@ def main(argv=None, model=None):
     `{stem}_clean_mask.jpg` and `{stem}_clean_overlay.jpg`; `--export_anno PATH` writes the regions as polygons in the
     annotation's JSON format.  The returned map and the three standard JPEGs are those of a run without these flags, and
     `--anno` keeps scoring the uncleaned map (the cleaned one gets a second score).
+    `--pyramid` makes `--layer L` of a `--synthetic` slide or a `.npy` image the slide at 1/L of its resolution (DESIGN.md section
+    4.14): the exact area average, built on the device; everything below reads that layer, and `--stain` normalises it.
     `--stain macenko` normalises the slide's stain appearance first (resident slide): the prediction, the
     tissue filter and the overlays all read the normalised slide; `--stain_target PATH` takes another slide's saved fit as the
     target instead of the default constants, `--save_stain_fit PATH` writes this slide's fit (rank 0).

@@ -102,6 +102,30 @@ def _geom_aug_from_cfg(cfg, rank: int = 0):
         raise ValueError(f"dataset.geom_augment.{msg}") from None
 
 
+def _pyramid_from_cfg(cfg) -> bool:
+    """The optional `dataset.pyramid` (absent: False): the `.npy` / array slides of the region samplers are read through a
+    `resample.PyramidSlide`, so `dataset.layer` is the slide at 1 / layer of its resolution for the training, validation and
+    `--extract_test` patches alike.  Anything but true / false is refused by name."""
+    value = cfg.get("dataset", {}).get("pyramid", False)
+    if not isinstance(value, bool):
+        raise ValueError(f"dataset.pyramid must be true or false, not {value!r}")
+    return value
+
+
+def _dataset_paths(cfg, sample: str):
+    """The (image, annotation) pairs of `dataset.folder`; with `dataset.pyramid` its `.npy` slides count as images too."""
+    suffixes = (".psi", ".npy") if _pyramid_from_cfg(cfg) else (".psi",)
+    return utils.get_img_ano_paths(ds_folder=Path(cfg["dataset"]["folder"]), sample=sample, suffixes=suffixes)
+
+
+def _pyramid_sources(cfg, img_anno_paths, device):
+    """`img_anno_paths` with every array, tensor or `.npy` image behind a PyramidSlide when `dataset.pyramid` is set."""
+    if not _pyramid_from_cfg(cfg):
+        return img_anno_paths
+    from ...resample import wrap_pyramid
+    return [(wrap_pyramid(img, device), anno) for img, anno in img_anno_paths]
+
+
 def _synthetic_sampler(cfg, device):
     from ... import tiles
 
@@ -119,11 +143,12 @@ def prepare_test_patches(cfg, img_anno_paths=None, device="cuda"):
     import shutil
 
     if img_anno_paths is None:
-        img_anno_paths = utils.get_img_ano_paths(ds_folder=Path(cfg["dataset"]["folder"]), sample="test")
+        img_anno_paths = _dataset_paths(cfg, "test")
     out_dir = Path(cfg["test"]["dir"])
     if out_dir.exists() and out_dir.is_dir():
         shutil.rmtree(out_dir)
-    return extract_and_save_subset(img_anno_paths=img_anno_paths, out_folder=out_dir, patch_size=cfg["dataset"]["patch_size"],
+    return extract_and_save_subset(img_anno_paths=_pyramid_sources(cfg, img_anno_paths, device), out_folder=out_dir,
+                                   patch_size=cfg["dataset"]["patch_size"],
                                    layer=cfg["dataset"]["layer"], patches_per_class=cfg["test"]["samples_per_class"],
                                    device=device, stain=_stain_from_cfg(cfg))
 
@@ -232,13 +257,14 @@ def train(cfg, sampler=None, epochs=None, steps_per_epoch=200, log=print, model=
     out_dir = Path(cfg["training"]["out_dir"])
     out_dir.mkdir(parents=True, exist_ok=True)
 
+    _pyramid_from_cfg(cfg)   # a bad value stops the run here, whichever sampler follows
     if sampler is None:
         folder = Path(cfg["dataset"]["folder"])
         if world > 1:   # the annotation samplers draw from the global NumPy RNG (as the reference's do): one stream per rank
             import numpy as np
             np.random.seed(20240 + rank)
         if folder.exists():   # the reference's data source (train.py:93-103); .psi files need the psimage package
-            sampler = AnnoRegionRndSampler(utils.get_img_ano_paths(folder, sample="train"),
+            sampler = AnnoRegionRndSampler(_pyramid_sources(cfg, _dataset_paths(cfg, "train"), device),
                                            patch_size=cfg["dataset"]["patch_size"], layer=cfg["dataset"]["layer"],
                                            patches_from_one_region=cfg["dataset"]["patches_from_one_region"],
                                            one_image_for_batch=cfg["training"].get("one_image_for_batch", False),

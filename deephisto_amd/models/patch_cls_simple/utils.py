@@ -23,9 +23,9 @@ def get_device():
     return torch.device(next(name for name, available in candidates if available()))
 
 
-def get_img_ano_paths(ds_folder, sample: str = "train") -> list[tuple[Path, Path]]:
+def get_img_ano_paths(ds_folder, sample: str = "train", suffixes=(".psi",)) -> list[tuple[Path, Path]]:
     """(image, annotation) pairs of a dataset folder: every `images/<sample>/*.psi` with its
-    `annotations/<sample>/<stem>.json`."""
+    `annotations/<sample>/<stem>.json`.  `suffixes`: the image files taken (`dataset.pyramid` adds `.npy` slides)."""
     root = Path(ds_folder)
-    images = sorted(p for p in (root / "images" / sample).iterdir() if p.is_file() and p.suffix == ".psi")
+    images = sorted(p for p in (root / "images" / sample).iterdir() if p.is_file() and p.suffix in suffixes)
     return [(img, root / "annotations" / sample / (img.stem + ".json")) for img in images]

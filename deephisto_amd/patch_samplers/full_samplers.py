@@ -88,6 +88,14 @@ class _SlideHolder:
             self._reader = open_slide(psimage_path)
             self._reader._assert_layer(layer)
             self.h, self.w = self._reader.layer_size(self.layer)
+        elif hasattr(psimage_path, "layer_device"):
+            # a reader that holds its layers in HBM (resample.PyramidSlide): the resident layer is taken as it is, with no
+            # whole-layer host read and re-upload; the reader keeps its cache, so it is not closed here
+            psim = open_slide(psimage_path)
+            psim._assert_layer(layer)
+            self.h, self.w = psim.layer_size(self.layer)
+            self._dev = psim.layer_device(self.layer)
+            self.device = self._dev.device
         else:
             with open_slide(psimage_path) as psim:
                 psim._assert_layer(layer)

@@ -364,8 +364,11 @@ class _SlideBank:
     def slide(self, j: int) -> torch.Tensor:
         if self._dev[j] is None:
             r = self._readers[j]
-            h, w = r.layer_size(self.layer)
-            self._dev[j] = torch.from_numpy(np.ascontiguousarray(r.get_region_from_layer(self.layer, (0, 0), (h, w)))).to(self.device)
+            if hasattr(r, "layer_device"):   # resample.PyramidSlide: the layer is resident already
+                self._dev[j] = r.layer_device(self.layer).to(self.device)
+            else:
+                h, w = r.layer_size(self.layer)
+                self._dev[j] = torch.from_numpy(np.ascontiguousarray(r.get_region_from_layer(self.layer, (0, 0), (h, w)))).to(self.device)
         if self.stain is not None and not self._normalised[j]:
             info = {}
             self._dev[j] = self.stain.normalize(self._dev[j], info)   # a new tensor: a caller's own slide is left as it is

@@ -475,6 +475,23 @@ int dh_stain_apply(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t
                    const int32_t* matrix_host, int32_t shift, const uint8_t* lut_dev, int32_t lut_n, uint8_t* out_dev,
                    void* stream);
 
+/* ---- n2: pyramid layers of the resident slide ---------------------------------
+ * The reference reads layer L of a .psi file through psimage; for a slide that is an array in HBM this is the
+ * layer: an integer-exact area average of src_dev = uint8[h][w][3] by the rational factor num/den >= 1,
+ * 1 <= den <= num <= 2048 and num <= 64 * den (reduced by their gcd inside the call).
+ *   Output size: oh = (h * den) / num, ow = (w * den) / num: only output pixels whose footprint lies wholly
+ *     inside the source exist, the ragged remainder is dropped.  oh and ow are passed in and checked;
+ *     oh == 0 or ow == 0 is refused.
+ *   Weights: wy(y, j) = max(0, min((j+1)*den, (y+1)*num) - max(j*den, y*num)), wx the same in x; the weights of
+ *     one output pixel sum to num per axis.
+ *   Sum and rounding: S = sum_j sum_i wy * wx * src[j][i][c], D = num * num, out = (2*S + D) / (2*D) in
+ *     integers: the exact mean rounded half up, once.
+ *   Overflow: 2*S + D <= 511 * 2048^2 < 2^32.
+ *   src_dev and dst_dev = uint8[oh][ow][3] are 16-byte aligned; all byte offsets are 64-bit (h, w <= 2^20);
+ *     dst must not overlap src (refused before the launch). */
+int dh_resample_area(const uint8_t* src_dev, int64_t h, int64_t w, int32_t num, int32_t den, uint8_t* dst_dev,
+                     int64_t oh, int64_t ow, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------
  * Times the dominant kernel (3x3 stride-1 conv, ~85 % of the model FLOPs) with HIP
  * events recorded on the launch stream around every `sample_every`-th launch (at most
