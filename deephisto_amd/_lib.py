@@ -105,6 +105,7 @@ SIGNATURES = {
     "dh_stain_conc_hist": (C.c_int, [_p, _i64, _i64, _p, _p, _i32, _p, _i32, _i32, _p, _p]),
     "dh_stain_apply": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _p, _i32, _p, _p]),
     "dh_resample_area": (C.c_int, [_p, _i64, _i64, _i32, _i32, _p, _i64, _i64, _p]),
+    "dh_slide_dihedral": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
     "dh_profile_start":(C.c_int, [_i32, _i32]),
     "dh_profile_stop": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }

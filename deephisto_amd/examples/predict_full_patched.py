@@ -34,6 +34,7 @@ from ..regions import (SlideRegions, clean_map, export_annotation, extract_regio
 from ..scoring import SlideScore, confusion, rasterize_annotation, save_score, score_prediction  # noqa: F401  (exported here)
 from ..stain import StainFit, StainNormalizer  # noqa: F401  (exported here)
 from ..tissue import TissueFilter, fill_uncovered, score_tiles  # noqa: F401  (exported here)
+from ..tta import TestTimeAugmenter, dihedral_view  # noqa: F401  (exported here)
 from ..visualize import ERROR_COLORS, KNOWN_COLORS, _save_jpeg, perform_and_save_visualizations, save_proba  # noqa: F401  (exported here)
 
 
@@ -241,6 +242,19 @@ def _stain_from_args(ap, args) -> StainNormalizer | None:
     return StainNormalizer(args.stain)
 
 
+def _tta_from_args(ap, args, model=None) -> TestTimeAugmenter | None:
+    """The TestTimeAugmenter of --tta, or None for `--tta off`; a bad combination is an argparse error.  `model`: the module
+    injected into main, if any: a foreign one under --random_sampler goes the callback route, which has no views."""
+    if args.tta == "off":
+        return None
+    if args.ondisk:
+        ap.error("--tta needs the slide resident in HBM; it cannot be combined with --ondisk")
+    if args.random_sampler and model is not None and not isinstance(model, ResNetHIP):
+        ap.error("--tta runs on the fused routes (a ResNet18HIP or ResNet50HIP model); under --random_sampler a foreign model "
+                 "goes through the per-batch callback, which has no views")
+    return TestTimeAugmenter(args.tta)
+
+
 def _pyramid_from_args(ap, args) -> None:
     """Checks --pyramid; a bad combination is an argparse error."""
     if not args.pyramid:
@@ -305,6 +319,9 @@ def _build_parser():
                          "with --pyramid the layer is normalised, not the base")
     ap.add_argument("--stain_target", default=None, metavar="PATH", help="with --stain: a StainFit JSON (another slide's fit) as the target")
     ap.add_argument("--save_stain_fit", default=None, metavar="PATH", help="with --stain: this slide's StainFit as JSON (rank 0)")
+    ap.add_argument("--tta", choices=["off", "flips", "d4"], default="off",
+                    help="test-time augmentation: classify every tile in 4 (flips) or all 8 (d4) orientations of the square and "
+                         "average the logits (resident slide; 4 / 8 times the forward work)")
     ap.add_argument("--proba", action="store_true", help="per-cell mean softmax probabilities; writes {stem}_confidence.jpg")
     ap.add_argument("--heat", nargs="+", default=[], metavar="LABEL",
                     help=f"with --proba: one {{stem}}_heat_LABEL.jpg per class label ({', '.join(KNOWN_COLORS)})")
@@ -321,14 +338,15 @@ def _build_parser():
     return ap
 
 
-def _check_args(ap, args) -> None:
+def _check_args(ap, args, model=None) -> None:
     """The flag checkers, before the process group or any GPU is touched; leaves the TissueFilter (or None) in
-    `args.tissue_filter`, the StainNormalizer (or None) in `args.stain_norm` and the records of --anno (or None) in
-    `args.anno_records`."""
+    `args.tissue_filter`, the StainNormalizer (or None) in `args.stain_norm`, the TestTimeAugmenter (or None) in `args.tta_aug`
+    and the records of --anno (or None) in `args.anno_records`.  `model`: the module injected into main, if any."""
     _regions_from_args(ap, args)
     _pyramid_from_args(ap, args)
     args.stain_norm = _stain_from_args(ap, args)
     args.tissue_filter = _tissue_from_args(ap, args)
+    args.tta_aug = _tta_from_args(ap, args, model)
     args.anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
 
@@ -373,7 +391,7 @@ def _run(args, model, device, rank, world):
                                     mode=mode, stride=args.stride, device=device)
         info: dict = {}
         out = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
-                                   tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba)
+                                   tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug)
         pred, proba = out if args.proba else (out, None)
         if args.tissue_filter is not None and rank == 0:
             print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
@@ -384,10 +402,12 @@ def _run(args, model, device, rank, world):
     smp = FullImageRndSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                               mode=mode, device=device)
     if smp.resident and smp.index_logic == "device" and isinstance(model, ResNetHIP):
-        out = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis, return_proba=args.proba)
+        out = predict_random_patched(smp, model, n_cls, downscale=args.downscale_vis, return_proba=args.proba, tta=args.tta_aug)
         pred, proba = out if args.proba else (out, None)
         pred = pred.cpu().numpy()
     else:   # a foreign module or a slide streamed from disk: the reference's callback loop
+        if args.tta_aug is not None:   # _check_args refused what it could see; a sampler that fell back to host index logic lands here
+            raise ValueError("--tta runs on the fused routes only; this slide and sampler go through the per-batch callback")
         predictor = ImagePredictorPatched((smp.h, smp.w), patch_sampler=smp.generator(),
                                           batch_predictor=lambda patches: batch_predictor(patches, model, device),
                                           anno=anno_dsc, layer=args.layer, downscale=args.downscale_vis, device=device)
@@ -464,6 +484,9 @@ def main(argv=None, model=None):
     `--anno` keeps scoring the uncleaned map (the cleaned one gets a second score).
     `--pyramid` makes `--layer L` of a `--synthetic` slide or a `.npy` image the slide at 1/L of its resolution (DESIGN.md section
     4.14): the exact area average, built on the device; everything below reads that layer, and `--stain` normalises it.
+    `--tta flips|d4` classifies every tile in four or all eight orientations of the square and averages the logits per tile
+    (both fused routes, resident slide; refused with `--ondisk` and for a foreign model on the callback
+    route); overlays, scoring and regions read the untransformed slide and the map, as without it.
     `--stain macenko` normalises the slide's stain appearance first (resident slide): the prediction, the
     tissue filter and the overlays all read the normalised slide; `--stain_target PATH` takes another slide's saved fit as the
     target instead of the default constants, `--save_stain_fit PATH` writes this slide's fit (rank 0).
@@ -473,7 +496,7 @@ def main(argv=None, model=None):
 
     ap = _build_parser()
     args = ap.parse_args(argv)
-    _check_args(ap, args)
+    _check_args(ap, args, model)
     rank, world, _dev_index, owned = init_from_env()   # binds the rank's GPU before any other GPU call
     ok = False
     try:

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import inspect
 import os
 
 import numpy as np
@@ -22,6 +23,7 @@ from .models.patch_cls_simple.engine import ResNetHIP
 from .patch_samplers.full_samplers import FullImageDenseSampler
 from .stain import StainNormalizer
 from .tissue import TissueFilter, fill_uncovered, score_tiles
+from .tta import TestTimeAugmenter, as_augmenter, dihedral_view, map_origins_device, view_shape
 
 
 def shard_range(n_items: int, world: int, rank: int) -> tuple[int, int]:
@@ -125,6 +127,10 @@ def _normalised_first(predict):
             return predict(sampler, *args, **kwargs)
         finally:
             sampler._dev = raw
+    # what inspect shows stays the positional parameters, which are the reference's: the keyword-only additions (these two, and
+    # `tta=` / `tta_info=` of the wrapped function, which pass through **kwargs) are described in the docstrings
+    sig = inspect.signature(predict)
+    with_stain.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.kind is not p.KEYWORD_ONLY])
     return with_stain
 
 
@@ -139,7 +145,8 @@ def _launch_tiles(fwd, fwd_name, handle, slide, h, w, o_dev, s, e, P, out, n_cla
 def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
                          downscale: int = 16, micro_batch: int | None = None, group=None,
                          return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None,
-                         tissue: TissueFilter | None = None, tissue_info: dict | None = None, return_proba: bool = False):
+                         tissue: TissueFilter | None = None, tissue_info: dict | None = None, return_proba: bool = False, *,
+                         tta: TestTimeAugmenter | None = None, tta_info: dict | None = None):
     """Device-resident whole-slide prediction (rows a1-a8 end to end).
 
     `model`: ResNet18HIP or ResNet50HIP; it names its own fused entry (`tiles_entry`) and launch size
@@ -168,11 +175,22 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     `dedupe_padding=True` removes that.  With `tissue` it runs over the kept tiles only (a rejected tile's NaN row never
     enters a softmax) and uncovered cells get `tissue.fill_class`.
     Keyword-only `stain=` / `stain_info=`: see `_normalised_first`, which wraps this function.
+    Keyword-only `tta`: a tta.TestTimeAugmenter (or what its constructor takes): every tile is classified
+    in each of the augmenter's dihedral views and the logits are averaged per tile, in the order of the views, before the
+    exchange; tile list, tissue filter, shard range, launch size, the one all-gather and everything behind it are those of
+    the plain run, which sees one logits row per tile as before.  A view of the slide is built once per view into one reused
+    buffer of the slide's size (peak memory: the slide plus one copy) and the unchanged fused entry runs over the mapped
+    origins; every rank transforms its own copy (the bytes are exact, nothing is exchanged).  Needs a resident slide.  `stain=`
+    composes: the views are those of the normalised slide.  `tta_info`: a dict that receives views (names) and
+    n_forward_tiles (tiles x views on this rank).  None leaves every code path and every bit as it is.
     Returns int64[h//d, w//d] on the device (and the float32[n_padded, n_cls] logits; rows of rejected tiles are NaN).
     """
     import torch.distributed as dist
 
     streamed = not sampler.resident          # ONDISK_MULTIPROC: row strips are uploaded as they are needed
+    tta = as_augmenter(tta)
+    if tta is not None and streamed:
+        raise ValueError("test-time augmentation needs an HBM-resident slide (ONDISK_MULTIPROC streams it)")
     if tissue is not None:
         if not isinstance(sampler, FullImageDenseSampler):
             raise ValueError("the tissue filter works on the dense sampler's grid only (not on the random sampler's branch)")
@@ -214,7 +232,11 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     fwd, fwd_name = model.tiles_entry()
     if streamed:
         _forward_streamed(sampler, handles[0], origins[lo:hi], local, n_classes, mb, model)
-    for k, s in enumerate(range(0, 0 if streamed else hi - lo, mb)):
+    if tta is not None:
+        _forward_views(tta, fwd, fwd_name, handles, lanes, slide, o_dev, P, mb, local, n_classes)
+        if tta_info is not None:
+            tta_info.update(views=list(tta.views), n_forward_tiles=(hi - lo) * len(tta))
+    for k, s in enumerate(range(0, 0 if streamed or tta is not None else hi - lo, mb)):
         lane = k % len(handles)
         _launch_tiles(fwd, fwd_name, handles[lane], slide, sampler.h, sampler.w, o_dev, s, min(s + mb, hi - lo), P, local,
                       n_classes, lanes[lane])
@@ -231,6 +253,45 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     else:
         logits_work = exchange_logits(local, n_work, group) if distributed else local[:n_work]
     return _finish(sampler, logits_work, kept, kept_yx_dev, downscale, dedupe_padding, tissue, return_logits, return_proba)
+
+
+def _forward_views(tta, fwd, fwd_name, handles, lanes, slide, o_dev, P, mb, local, n_classes):
+    """The launches of predict_full_patched under test-time augmentation: for each view of `tta` in turn the view of `slide` is
+    built (into one buffer, reused; "r0" is the slide itself), the fused entry runs over the mapped origins of `o_dev` in the
+    plain run's micro-batches on `lanes`, and the view's logits are folded into the first len(o_dev) rows of `local`.
+    The micro-batches of a view run on the lane streams and the transform of the next view overwrites the slide they read, so
+    the lanes are joined into the main stream (lanes[0]) before each transform and wait for it afterwards; the fold of a view
+    runs on the main stream behind the same join.  On return every lane has been joined and `local` holds the mean."""
+    main, n = lanes[0], int(o_dev.shape[0])
+    h, w = int(slide.shape[0]), int(slide.shape[1])
+    buf = per_view = None
+    if n == 0:
+        return
+    for k, v in enumerate(tta.ids):
+        for st in lanes[1:]:
+            main.wait_stream(st)
+        if k > 1:
+            tta.fold(local[:n], per_view, k - 1)      # view k - 1 has finished; view 0 went straight into `local`
+        if v == 0:
+            view = slide
+        else:
+            buf = torch.empty(slide.numel(), dtype=torch.uint8, device=slide.device) if buf is None else buf
+            view = dihedral_view(slide, v, out=buf)
+        o_view = map_origins_device(o_dev, h, w, P, v)
+        if k and per_view is None:
+            per_view = torch.empty((n, n_classes), dtype=torch.float32, device=slide.device)
+        for st in lanes[1:]:
+            st.wait_stream(main)
+        vh, vw = view_shape(h, w, v)
+        for j, s in enumerate(range(0, n, mb)):
+            lane = j % len(handles)
+            _launch_tiles(fwd, fwd_name, handles[lane], view, vh, vw, o_view, s, min(s + mb, n), P, local if k == 0 else per_view,
+                          n_classes, lanes[lane])
+    for st in lanes[1:]:
+        main.wait_stream(st)
+    if len(tta) > 1:
+        tta.fold(local[:n], per_view, len(tta) - 1)
+    tta.finish(local[:n])
 
 
 def _finish(sampler, logits_work, kept, kept_yx_dev, downscale, dedupe_padding, tissue, return_logits, return_proba):
@@ -275,7 +336,8 @@ def _padded_logits(logits_work, kept, n_unique, n_padded):
 
 @_normalised_first
 def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, micro_batch: int | None = None,
-                           return_canvas: bool = False, timing: dict | None = None, return_proba: bool = False):
+                           return_canvas: bool = False, timing: dict | None = None, return_proba: bool = False, *,
+                           tta: TestTimeAugmenter | None = None):
     """The reference's default branch (FullImageRndSampler through ImagePredictorPatched.process(),
     predict_full_patched.py:40-63, 150-162) with the random sampler's device index logic and large forward launches.
 
@@ -290,6 +352,11 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     sequence: under this sampler a cell is covered anything from `dense_level` to dozens of times, and `count` is what makes
     its probabilities comparable from cell to cell.
     Keyword-only `stain=` / `stain_info=`: see `_normalised_first`, which wraps this function.
+    Keyword-only `tta`: a tta.TestTimeAugmenter (or what its constructor takes): every launch group runs
+    once per view over the device-mapped origins and the logits are averaged per tile in the order of the views; sampler,
+    origin sequence and accumulation are those of the plain run.  The groups are launched while the sampler is still
+    planning, so all requested views of the slide are built once up front: V - 1 extra resident slides for V views ("r0" is
+    the slide itself).  None changes nothing.
     Returns int64[h//d, w//d] on the device (and the float32 canvas when `return_canvas`)."""
     import time
 
@@ -309,6 +376,9 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
     cov_stream.wait_stream(main)                   # the slide / model state queued so far
     model.eval()
     model.lane_handles(1)
+    tta = as_augmenter(tta)
+    # (view id, that view of the slide): built on the compute stream before the first launch
+    views = [] if tta is None else [(v, slide if v == 0 else dihedral_view(slide, v)) for v in tta.ids]
     chunks: list[torch.Tensor] = []                # int32[cap, 2] origin buffers (kept alive to the end)
     logits: list[torch.Tensor] = []
     hosts: list[np.ndarray] = []
@@ -329,8 +399,13 @@ def predict_random_patched(sampler, model, n_classes: int, downscale: int = 16, 
         ev.record(cov_stream)
         main.wait_event(ev)
         with torch.cuda.stream(main):
+            if tta is None:
+                for s0 in range(0, o.shape[0], mb):
+                    logits.append(model.forward_tiles(slide, o[s0:s0 + mb], P))
+                return
+            mapped = [map_origins_device(o, sampler.h, sampler.w, P, v) for v, _ in views]
             for s0 in range(0, o.shape[0], mb):
-                logits.append(model.forward_tiles(slide, o[s0:s0 + mb], P))
+                logits.append(tta.combine(model.forward_tiles(view, m[s0:s0 + mb], P) for (_, view), m in zip(views, mapped)))
 
     n_batches, host_s = 0, 0.0
     th = time.perf_counter()

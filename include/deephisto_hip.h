@@ -492,6 +492,19 @@ int dh_stain_apply(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t
 int dh_resample_area(const uint8_t* src_dev, int64_t h, int64_t w, int32_t num, int32_t den, uint8_t* dst_dev,
                      int64_t oh, int64_t ow, void* stream);
 
+/* ---- n3: dihedral views of the resident slide, for test-time augmentation ------
+ * A mirrored or turned tile of a slide is the plain tile, at a mapped origin, of the mirrored or turned slide;
+ * this builds that slide.  view = k + 4 * f with k in 0..3 and f in 0..1:
+ *     dst = np.rot90(np.fliplr(src) if f else src, k)        over axes (0, 1)
+ * for src_dev = uint8[h][w][3]; the channel triple is never reordered.  dst_dev is uint8[h][w][3] for even k and
+ * uint8[w][h][3] for odd k, 3 * h * w bytes either way.  View 0 is a copy.  One quarter turn sends pixel (y, x)
+ * to (w - 1 - x, y), the mirror sends it to (y, w - 1 - x).
+ *   Every destination byte is a source byte: no arithmetic, no float, no atomics.  All byte offsets are 64-bit;
+ *     1 <= h, w <= 2^20.  Neither pointer needs any alignment.
+ *   Refused with DH_EINVAL (reason in dh_last_error): a view outside 0..7, h or w below 1 (or above 2^20), a null
+ *     pointer, dst == src or any overlap of the two ranges of 3 * h * w bytes. */
+int dh_slide_dihedral(const uint8_t* src_dev, int64_t h, int64_t w, int32_t view, uint8_t* dst_dev, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------
  * Times the dominant kernel (3x3 stride-1 conv, ~85 % of the model FLOPs) with HIP
  * events recorded on the launch stream around every `sample_every`-th launch (at most
