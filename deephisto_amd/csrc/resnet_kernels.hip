@@ -1730,6 +1730,7 @@ extern "C" int dh_debug_stem_strip_width(int32_t pc) {
 }
 
 #include "gemm1x1_f32.inc"
+#include "train_core.inc"
 #include "train.inc"
 #include "train2_kernels.inc"
 #include "wgrad_ring.inc"

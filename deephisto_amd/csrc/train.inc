@@ -1,5 +1,6 @@
 // train.inc -- training step of the ResNet-18 patch classifier (SURVEY row a7), float32.
-// Included at the end of resnet_kernels.hip (same translation unit: reuses the conv kernels).
+// Included at the end of resnet_kernels.hip (same translation unit: reuses the conv kernels), behind train_core.inc (the parameter
+// store, buckets, Adam launch and side-stream hand-off shared with the bf16 engine).
 //
 // Replaces, for the network of models/patch_cls_simple/model.py:5-11, the work of
 //   outputs = model(inputs); loss = criterion(outputs, labels); loss.backward(); optimizer.step()
@@ -14,8 +15,8 @@
 //   forward  : conv (the inference kernels with unit scale / zero shift) -> batch statistics
 //              -> normalise (+residual) (+ReLU)
 //   backward : ReLU mask + BN backward (two per-channel sums, then one elementwise pass),
-//              dgrad = the same 3x3 conv kernel on the flipped weights (stride 2: on the
-//              zero-upsampled gradient), wgrad = pixel-reduction GEMM on v_mfma_f32_32x32x2_f32
+//              dgrad = the same 3x3 conv kernel on the flipped weights (stride 2: the four
+//              parity classes of dX over dZ itself), wgrad = pixel-reduction GEMM on v_mfma_f32_32x32x2_f32
 //              (K = output pixels); per-workgroup partial tiles go to slab buffers with plain stores and are summed
 //              in a fixed order: no float atomics anywhere in the step, so gradients and updates are bit-reproducible.
 #include <array>
@@ -28,11 +29,7 @@ namespace {
 
 constexpr float BN_EPS = 1e-5f, BN_MOMENTUM = 0.1f;
 
-// ---------------- small elementwise / utility kernels ----------------
-__global__ void fill_kernel(float* p, int64_t n, float v) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
+// ---------------- small elementwise / utility kernels (fill_kernel, adam_kernel, grid_for: train_core.inc) ----------------
 // pack [cout][cin][ks][ks] f32 master weights into MFMA fragment order (see pack_conv_weights);
 // FLIPT: pack the dgrad operator instead: Wd[co'=ci][ci'=co][kh][kw] = W[co][ci][ks-1-kh][ks-1-kw].
 template <typename T, bool FLIPT>
@@ -1140,24 +1137,6 @@ __global__ void ce_loss_kernel(const float* __restrict__ logits, const int64_t* 
   if (threadIdx.x == 0) *loss = red[0] / (float)B;
 }
 
-// Adam (torch.optim.Adam defaults, no weight decay, no amsgrad) over one flat parameter arena
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2,
-                                                   float eps, float bc1, float bc2_sqrt) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - (lr / bc1) * (mi / denom);
-  }
-}
-
-inline int grid_for(int64_t n, int per = 256, int cap = 256 * 16) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, cap));
-}
-
 }  // namespace
 
 // =====================================================================================
@@ -1174,15 +1153,14 @@ struct TrainConv {
   int Ho = 0, Wo = 0, Hi = 0, Wi = 0;
 };
 
-struct dh_train {
+struct TrBlock { int c1, c2, ds; int hi, ho; };   // a residual block: conv indices (ds: downsample or -1) and its input / output map size
+
+struct dh_train : TrainStore {   // the arena is in FORWARD order: the backward pass completes it from the end
   int B = 0, P = 0;
-  std::map<std::string, std::pair<int64_t, int64_t>> slot;   // name -> (offset, n) in the parameter arenas
-  std::map<std::string, std::pair<int64_t, int64_t>> rslot;  // running_mean / running_var -> (offset, n)
-  int64_t n_params = 0, n_running = 0;
-  float *Pm = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *R = nullptr;
   std::vector<TrainConv> tc;
+  std::vector<TrBlock> blocks;    // forward order; made once at the first train_begin (sizes: per batch shape)
   float *ones = nullptr, *zeros = nullptr, *partial = nullptr;
-  float *X1 = nullptr, *pooled = nullptr, *dlogits_fc = nullptr;
+  float *X1 = nullptr, *pooled = nullptr;
   float *BIG1 = nullptr, *SM[4] = {nullptr, nullptr, nullptr, nullptr};
   float* stem_slabs = nullptr;
   uint8_t* pool_idx = nullptr;    // first-maximum position (0..8) of every maxpool output element
@@ -1191,20 +1169,8 @@ struct dh_train {
   int pack_blocks = 0, pack_nd = 0;
   std::vector<int> pack_blk0;     // first workgroup of every descriptor (+ the total), host copy; descriptor j = conv j + 1
   const float* x_in = nullptr;  // input of the last forward (caller memory; must stay alive until backward)
-  std::vector<void*> allocs;        // live as long as the training state: arenas, packed weights, per-channel buffers
-  std::vector<void*> shape_allocs;  // sized by (B, P): activations and workspaces, re-made when the batch shape changes
-  bool shape_phase = false;         // tr_alloc target
-  int64_t tracked = 0;          // num_batches_tracked
-  int64_t adam_t = 0;           // Adam steps taken (bias correction when the caller passes step <= 0)
-  // data-parallel gradient buckets: the arena is in forward order and the backward pass completes it from the END
-  // (fc, then the blocks last to first, then the stem), so bucket k is a suffix slice [offset, offset + count)
-  void (*bucket_cb)(int32_t, int64_t, int64_t, void*) = nullptr;
-  void* bucket_user = nullptr;
-  std::vector<std::pair<int64_t, int64_t>> buckets;   // (offset, count) in completion order
-  // weight gradients on a side stream (lowest priority), handed over once per residual block: they fill the CUs the persistent
+  // TrainStore::side: the weight gradients are handed over once per residual block: they fill the CUs the persistent
   // convolution launches leave idle in their last round of tiles.  DH_T1_SIDE=0: everything on the caller's stream.
-  hipStream_t side = nullptr;
-  hipEvent_t ev_dz = nullptr, ev_join = nullptr;
 };
 
 namespace {
@@ -1231,12 +1197,6 @@ void tr_dump(const char* name, int blk, const float* dev, int64_t n, hipStream_t
 }
 #endif
 
-int tr_alloc(dh_train* t, float** p, int64_t n) {
-  DH_HIP(hipMalloc((void**)p, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
-  (t->shape_phase ? t->shape_allocs : t->allocs).push_back(*p);
-  return DH_OK;
-}
-
 // packs the weights of convs [i0, i1), 1 <= i0 (the stem has its own kernel: tr_pack_all)
 int tr_pack(dh_resnet18* net, hipStream_t st, int i0, int i1) {
   dh_train* t = net->train;
@@ -1246,9 +1206,7 @@ int tr_pack(dh_resnet18* net, hipStream_t st, int i0, int i1) {
     for (size_t i = 1; i < net->convs.size(); ++i) {
       const ConvLayer& c = net->convs[i];
       t->pack_blk0.push_back(blk);
-      const int64_t n = (int64_t)c.cout * c.cin * c.ks * c.ks;
       d.push_back({t->Pm + t->slot[c.name + ".weight"].first, t->tc[i].wp_f, t->tc[i].wp_d, c.cout, c.cin, c.ks, blk});
-      (void)n;
       DH_REQUIRE(c.ks != 3 || (c.cout % 64 == 0 && c.cin % 64 == 0), "pack: 3x3 convolution %s with %d -> %d channels (multiples of 64)", c.name.c_str(), c.cin, c.cout);
       blk += packf_blocks(c.cout, c.cin, c.ks);
     }
@@ -1275,10 +1233,14 @@ int tr_pack_all(dh_resnet18* net, hipStream_t st) {
   return rc ? rc : tr_pack(net, st, 1, (int)net->convs.size());
 }
 
+// The launch helpers below take what they use (no engine handle), so the test hooks at the end of this file run the very code of a step.
+// `ones` / `zeros`: per-channel unit scale and zero shift (at least `cout` floats) of the inference kernels' epilogue.
+struct UnitAffine { const float *ones, *zeros; };
+
 // conv through the inference kernels with unit scale / zero shift (raw conv output).  1x1 (the downsample branches; round 5): the
 // float32 GEMM of gemm1x1_f32.inc -- `wp` is then W[cout][cin] K-contiguous: the master tensor (forward) or the transposed copy of the
 // data gradient's operator (pack_all_f32_kernel).
-int tr_conv(dh_resnet18* net, int cin, int cout, int ks, int stride, const float* wp, const float* in,
+int tr_conv(UnitAffine u, int cin, int cout, int ks, int stride, const float* wp, const float* in,
             const float* res, float* out, int B, int Hi, int Wi, hipStream_t st) {
   if (ks == 1) {
     const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
@@ -1286,46 +1248,60 @@ int tr_conv(dh_resnet18* net, int cin, int cout, int ks, int stride, const float
   }
   ConvLayer L{"train", "train", cin, cout, ks, stride};
   L.w_dev = const_cast<float*>(wp);
-  L.scale_dev = net->train->ones;
-  L.shift_dev = net->train->zeros;
+  L.scale_dev = const_cast<float*>(u.ones);
+  L.shift_dev = const_cast<float*>(u.zeros);
   int ho, wo;
   return run_conv<float>(L, in, res, out, B, Hi, Wi, false, st, &ho, &wo);
 }
 
 // dX = data gradient of a 3x3 / stride-2 conv (cz channels of dZ -> cx channels of dX) from the packed dgrad operator `wp`
-int tr_dgrad_s2(dh_resnet18* net, int cz, int cx, const float* wp, const float* dz, const float* res, float* dx, int B, int Ho, int Wo,
+int tr_dgrad_s2(UnitAffine u, int cz, int cx, const float* wp, const float* dz, const float* res, float* dx, int B, int Ho, int Wo,
                 int Hi, int Wi, hipStream_t st) {
   ConvLayer L{"train", "train", cz, cx, 3, 1};
   L.w_dev = const_cast<float*>(wp);
-  L.scale_dev = net->train->ones;
-  L.shift_dev = net->train->zeros;
+  L.scale_dev = const_cast<float*>(u.ones);
+  L.shift_dev = const_cast<float*>(u.zeros);
   return launch_dgrad_s2<float>(L, dz, res, dx, B, Ho, Wo, Hi, Wi, st);
 }
 
-// pool_out / pool_idx (the stem): normalise + ReLU + 3x3/2 maxpool in one pass (bn_apply_pool_kernel); tc.Y stays unwritten
-int tr_bn_forward(dh_resnet18* net, const ConvLayer& c, TrainConv& tc, const float* res, bool relu, int B, hipStream_t st,
-                  float* pool_out = nullptr, uint8_t* pool_idx = nullptr) {
+// One BN layer as its launches see it: pre-activation map Z [rows][C], affine parameters and their gradients, running statistics,
+// the per-channel buffers and the reduction workspace `partial` (RED_NB * 2 * C floats).  B, Ho, Wo: only the pooled (stem) paths.
+struct BnView {
+  const float* Z;
+  const float *gamma, *beta;
+  float *run_mean, *run_var, *dgamma, *dbeta;
+  BnBufs bn;
+  int64_t rows;
+  int C, B, Ho, Wo;
+  float* partial;
+  int red_blocks(int64_t units) const { const int rpi = 256 / (C / 4); return (int)std::min<int64_t>(RED_NB, (units + rpi - 1) / rpi); }
+};
+BnView tr_bn_view(dh_resnet18* net, int i) {
   dh_train* t = net->train;
-  const int C = c.cout;
-  const int64_t rows = (int64_t)B * tc.Ho * tc.Wo;
-  const int rpi = 256 / (C / 4);
-  const int nb = (int)std::min<int64_t>(RED_NB, (rows + rpi - 1) / rpi);
-  const float* gamma = t->Pm + t->slot[c.bn + ".weight"].first;
-  const float* beta = t->Pm + t->slot[c.bn + ".bias"].first;
-  float* rm = t->R + t->rslot[c.bn + ".running_mean"].first;
-  float* rv = t->R + t->rslot[c.bn + ".running_var"].first;
+  const ConvLayer& c = net->convs[i];
+  const TrainConv& tc = t->tc[i];
+  const int64_t w = t->slot[c.bn + ".weight"].first, b = t->slot[c.bn + ".bias"].first;
+  return {tc.Z, t->Pm + w, t->Pm + b, t->R + t->rslot[c.bn + ".running_mean"].first, t->R + t->rslot[c.bn + ".running_var"].first,
+          t->G + w, t->G + b, tc.bn, (int64_t)t->B * tc.Ho * tc.Wo, c.cout, t->B, tc.Ho, tc.Wo, t->partial};
+}
+
+// y = [relu](bn(Z) [+ res]) with batch statistics.  pool_out / pool_idx (the stem): normalise + ReLU + 3x3/2 maxpool in one pass
+// (bn_apply_pool_kernel); y stays unwritten
+int tr_bn_forward(const BnView& v, const float* res, bool relu, float* y, hipStream_t st, float* pool_out = nullptr, uint8_t* pool_idx = nullptr) {
+  const int C = v.C;
+  const int nb = v.red_blocks(v.rows);
   // one pass: {sum z, sum z^2} per workgroup in float32, column sums and E[z^2] - mean^2 in double
-  hipLaunchKernelGGL((col_reduce_kernel<3>), dim3(nb), dim3(256), 0, st, tc.Z, nullptr, nullptr, nullptr, nullptr, rows, C, 0, t->partial);
-  hipLaunchKernelGGL(bn_stat_finalize_onepass_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, t->partial, nb, C, (double)rows,
-                     tc.bn.mean, tc.bn.invstd, gamma, beta, tc.bn.scale, tc.bn.shift, rm, rv);
-  const int64_t n4 = rows * C / 4;
+  hipLaunchKernelGGL((col_reduce_kernel<3>), dim3(nb), dim3(256), 0, st, v.Z, nullptr, nullptr, nullptr, nullptr, v.rows, C, 0, v.partial);
+  hipLaunchKernelGGL(bn_stat_finalize_onepass_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, v.partial, nb, C, (double)v.rows,
+                     v.bn.mean, v.bn.invstd, v.gamma, v.beta, v.bn.scale, v.bn.shift, v.run_mean, v.run_var);
+  const int64_t n4 = v.rows * C / 4;
   if (pool_out) {
     DH_REQUIRE(relu && !res && pool_idx, "bn + pool: ReLU'd BN without a residual");
-    const int Hp = (tc.Ho + 2 - 3) / 2 + 1, Wp = (tc.Wo + 2 - 3) / 2 + 1;
-    hipLaunchKernelGGL(bn_apply_pool_kernel, dim3(grid_for((int64_t)B * Hp * Wp * (C / 4))), dim3(256), 0, st, tc.Z, tc.bn.scale, tc.bn.shift,
-                       pool_out, pool_idx, B, tc.Ho, tc.Wo, C, Hp, Wp);
+    const int Hp = (v.Ho + 2 - 3) / 2 + 1, Wp = (v.Wo + 2 - 3) / 2 + 1;
+    hipLaunchKernelGGL(bn_apply_pool_kernel, dim3(grid_for((int64_t)v.B * Hp * Wp * (C / 4))), dim3(256), 0, st, v.Z, v.bn.scale, v.bn.shift,
+                       pool_out, pool_idx, v.B, v.Ho, v.Wo, C, Hp, Wp);
   } else {
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, tc.Z, tc.bn.scale, tc.bn.shift, res, tc.Y, n4, C, relu ? 1 : 0);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, v.Z, v.bn.scale, v.bn.shift, res, y, n4, C, relu ? 1 : 0);
   }
   DH_LAUNCH_CHECK();
   return DH_OK;
@@ -1333,64 +1309,42 @@ int tr_bn_forward(dh_resnet18* net, const ConvLayer& c, TrainConv& tc, const flo
 
 // dZ (and optionally the masked gradient g) from dY for one BN(+ReLU); fills dgamma / dbeta
 // relu with y_for_mask == nullptr: the BN output went straight into a ReLU (no identity term): the pattern is recomputed from Z
-int tr_bn_backward(dh_resnet18* net, const ConvLayer& c, TrainConv& tc, const float* dy, const float* y_for_mask,
-                   bool relu, float* dz, float* g_out, int B, hipStream_t st) {
+int tr_bn_backward(const BnView& v, const float* dy, const float* y_for_mask, bool relu, float* dz, float* g_out, hipStream_t st) {
   const int rmode = !relu ? 0 : y_for_mask ? 1 : 2;
-  dh_train* t = net->train;
-  const int C = c.cout;
-  const int64_t rows = (int64_t)B * tc.Ho * tc.Wo;
-  const int rpi = 256 / (C / 4);
-  const int nb = (int)std::min<int64_t>(RED_NB, (rows + rpi - 1) / rpi);
-  const float* gamma = t->Pm + t->slot[c.bn + ".weight"].first;
-  float* dgamma = t->G + t->slot[c.bn + ".weight"].first;
-  float* dbeta = t->G + t->slot[c.bn + ".bias"].first;
-  hipLaunchKernelGGL((col_reduce_kernel<2>), dim3(nb), dim3(256), 0, st, tc.Z, dy, y_for_mask, tc.bn.mean, tc.bn.invstd, rows, C,
-                     rmode, t->partial, tc.bn.scale, tc.bn.shift);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, t->partial, nb, C, (double)rows, gamma,
-                     tc.bn.mean, tc.bn.invstd, dgamma, dbeta, tc.bn.k0, tc.bn.k1, tc.bn.k2);
-  const int64_t n4 = rows * C / 4;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, dy, y_for_mask, tc.Z, tc.bn.k0, tc.bn.k1, tc.bn.k2,
-                     dz, g_out, n4, C, rmode, tc.bn.scale, tc.bn.shift);
+  const int C = v.C;
+  const int nb = v.red_blocks(v.rows);
+  hipLaunchKernelGGL((col_reduce_kernel<2>), dim3(nb), dim3(256), 0, st, v.Z, dy, y_for_mask, v.bn.mean, v.bn.invstd, v.rows, C,
+                     rmode, v.partial, v.bn.scale, v.bn.shift);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, v.partial, nb, C, (double)v.rows, v.gamma,
+                     v.bn.mean, v.bn.invstd, v.dgamma, v.dbeta, v.bn.k0, v.bn.k1, v.bn.k2);
+  const int64_t n4 = v.rows * C / 4;
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, dy, y_for_mask, v.Z, v.bn.k0, v.bn.k1, v.bn.k2,
+                     dz, g_out, n4, C, rmode, v.bn.scale, v.bn.shift);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
 // BN(+ReLU, pattern from Z) backward of a map that went through the 3x3/2 maxpool (the stem): dy is gathered from the pooled gradient and
 // the recorded positions inside both passes (no maxpool-backward launch, no 112 x 112 gradient tensor in HBM)
-int tr_bn_pool_backward(dh_resnet18* net, const ConvLayer& c, TrainConv& tc, const float* dpool, const uint8_t* pool_idx, float* dz, int B,
-                        hipStream_t st) {
-  dh_train* t = net->train;
-  const int C = c.cout;
-  const int64_t rows = (int64_t)B * tc.Ho * tc.Wo;
-  const int64_t blocks4 = (int64_t)B * ((tc.Ho + 1) / 2) * ((tc.Wo + 1) / 2);
-  const int rpi = 256 / (C / 4);
-  const int nb = (int)std::min<int64_t>(RED_NB, (blocks4 + rpi - 1) / rpi);
-  const int Hp = (tc.Ho + 2 - 3) / 2 + 1, Wp = (tc.Wo + 2 - 3) / 2 + 1;
-  const float* gamma = t->Pm + t->slot[c.bn + ".weight"].first;
-  float* dgamma = t->G + t->slot[c.bn + ".weight"].first;
-  float* dbeta = t->G + t->slot[c.bn + ".bias"].first;
-  hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(nb), dim3(256), 0, st, tc.Z, dpool, pool_idx, tc.bn.mean, tc.bn.invstd, tc.bn.scale,
-                     tc.bn.shift, B, tc.Ho, tc.Wo, C, Hp, Wp, t->partial);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, t->partial, nb, C, (double)rows, gamma,
-                     tc.bn.mean, tc.bn.invstd, dgamma, dbeta, tc.bn.k0, tc.bn.k1, tc.bn.k2);
-  hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(grid_for(blocks4 * C / 4)), dim3(256), 0, st, tc.Z, dpool, pool_idx, tc.bn.k0, tc.bn.k1,
-                     tc.bn.k2, tc.bn.scale, tc.bn.shift, dz, B, tc.Ho, tc.Wo, C, Hp, Wp);
+int tr_bn_pool_backward(const BnView& v, const float* dpool, const uint8_t* pool_idx, float* dz, hipStream_t st) {
+  const int C = v.C;
+  const int64_t blocks4 = (int64_t)v.B * ((v.Ho + 1) / 2) * ((v.Wo + 1) / 2);
+  const int nb = v.red_blocks(blocks4);
+  const int Hp = (v.Ho + 2 - 3) / 2 + 1, Wp = (v.Wo + 2 - 3) / 2 + 1;
+  hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(nb), dim3(256), 0, st, v.Z, dpool, pool_idx, v.bn.mean, v.bn.invstd, v.bn.scale,
+                     v.bn.shift, v.B, v.Ho, v.Wo, C, Hp, Wp, v.partial);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, v.partial, nb, C, (double)v.rows, v.gamma,
+                     v.bn.mean, v.bn.invstd, v.dgamma, v.dbeta, v.bn.k0, v.bn.k1, v.bn.k2);
+  hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(grid_for(blocks4 * C / 4)), dim3(256), 0, st, v.Z, dpool, pool_idx, v.bn.k0, v.bn.k1,
+                     v.bn.k2, v.bn.scale, v.bn.shift, dz, v.B, v.Ho, v.Wo, C, Hp, Wp);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
-// dW of one conv from its input x and output gradient dz; `wgrad_slabs` holds WGRAD3_WGS * 64*64*9 floats.  `force_pertap`
+// dW (`dw_out`) of one conv from its input x and output gradient dz; `wgrad_slabs` holds WGRAD3_WGS * 64*64*9 floats.  `force_pertap`
 // routes a 3x3 layer through the per-tap kernel (the path of layers whose rows do not fit the fused kernel; test hook).
-int tr_wgrad_raw(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const TrainConv& tc, const float* x, const float* dz, int B,
-                 hipStream_t st, bool force_pertap);
-int tr_wgrad(dh_resnet18* net, const ConvLayer& c, const TrainConv& tc, const float* x, const float* dz, int B, hipStream_t st) {
-  dh_train* t = net->train;
-  return tr_wgrad_raw(t->wgrad_slabs, t->G + t->slot[c.name + ".weight"].first, c, tc, x, dz, B, st, false);
-}
-int tr_wgrad_raw(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const TrainConv& tc, const float* x, const float* dz, int B,
-                 hipStream_t st, bool force_pertap) {
-  struct { float* wgrad_slabs; } tt{wgrad_slabs};
-  auto* t = &tt;
+int tr_wgrad(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const TrainConv& tc, const float* x, const float* dz, int B,
+             hipStream_t st, bool force_pertap = false) {
   WgradParams p;
   p.dz = dz; p.x = x; p.slabs = nullptr;
   p.B = B; p.Hi = tc.Hi; p.Wi = tc.Wi; p.Cin = c.cin; p.Ho = tc.Ho; p.Wo = tc.Wo; p.Cout = c.cout;
@@ -1399,7 +1353,7 @@ int tr_wgrad_raw(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const Tr
   // fused 9-tap kernel when one output row's window fits its staging plan (else the per-tap kernel below)
   if (!force_pertap && c.ks == 3 && tc.Wo <= 64 && 3 * ((tc.Wo - 1) * c.stride + 3) * 16 <= WG3_MAXX * 512) {
     Wgrad3Params q;
-    q.dz = dz; q.x = x; q.slabs = t->wgrad_slabs;
+    q.dz = dz; q.x = x; q.slabs = wgrad_slabs;
     q.B = B; q.Hi = tc.Hi; q.Wi = tc.Wi; q.Cin = c.cin; q.Ho = tc.Ho; q.Wo = tc.Wo; q.Cout = c.cout; q.STRIDE = c.stride;
     const int combos3 = (c.cout / 64) * (c.cin / 64);
     const int XC = (tc.Wo - 1) * c.stride + 3;   // staged window columns (halo included)
@@ -1427,7 +1381,7 @@ int tr_wgrad_raw(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const Tr
     if (int arc = ensure_dyn_lds(reinterpret_cast<const void*>(&wgrad3_kernel), 160 * 1024)) return arc;
     if (!(DH_T1_ABL & 1)) hipLaunchKernelGGL(wgrad3_kernel, dim3(n_slabs * combos3), dim3(512), lds, st, q);
     const int64_t npairs = (int64_t)c.cout * c.cin;
-    if (!(DH_T1_ABL & 2)) hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)((npairs / 4 + 31) / 32), 9), dim3(256), 0, st, t->wgrad_slabs, n_slabs, npairs, dw_out);
+    if (!(DH_T1_ABL & 2)) hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)((npairs / 4 + 31) / 32), 9), dim3(256), 0, st, wgrad_slabs, n_slabs, npairs, dw_out);
     DH_LAUNCH_CHECK();
     return DH_OK;
   }
@@ -1440,12 +1394,36 @@ int tr_wgrad_raw(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const Tr
   p.pairs_per_slab = (int)(((pairs + n_slabs - 1) / n_slabs + 15) / 16 * 16);  // whole 32-pixel chunks
   n_slabs = (int)((pairs + p.pairs_per_slab - 1) / p.pairs_per_slab);
   p.n_slabs = n_slabs;
-  p.slabs = t->wgrad_slabs;
+  p.slabs = wgrad_slabs;
   hipLaunchKernelGGL(wgrad_kernel, dim3(n_slabs * combos), dim3(256), 0, st, p);
   const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nw / 4 + 31) / 32)), dim3(256), 0, st, t->wgrad_slabs, n_slabs, nw, dw_out);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nw / 4 + 31) / 32)), dim3(256), 0, st, wgrad_slabs, n_slabs, nw, dw_out);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+
+// first train_begin: the block table from the handle's convolution list (conv1, conv2 and, where the next entry is a 1x1, its downsample),
+// the arena layout in forward order, and the completion items of the backward pass: fc, the blocks last to first, the stem -- each
+// runs from its first tensor down to where the previous item started
+void tr_layout(dh_resnet18* net) {
+  dh_train* t = net->train;
+  const int nconv = (int)net->convs.size();
+  for (int i = 1; i + 1 < nconv;) {
+    const int ds = i + 2 < nconv && net->convs[i + 2].ks == 1 ? i + 2 : -1;
+    t->blocks.push_back({i, i + 1, ds, 0, 0});
+    i += ds < 0 ? 2 : 3;
+  }
+  for (const auto& c : net->convs) {
+    store_add(*t, c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
+    store_add(*t, c.bn + ".weight", c.cout); store_add(*t, c.bn + ".bias", c.cout);
+    store_radd(*t, c.bn + ".running_mean", c.cout); store_radd(*t, c.bn + ".running_var", c.cout);
+  }
+  store_add(*t, "fc.weight", (int64_t)net->n_classes * 512); store_add(*t, "fc.bias", net->n_classes);
+  int64_t end = t->n_params;
+  auto item_from = [&](int64_t start) { t->items.push_back({start, end - start}); end = start; };
+  item_from(t->slot["fc.weight"].first);
+  for (auto b = t->blocks.rbegin(); b != t->blocks.rend(); ++b) item_from(t->slot[net->convs[b->c1].name + ".weight"].first);
+  item_from(0);
 }
 
 }  // namespace
@@ -1468,30 +1446,9 @@ extern "C" int dh_resnet18_train_begin(dh_resnet18* net, int64_t n, int32_t P, v
     // a train-mode forward at another size) keeps the optimizer state and re-makes only the activations below.
     t = new dh_train();
     net->train = t;
-    if (dh::env_int("DH_T1_SIDE") != 0) {
-      int pr_lo = 0, pr_hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-      if (pr_lo == pr_hi || hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, pr_lo) != hipSuccess) {
-        (void)hipGetLastError();   // the failed attempt's error is sticky: without this the next DH_LAUNCH_CHECK reports it as a launch failure
-        DH_HIP(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));   // (no priorities on this device: a plain stream)
-      }
-      DH_HIP(hipEventCreateWithFlags(&t->ev_dz, hipEventDisableTiming));
-      DH_HIP(hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming));
-    }
-    int64_t off = 0, roff = 0;
-    auto add = [&](const std::string& k, int64_t cnt) { t->slot[k] = {off, cnt}; off += (cnt + 3) & ~(int64_t)3; };
-    auto radd = [&](const std::string& k, int64_t cnt) { t->rslot[k] = {roff, cnt}; roff += (cnt + 3) & ~(int64_t)3; };
-    for (const auto& c : net->convs) {
-      add(c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
-      add(c.bn + ".weight", c.cout); add(c.bn + ".bias", c.cout);
-      radd(c.bn + ".running_mean", c.cout); radd(c.bn + ".running_var", c.cout);
-    }
-    add("fc.weight", (int64_t)net->n_classes * 512); add("fc.bias", net->n_classes);
-    t->n_params = off; t->n_running = roff;
-    if ((rc = tr_alloc(t, &t->Pm, off)) || (rc = tr_alloc(t, &t->G, off)) || (rc = tr_alloc(t, &t->M, off)) ||
-        (rc = tr_alloc(t, &t->V, off)) || (rc = tr_alloc(t, &t->R, roff))) return rc;
-    DH_HIP(hipMemsetAsync(t->Pm, 0, off * 4, st)); DH_HIP(hipMemsetAsync(t->G, 0, off * 4, st));
-    DH_HIP(hipMemsetAsync(t->M, 0, off * 4, st)); DH_HIP(hipMemsetAsync(t->V, 0, off * 4, st));
+    if (dh::env_int("DH_T1_SIDE") != 0 && (rc = store_open_side(*t))) return rc;
+    tr_layout(net);
+    if ((rc = store_alloc_arenas(*t, st))) return rc;
     for (const auto& kv : t->slot) {
       auto it = net->params.find(kv.first);
       DH_REQUIRE(it != net->params.end(), "train begin: parameter '%s' was never set", kv.first.c_str());
@@ -1503,59 +1460,53 @@ extern "C" int dh_resnet18_train_begin(dh_resnet18* net, int64_t n, int32_t P, v
       DH_HIP(hipMemcpyAsync(t->R + kv.second.first, it->second.data(), kv.second.second * 4, hipMemcpyHostToDevice, st));
     }
     t->tc.resize(net->convs.size());
-    if ((rc = tr_alloc(t, &t->ones, 512)) || (rc = tr_alloc(t, &t->zeros, 512)) ||
-        (rc = tr_alloc(t, &t->partial, (int64_t)RED_NB * 2 * 512)) ||
-        (rc = tr_alloc(t, &t->stem_slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160)) ||
-        (rc = tr_alloc(t, &t->wgrad_slabs, (int64_t)WGRAD3_WGS * 64 * 64 * 9))) return rc;
+    if ((rc = store_alloc(*t, &t->ones, 512)) || (rc = store_alloc(*t, &t->zeros, 512)) ||
+        (rc = store_alloc(*t, &t->partial, (int64_t)RED_NB * 2 * 512)) ||
+        (rc = store_alloc(*t, &t->stem_slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160)) ||
+        (rc = store_alloc(*t, &t->wgrad_slabs, (int64_t)WGRAD3_WGS * 64 * 64 * 9))) return rc;
     hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, t->ones, (int64_t)512, 1.0f);
     DH_HIP(hipMemsetAsync(t->zeros, 0, 512 * 4, st));
     for (size_t i = 0; i < net->convs.size(); ++i) {
       const ConvLayer& c = net->convs[i];
       TrainConv& tc = t->tc[i];
       const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;
-      if (i == 0) { if ((rc = tr_alloc(t, &tc.wp_f, 7 * 11 * 2 * 64))) return rc; }
-      else { if ((rc = tr_alloc(t, &tc.wp_f, nw)) || (rc = tr_alloc(t, &tc.wp_d, nw))) return rc; }
+      if (i == 0) { if ((rc = store_alloc(*t, &tc.wp_f, 7 * 11 * 2 * 64))) return rc; }
+      else { if ((rc = store_alloc(*t, &tc.wp_f, nw)) || (rc = store_alloc(*t, &tc.wp_d, nw))) return rc; }
       float** bb[7] = {&tc.bn.mean, &tc.bn.invstd, &tc.bn.scale, &tc.bn.shift, &tc.bn.k0, &tc.bn.k1, &tc.bn.k2};
-      for (auto q : bb) if ((rc = tr_alloc(t, q, c.cout))) return rc;
+      for (auto q : bb) if ((rc = store_alloc(*t, q, c.cout))) return rc;
     }
     if ((rc = tr_pack_all(net, st))) return rc;
   } else {
-    // ---- batch shape changed: drop the (B, P)-sized buffers only (hipFree waits for work that still uses them)
-    for (void* q : t->shape_allocs) (void)hipFree(q);
-    t->shape_allocs.clear();
+    store_free_shape(*t);   // batch shape changed: drop the (B, P)-sized buffers only
   }
   t->B = B; t->P = P;
   // ---- activations and workspaces of this batch shape
   t->shape_phase = true;
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
-  int H = H2;
-  size_t ci = 1;
   auto setup = [&](size_t i, int hi, int ho) -> int {
     const ConvLayer& c = net->convs[i];
     TrainConv& tc = t->tc[i];
     tc.Hi = tc.Wi = hi; tc.Ho = tc.Wo = ho;
     const int64_t nout = (int64_t)B * ho * ho * c.cout;
     int r;
-    if ((r = tr_alloc(t, &tc.Z, nout)) || (r = tr_alloc(t, &tc.Y, nout))) return r;
-    if (t->side && i > 0 && (r = tr_alloc(t, &tc.dZ, nout))) return r;
+    if ((r = store_alloc(*t, &tc.Z, nout)) || (r = store_alloc(*t, &tc.Y, nout))) return r;
+    if (t->side && i > 0 && (r = store_alloc(*t, &tc.dZ, nout))) return r;
     return DH_OK;
   };
   auto shape_done = [&](int r) { t->shape_phase = false; return r; };
   if ((rc = setup(0, P, H1))) return shape_done(rc);
-  for (int s = 0; s < 4; ++s)
-    for (int blk = 0; blk < 2; ++blk) {
-      const bool ds = (blk == 0 && s > 0);
-      const int Ho = ds ? H / 2 : H;
-      if ((rc = setup(ci, H, Ho)) || (rc = setup(ci + 1, Ho, Ho))) return shape_done(rc);
-      if (ds && (rc = setup(ci + 2, H, Ho))) return shape_done(rc);
-      H = Ho; ci += ds ? 3 : 2;
-    }
+  int H = H2;
+  for (TrBlock& b : t->blocks) {
+    b.hi = H; b.ho = H / net->convs[b.c1].stride;
+    if ((rc = setup(b.c1, b.hi, b.ho)) || (rc = setup(b.c2, b.ho, b.ho))) return shape_done(rc);
+    if (b.ds >= 0 && (rc = setup(b.ds, b.hi, b.ho))) return shape_done(rc);
+    H = b.ho;
+  }
   const int64_t S1 = (int64_t)B * H2 * H2 * 64;
-  if ((rc = tr_alloc(t, &t->X1, S1)) || (rc = tr_alloc(t, reinterpret_cast<float**>(&t->pool_idx), (S1 + 3) / 4)) ||
-      (rc = tr_alloc(t, &t->pooled, (int64_t)B * 512)) ||
-      (rc = tr_alloc(t, &t->dlogits_fc, (int64_t)B * net->n_classes)) ||
-      (rc = tr_alloc(t, &t->BIG1, 4 * S1))) return shape_done(rc);
-  for (int i = 0; i < 4; ++i) if ((rc = tr_alloc(t, &t->SM[i], S1))) return shape_done(rc);
+  if ((rc = store_alloc(*t, &t->X1, S1)) || (rc = store_alloc(*t, &t->pool_idx, S1)) ||
+      (rc = store_alloc(*t, &t->pooled, (int64_t)B * 512)) ||
+      (rc = store_alloc(*t, &t->BIG1, 4 * S1))) return shape_done(rc);
+  for (int i = 0; i < 4; ++i) if ((rc = store_alloc(*t, &t->SM[i], S1))) return shape_done(rc);
   return shape_done(DH_OK);
 }
 
@@ -1575,10 +1526,7 @@ extern "C" int dh_resnet18_train_end(dh_resnet18* net) {
     v.resize(kv.second.second);
     DH_HIP(hipMemcpy(v.data(), t->R + kv.second.first, kv.second.second * 4, hipMemcpyDeviceToHost));
   }
-  for (void* p : t->allocs) (void)hipFree(p);
-  for (void* p : t->shape_allocs) (void)hipFree(p);
-  for (hipEvent_t e : {t->ev_dz, t->ev_join}) if (e) (void)hipEventDestroy(e);
-  if (t->side) (void)hipStreamDestroy(t->side);
+  store_free_all(*t);
   delete t;
   net->train = nullptr;
   return dh_resnet18_finalize(net, nullptr);
@@ -1591,6 +1539,7 @@ extern "C" int dh_resnet18_forward_train(dh_resnet18* net, const float* x, int64
   dh_train* t = net->train;
   hipStream_t st = dh::as_stream(stream);
   const int B = (int)n;
+  const UnitAffine u{t->ones, t->zeros};
   t->x_in = x;
   // stem: raw conv (unit scale, zero shift, no ReLU) -> batch-stat BN + ReLU -> maxpool
   {
@@ -1604,31 +1553,27 @@ extern "C" int dh_resnet18_forward_train(dh_resnet18* net, const float* x, int64
     if (int arc = ensure_dyn_lds(reinterpret_cast<const void*>(&stem_kernel<float, false>), 96 * 1024)) return arc;
     hipLaunchKernelGGL((stem_kernel<float, false>), dim3(B * sp.tiles_y * sp.tiles_x), dim3(256), lds, st, sp);
     DH_LAUNCH_CHECK();
-    if ((rc = tr_bn_forward(net, net->convs[0], tc, nullptr, true, B, st, t->X1, t->pool_idx))) return rc;   // + ReLU + maxpool in the same pass
+    if ((rc = tr_bn_forward(tr_bn_view(net, 0), nullptr, true, nullptr, st, t->X1, t->pool_idx))) return rc;   // + ReLU + maxpool in the same pass
   }
   const float* X = t->X1;
-  size_t ci = 1;
-  for (int s = 0; s < 4; ++s)
-    for (int blk = 0; blk < 2; ++blk) {
-      const bool ds = (blk == 0 && s > 0);
-      const ConvLayer &c1 = net->convs[ci], &c2 = net->convs[ci + 1];
-      TrainConv &t1 = t->tc[ci], &t2 = t->tc[ci + 1];
-      if ((rc = tr_conv(net, c1.cin, c1.cout, 3, c1.stride, t1.wp_f, X, nullptr, t1.Z, B, t1.Hi, t1.Wi, st))) return rc;
-      if ((rc = tr_bn_forward(net, c1, t1, nullptr, true, B, st))) return rc;
-      const float* idt = X;
-      if (ds) {
-        const ConvLayer& cd = net->convs[ci + 2];
-        TrainConv& td = t->tc[ci + 2];
-        if ((rc = tr_conv(net, cd.cin, cd.cout, 1, 2, t->Pm + t->slot[cd.name + ".weight"].first, X, nullptr, td.Z, B, td.Hi, td.Wi, st))) return rc;
-        if ((rc = tr_bn_forward(net, cd, td, nullptr, false, B, st))) return rc;
-        idt = td.Y;
-      }
-      if ((rc = tr_conv(net, c2.cin, c2.cout, 3, 1, t2.wp_f, t1.Y, nullptr, t2.Z, B, t2.Hi, t2.Wi, st))) return rc;
-      if ((rc = tr_bn_forward(net, c2, t2, idt, true, B, st))) return rc;
-      X = t2.Y;
-      ci += ds ? 3 : 2;
+  for (const TrBlock& b : t->blocks) {
+    const ConvLayer &c1 = net->convs[b.c1], &c2 = net->convs[b.c2];
+    TrainConv &t1 = t->tc[b.c1], &t2 = t->tc[b.c2];
+    if ((rc = tr_conv(u, c1.cin, c1.cout, 3, c1.stride, t1.wp_f, X, nullptr, t1.Z, B, t1.Hi, t1.Wi, st))) return rc;
+    if ((rc = tr_bn_forward(tr_bn_view(net, b.c1), nullptr, true, t1.Y, st))) return rc;
+    const float* idt = X;
+    if (b.ds >= 0) {
+      const ConvLayer& cd = net->convs[b.ds];
+      TrainConv& td = t->tc[b.ds];
+      if ((rc = tr_conv(u, cd.cin, cd.cout, 1, 2, t->Pm + t->slot[cd.name + ".weight"].first, X, nullptr, td.Z, B, td.Hi, td.Wi, st))) return rc;
+      if ((rc = tr_bn_forward(tr_bn_view(net, b.ds), nullptr, false, td.Y, st))) return rc;
+      idt = td.Y;
     }
-  const TrainConv& l4 = t->tc[net->convs.size() - 1];  // layer4.1.conv2 (the last block has no downsample)
+    if ((rc = tr_conv(u, c2.cin, c2.cout, 3, 1, t2.wp_f, t1.Y, nullptr, t2.Z, B, t2.Hi, t2.Wi, st))) return rc;
+    if ((rc = tr_bn_forward(tr_bn_view(net, b.c2), idt, true, t2.Y, st))) return rc;
+    X = t2.Y;
+  }
+  const TrainConv& l4 = t->tc[t->blocks.back().c2];
   const int HW = l4.Ho * l4.Wo;
   hipLaunchKernelGGL(avgpool_kernel, dim3(B), dim3(256), 0, st, X, HW, 512, t->pooled);
   const float* fw = t->Pm + t->slot["fc.weight"].first;
@@ -1636,59 +1581,45 @@ extern "C" int dh_resnet18_forward_train(dh_resnet18* net, const float* x, int64
   hipLaunchKernelGGL(fc_fwd_kernel, dim3((B * net->n_classes + 3) / 4), dim3(256), 0, st, t->pooled, fw, fb, B, 512,
                      net->n_classes, logits);
   DH_LAUNCH_CHECK();
-  t->tracked += 1;
   return DH_OK;
 }
 
 namespace {
-struct AdamArgsF { float lr, beta1, beta2, eps, bc1, bc2s; };
-void tr_adam_range(dh_train* t, const AdamArgsF& a, int64_t off, int64_t n, hipStream_t st) {
-  if (n <= 0) return;
-  if (!(DH_T1_ABL & 8)) hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, st, t->Pm + off, t->G + off, t->M + off, t->V + off, n, a.lr, a.beta1, a.beta2,
-                     a.eps, a.bc1, a.bc2s);
-}
-
 // `fused` (single-rank training): the Adam update and the repack of a block's tensors follow that block's weight gradients on the side
 // stream, instead of one update of the whole arena after the pass (same arithmetic per element: identical parameters).
-int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const AdamArgsF* fused) {
+int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const AdamArgs* fused) {
   dh_train* t = net->train;
   const int B = t->B, ncls = net->n_classes;
+  const UnitAffine u{t->ones, t->zeros};
   int rc;
-  size_t next_bucket = 0;
-  auto mark_done = [&](int64_t done_from) {   // every gradient at arena offsets >= done_from has been enqueued
-    while (next_bucket < t->buckets.size() && t->buckets[next_bucket].first >= done_from) {
-      if (t->bucket_cb) t->bucket_cb((int32_t)next_bucket, t->buckets[next_bucket].first, t->buckets[next_bucket].second, t->bucket_user);
-      ++next_bucket;
-    }
-  };
-  // side-stream weight gradients (see dh_train2_backward for the scheme): queued per block behind one event of the main stream
+  store_begin_backward(*t);
+  auto grad_of = [&](const ConvLayer& c) { return t->G + t->slot[c.name + ".weight"].first; };
+  // side-stream weight gradients (see t2_backward for the scheme): queued per block behind one event of the main stream
   const bool side = t->side != nullptr;
   struct PendingW { const ConvLayer* c; const TrainConv* tc; const float* x; const float* dz; };
   std::vector<PendingW> pending;
   auto wgrad_of = [&](const ConvLayer& c, const TrainConv& tc, const float* x, const float* dz) -> int {
-    if (!side) return tr_wgrad(net, c, tc, x, dz, B, st);
+    if (!side) return tr_wgrad(t->wgrad_slabs, grad_of(c), c, tc, x, dz, B, st);
     pending.push_back({&c, &tc, x, dz});
     return DH_OK;
   };
   int64_t adam_end = t->n_params;   // fused optimiser: the arena from here on has been updated (it completes from the end)
   auto flush_side = [&]() -> int {
     if (pending.empty()) return DH_OK;
-    DH_HIP(hipEventRecord(t->ev_dz, st));
-    DH_HIP(hipStreamWaitEvent(t->side, t->ev_dz, 0));
+    int r = side_handoff(*t, st);
+    if (r) return r;
     int lo = (int)net->convs.size(), hi = -1;
     for (const PendingW& w : pending) {
-      int r = tr_wgrad(net, *w.c, *w.tc, w.x, w.dz, B, t->side);
-      if (r) return r;
+      if ((r = tr_wgrad(t->wgrad_slabs, grad_of(*w.c), *w.c, *w.tc, w.x, w.dz, B, t->side))) return r;
       const int ci = (int)(w.c - net->convs.data());
       lo = std::min(lo, ci); hi = std::max(hi, ci);
     }
     if (fused) {   // the block's tensors start at its first conv (arena = forward order); everything behind them is complete too
       const int64_t from = t->slot[net->convs[lo].name + ".weight"].first;
       DH_REQUIRE(hi - lo + 1 == (int)pending.size() && from < adam_end, "backward: the convolutions of a hand-off are not a contiguous range");
-      tr_adam_range(t, *fused, from, adam_end - from, t->side);
+      if (!(DH_T1_ABL & 8)) adam_range(*t, *fused, from, adam_end - from, t->side);
       adam_end = from;
-      int r = tr_pack(net, t->side, lo, hi + 1);
-      if (r) return r;
+      if ((r = tr_pack(net, t->side, lo, hi + 1))) return r;
     }
     pending.clear();
     return DH_OK;
@@ -1696,68 +1627,53 @@ int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const Ad
   auto join_side = [&]() -> int {
     if (!side) return DH_OK;
     int r = flush_side();
-    if (r) return r;
-    DH_HIP(hipEventRecord(t->ev_join, t->side));
-    DH_HIP(hipStreamWaitEvent(st, t->ev_join, 0));
-    return DH_OK;
+    return r ? r : side_join(*t, st);
   };
   // fc + avgpool
-  const size_t nconv = net->convs.size();
-  (void)ncls;
-  const TrainConv& l4 = t->tc[nconv - 1];
+  const TrainConv& l4 = t->tc[t->blocks.back().c2];
   const int HW4 = l4.Ho * l4.Wo;
   hipLaunchKernelGGL(fc_wgrad_kernel, dim3((ncls * 512 + 255) / 256), dim3(256), 0, st, dlogits, t->pooled, B, 512, ncls,
                      t->G + t->slot["fc.weight"].first, t->G + t->slot["fc.bias"].first);
   float* dOut = t->SM[0];
   hipLaunchKernelGGL(avgpool_fc_dgrad_kernel, dim3(B), dim3(256), 0, st, dlogits, t->Pm + t->slot["fc.weight"].first, HW4, 512, ncls, dOut);
   DH_LAUNCH_CHECK();
-  mark_done(t->slot["fc.weight"].first);
-  // residual blocks in reverse; block table (conv1, conv2, downsample or -1) in forward order
-  std::vector<std::array<int, 3>> blocks;
-  {
-    int i = 1;
-    for (int s = 0; s < 4; ++s)
-      for (int blk = 0; blk < 2; ++blk) {
-        const bool ds = (blk == 0 && s > 0);
-        blocks.push_back({i, i + 1, ds ? i + 2 : -1});
-        i += ds ? 3 : 2;
-      }
-  }
-  for (int b = (int)blocks.size() - 1; b >= 0; --b) {
-    const int i1 = blocks[b][0], i2 = blocks[b][1], id = blocks[b][2];
+  store_mark_done(*t);   // fc
+  // residual blocks in reverse
+  for (int b = (int)t->blocks.size() - 1; b >= 0; --b) {
+    const int i1 = t->blocks[b].c1, i2 = t->blocks[b].c2, id = t->blocks[b].ds;
     const ConvLayer &c1 = net->convs[i1], &c2 = net->convs[i2];
     TrainConv &t1 = t->tc[i1], &t2 = t->tc[i2];
-    const float* Xin = b == 0 ? t->X1 : t->tc[blocks[b - 1][1]].Y;
+    const float* Xin = b == 0 ? t->X1 : t->tc[t->blocks[b - 1].c2].Y;
     float* G2 = t->SM[1];   // masked gradient at the block output (flows to both branches)
     float* dZ2 = side ? t2.dZ : t->SM[2];
     const int64_t n2 = (int64_t)B * t2.Ho * t2.Wo * c2.cout;
     tr_dump("dOut", b, dOut, n2, st);
-    if ((rc = tr_bn_backward(net, c2, t2, dOut, t2.Y, true, dZ2, G2, B, st))) return rc;   // dOut is dead after this
+    if ((rc = tr_bn_backward(tr_bn_view(net, i2), dOut, t2.Y, true, dZ2, G2, st))) return rc;   // dOut is dead after this
     tr_dump("dZ2", b, dZ2, n2, st);
     if ((rc = wgrad_of(c2, t2, t1.Y, dZ2))) return rc;
     float* dY1 = t->SM[3];
-    if ((rc = tr_conv(net, c2.cout, c2.cin, 3, 1, t2.wp_d, dZ2, nullptr, dY1, B, t2.Ho, t2.Wo, st))) return rc;
+    if ((rc = tr_conv(u, c2.cout, c2.cin, 3, 1, t2.wp_d, dZ2, nullptr, dY1, B, t2.Ho, t2.Wo, st))) return rc;
     tr_dump("dY1", b, dY1, n2, st);
     float* dZ1 = side ? t1.dZ : t->SM[2];  // (single stream: dZ2 is dead now)
-    if ((rc = tr_bn_backward(net, c1, t1, dY1, nullptr, true, dZ1, nullptr, B, st))) return rc;   // ReLU pattern from Z
+    if ((rc = tr_bn_backward(tr_bn_view(net, i1), dY1, nullptr, true, dZ1, nullptr, st))) return rc;   // ReLU pattern from Z
     tr_dump("dZ1", b, dZ1, n2, st);
     if ((rc = wgrad_of(c1, t1, Xin, dZ1))) return rc;
     float* dX = t->SM[0];
     if (id < 0) {
       // dX = dgrad(conv1) + G2 (identity branch), fused as the conv's residual input
-      if ((rc = tr_conv(net, c1.cout, c1.cin, 3, 1, t1.wp_d, dZ1, G2, dX, B, t1.Ho, t1.Wo, st))) return rc;
+      if ((rc = tr_conv(u, c1.cout, c1.cin, 3, 1, t1.wp_d, dZ1, G2, dX, B, t1.Ho, t1.Wo, st))) return rc;
     } else {
       const ConvLayer& cd = net->convs[id];
       TrainConv& td = t->tc[id];
       // stride-2 data gradient: four parity-class launches over dZ1 itself (round 2 ran a stride-1 conv over a zero-upsampled
       // copy: four times the MFMA work and a 4x-sized tensor written and read)
-      if ((rc = tr_dgrad_s2(net, c1.cout, c1.cin, t1.wp_d, dZ1, nullptr, dX, B, t1.Ho, t1.Wo, t1.Hi, t1.Wi, st))) return rc;
+      if ((rc = tr_dgrad_s2(u, c1.cout, c1.cin, t1.wp_d, dZ1, nullptr, dX, B, t1.Ho, t1.Wo, t1.Hi, t1.Wi, st))) return rc;
       // downsample branch: BN (no ReLU) <- G2 ; 1x1 stride-2 conv
       float* dZd = side ? td.dZ : t->SM[3];  // (single stream: dY1 is dead)
-      if ((rc = tr_bn_backward(net, cd, td, G2, nullptr, false, dZd, nullptr, B, st))) return rc;
+      if ((rc = tr_bn_backward(tr_bn_view(net, id), G2, nullptr, false, dZd, nullptr, st))) return rc;
       if ((rc = wgrad_of(cd, td, Xin, dZd))) return rc;
       float* tt = side ? t->SM[3] : t->SM[2];   // dY1 (dZ1 on a single stream) is dead: [B, Ho, Wo, cin]
-      if ((rc = tr_conv(net, cd.cout, cd.cin, 1, 1, td.wp_d, dZd, nullptr, tt, B, td.Ho, td.Wo, st))) return rc;
+      if ((rc = tr_conv(u, cd.cout, cd.cin, 1, 1, td.wp_d, dZd, nullptr, tt, B, td.Ho, td.Wo, st))) return rc;
       const int64_t m4 = (int64_t)B * td.Ho * td.Wo * cd.cin / 4;
       hipLaunchKernelGGL(upsample2_add_kernel, dim3(grid_for(m4)), dim3(256), 0, st, tt, dX, B, td.Ho, td.Wo, cd.cin);
       DH_LAUNCH_CHECK();
@@ -1765,13 +1681,13 @@ int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const Ad
     dOut = dX;
     if (t->bucket_cb) { if ((rc = join_side())) return rc; }   // a bucket may complete here: its gradients precede the caller's event
     else if ((rc = flush_side())) return rc;
-    mark_done(t->slot[c1.name + ".weight"].first);   // the block's tensors start at its conv1 (arena = forward order)
+    store_mark_done(*t);   // the block
   }
   // stem: maxpool, BN+ReLU, wgrad
   {
     TrainConv& tc = t->tc[0];
     float* dZ0 = t->BIG1;
-    if ((rc = tr_bn_pool_backward(net, net->convs[0], tc, dOut, t->pool_idx, dZ0, B, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
+    if ((rc = tr_bn_pool_backward(tr_bn_view(net, 0), dOut, t->pool_idx, dZ0, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
     const int total_rows = B * tc.Ho;
     const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
     const int n_slabs = (total_rows + rpb - 1) / rpb;
@@ -1782,9 +1698,9 @@ int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const Ad
                        t->G + t->slot["conv1.weight"].first);
     DH_LAUNCH_CHECK();
     if ((rc = join_side())) return rc;   // the optimiser (and the last bucket) follow on the main stream
-    mark_done(0);
+    store_mark_done(*t);   // the stem
     if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
-      tr_adam_range(t, *fused, 0, adam_end, st);
+      if (!(DH_T1_ABL & 8)) adam_range(*t, *fused, 0, adam_end, st);
       if ((rc = tr_pack_stem(net, st))) return rc;
       if (adam_end == t->n_params && (rc = tr_pack(net, st, 1, (int)net->convs.size()))) return rc;
     }
@@ -1803,45 +1719,22 @@ extern "C" int dh_resnet18_backward(dh_resnet18* net, const float* dlogits, void
 extern "C" int dh_resnet18_backward_adam(dh_resnet18* net, const float* dlogits, float lr, float beta1, float beta2, float eps, int64_t step,
                                          void* stream) {
   DH_REQUIRE(net && net->train && dlogits, "backward: no training forward has run");
-  dh_train* t = net->train;
-  DH_REQUIRE(t->bucket_cb == nullptr, "backward_adam: gradient buckets are armed (data-parallel steps call backward and adam_step)");
-  if (step <= 0) step = t->adam_t + 1;
-  t->adam_t = step;
-  const AdamArgsF a{lr, beta1, beta2, eps, 1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step))};
+  DH_REQUIRE(net->train->bucket_cb == nullptr, "backward_adam: gradient buckets are armed (data-parallel steps call backward and adam_step)");
+  const AdamArgs a = adam_args(*net->train, lr, beta1, beta2, eps, step);
   return tr_backward(net, dlogits, dh::as_stream(stream), &a);
 }
 
-// Gradient buckets of the float32 engine (see dh_train2_set_buckets for the contract): buckets are cut from the END of
-// the forward-ordered arena, which is where the backward pass starts.  Needs a training state (call after a training forward).
+// Gradient buckets of the float32 engine (store_set_buckets has the contract): the arena is in forward order and the backward pass
+// completes it from the END, so bucket k is a suffix slice.  Needs a training state (call after a training forward).
 extern "C" int dh_resnet18_set_buckets(dh_resnet18* net, int64_t bucket_bytes, void (*cb)(int32_t, int64_t, int64_t, void*), void* user,
                                        int32_t* n_buckets_out) {
   DH_REQUIRE(net && net->train && bucket_bytes >= 0, "set buckets: no training state / bad arguments");
-  dh_train* t = net->train;
-  t->bucket_cb = cb; t->bucket_user = user;
-  // completion items: start offsets in completion order
-  std::vector<int64_t> starts;
-  starts.push_back(t->slot["fc.weight"].first);
-  std::vector<int64_t> block_starts;
-  for (size_t i = 1; i < net->convs.size(); ++i)
-    if (net->convs[i].name.find(".conv1") != std::string::npos) block_starts.push_back(t->slot[net->convs[i].name + ".weight"].first);
-  for (auto it = block_starts.rbegin(); it != block_starts.rend(); ++it) starts.push_back(*it);
-  starts.push_back(0);
-  t->buckets.clear();
-  int64_t end = t->n_params;
-  for (size_t i = 0; i < starts.size(); ++i) {
-    const bool last = i + 1 == starts.size();
-    if (last || (bucket_bytes > 0 && (end - starts[i]) * 4 >= bucket_bytes)) {
-      if (end > starts[i]) t->buckets.push_back({starts[i], end - starts[i]});
-      end = starts[i];
-    }
-  }
-  if (n_buckets_out) *n_buckets_out = (int32_t)t->buckets.size();
+  store_set_buckets(*net->train, bucket_bytes, cb, user, n_buckets_out);
   return DH_OK;
 }
 extern "C" int dh_resnet18_bucket(dh_resnet18* net, int32_t i, int64_t* offset, int64_t* count) {
-  DH_REQUIRE(net && net->train && offset && count && i >= 0 && (size_t)i < net->train->buckets.size(), "bucket: index out of range");
-  *offset = net->train->buckets[i].first; *count = net->train->buckets[i].second;
-  return DH_OK;
+  DH_REQUIRE(net && net->train, "bucket: index out of range");
+  return store_bucket(*net->train, "bucket", i, offset, count);
 }
 
 extern "C" int dh_ce_loss(const float* logits, const int64_t* labels, int64_t n, int32_t n_cls, float* loss_dev,
@@ -1856,33 +1749,16 @@ extern "C" int dh_resnet18_adam_step(dh_resnet18* net, float lr, float beta1, fl
   DH_REQUIRE(net && net->train, "adam step: no training state");
   dh_train* t = net->train;
   hipStream_t st = dh::as_stream(stream);
-  if (step <= 0) step = t->adam_t + 1;   // the library's own count (it survives batch-shape changes with the moments)
-  t->adam_t = step;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(t->n_params)), dim3(256), 0, st, t->Pm, t->G, t->M, t->V, t->n_params, lr, beta1,
-                     beta2, eps, bc1, bc2s);
+  adam_range(*t, adam_args(*t, lr, beta1, beta2, eps, step), 0, t->n_params, st);
   DH_LAUNCH_CHECK();
   return tr_pack_all(net, st);
 }
 
-// kind: 0 parameter, 1 gradient, 2 running statistic; to_lib != 0 copies caller -> library (then re-packs).
-// `ptr` may be host or device memory (hipMemcpyDefault).
+// store_tensor on the training state; the caller re-packs after pushing parameters (dh_resnet18_train_repack)
 extern "C" int dh_resnet18_train_tensor(dh_resnet18* net, const char* name, int32_t kind, void* ptr, int64_t n_elem,
                                         int32_t to_lib, void* stream) {
   DH_REQUIRE(net && net->train && name && ptr, "train tensor: no training state / null argument");
-  dh_train* t = net->train;
-  hipStream_t st = dh::as_stream(stream);
-  if (std::string(name).find("num_batches_tracked") != std::string::npos) return DH_OK;
-  float* base = kind == 0 ? t->Pm : kind == 1 ? t->G : t->R;
-  const auto& table = kind == 2 ? t->rslot : t->slot;
-  auto it = table.find(name);
-  DH_REQUIRE(it != table.end(), "train tensor: unknown tensor '%s' (kind %d)", name, kind);
-  DH_REQUIRE(it->second.second == n_elem, "train tensor: '%s' has %lld elements, got %lld", name,
-             (long long)it->second.second, (long long)n_elem);
-  if (to_lib) DH_HIP(hipMemcpyAsync(base + it->second.first, ptr, n_elem * 4, hipMemcpyDefault, st));
-  else DH_HIP(hipMemcpyAsync(ptr, base + it->second.first, n_elem * 4, hipMemcpyDefault, st));
-  return DH_OK;
+  return store_tensor(*net->train, "train tensor", name, kind, ptr, n_elem, to_lib, dh::as_stream(stream));
 }
 
 extern "C" int dh_resnet18_train_repack(dh_resnet18* net, void* stream) {
@@ -1890,13 +1766,9 @@ extern "C" int dh_resnet18_train_repack(dh_resnet18* net, void* stream) {
   return tr_pack_all(net, dh::as_stream(stream));
 }
 
-// Flat views of the training arenas (data-parallel training all-reduces the gradient arena in
-// place with RCCL): kind 0 parameters, 1 gradients, 2 running statistics.
 extern "C" int dh_resnet18_train_flat(dh_resnet18* net, int32_t kind, void** ptr_out, int64_t* n_out) {
   DH_REQUIRE(net && net->train && ptr_out && n_out && kind >= 0 && kind <= 2, "train flat: bad arguments / no training state");
-  dh_train* t = net->train;
-  *ptr_out = kind == 0 ? t->Pm : kind == 1 ? t->G : t->R;
-  *n_out = kind == 2 ? t->n_running : t->n_params;
+  store_flat(*net->train, kind, ptr_out, n_out);
   return DH_OK;
 }
 
@@ -1931,7 +1803,7 @@ extern "C" int dh_debug_wgrad_f32(const float* dz_dev, const float* x_dev, float
   ConvLayer c{"dbg", "dbg", cin, cout, ks, stride};
   TrainConv tc;
   tc.Hi = Hi; tc.Wi = Wi; tc.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; tc.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  if ((rc = tr_wgrad_raw(slabs, dw_dev, c, tc, x_dev, dz_dev, B, st, mode == 1))) return rc;
+  if ((rc = tr_wgrad(slabs, dw_dev, c, tc, x_dev, dz_dev, B, st, mode == 1))) return rc;
   return dbg_finish(st, "debug wgrad");
 }
 
@@ -1982,86 +1854,84 @@ extern "C" int dh_debug_dgrad_f32(const float* dz_dev, const float* w_dev, const
              "debug dgrad: bad arguments");
   hipStream_t st = dh::as_stream(stream);
   DbgScratch sc;
-  dh_resnet18 net;
-  dh_train tr;
-  net.train = &tr;
   const int Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1, Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
   const int64_t nw = (int64_t)cout * cin * ks * ks;
-  float *wp_d, *up;
+  float *wp_d, *ones, *zeros;
   int rc;
-  if ((rc = sc.get(&wp_d, nw)) || (rc = sc.get(&tr.ones, 512)) || (rc = sc.get(&tr.zeros, 512)) ||
-      (rc = sc.get(&up, (int64_t)B * Hi * Wi * std::max(cin, cout)))) { net.train = nullptr; return rc; }
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, tr.ones, (int64_t)512, 1.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, tr.zeros, (int64_t)512, 0.0f);
+  if ((rc = sc.get(&wp_d, nw)) || (rc = sc.get(&ones, 512)) || (rc = sc.get(&zeros, 512))) return rc;
+  const UnitAffine u{ones, zeros};
+  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, ones, (int64_t)512, 1.0f);
+  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, zeros, (int64_t)512, 0.0f);
   if (ks == 1) {   // the 1x1 data gradient is a GEMM over the transposed weights Wt[cin][cout] (what pack_all_f32_kernel keeps)
     PackDescF d{w_dev, wp_d, wp_d, cout, cin, 1, 0}, *dd;
-    if ((rc = sc.get(&dd, 1))) { net.train = nullptr; return rc; }
-    if (hipMemcpyAsync(dd, &d, sizeof d, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { net.train = nullptr; return DH_EHIP; }
+    if ((rc = sc.get(&dd, 1))) return rc;
+    if (hipMemcpyAsync(dd, &d, sizeof d, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return DH_EHIP;
     hipLaunchKernelGGL(pack_all_f32_kernel, dim3((unsigned)((nw + PACKF_PER_BLOCK - 1) / PACKF_PER_BLOCK)), dim3(256), 0, st, dd, 1, 0);
   } else {
     hipLaunchKernelGGL((pack_conv_dev_kernel<float, true>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, ks, wp_d);
   }
-  if (ks == 3 && stride == 1) rc = tr_conv(&net, cout, cin, 3, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
-  else if (ks == 3) {   // the path backward takes: the parity classes of dX over dZ itself
-    tr.BIG1 = up;
-    rc = tr_dgrad_s2(&net, cout, cin, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, Hi, Wi, st);
-    tr.BIG1 = nullptr;
-  } else if (stride == 1) rc = tr_conv(&net, cout, cin, 1, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
+  if (ks == 3 && stride == 1) rc = tr_conv(u, cout, cin, 3, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
+  else if (ks == 3) rc = tr_dgrad_s2(u, cout, cin, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, Hi, Wi, st);   // the parity classes of dX over dZ itself
+  else if (stride == 1) rc = tr_conv(u, cout, cin, 1, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
   else {   // 1x1 stride 2 (downsample branch): dx (+)= upsample(conv1x1(dz)); dx starts from res (or zero)
+    float* up;
+    if ((rc = sc.get(&up, (int64_t)B * Ho * Wo * cin))) return rc;
     const int64_t nx = (int64_t)B * Hi * Wi * cin;
     if (res_dev) (void)hipMemcpyAsync(dx_dev, res_dev, nx * 4, hipMemcpyDeviceToDevice, st);
     else (void)hipMemsetAsync(dx_dev, 0, nx * 4, st);
-    rc = tr_conv(&net, cout, cin, 1, 1, wp_d, dz_dev, nullptr, up, B, Ho, Wo, st);
+    rc = tr_conv(u, cout, cin, 1, 1, wp_d, dz_dev, nullptr, up, B, Ho, Wo, st);
     const int64_t m4 = (int64_t)B * Ho * Wo * cin / 4;
     if (!rc) hipLaunchKernelGGL(upsample2_add_kernel, dim3(grid_for(m4)), dim3(256), 0, st, up, dx_dev, B, Ho, Wo, cin);
   }
-  net.train = nullptr;   // `tr` is a stack object: keep ~dh_resnet18 / destroy paths away from it
   if (rc) return rc;
   DH_LAUNCH_CHECK();
   return dbg_finish(st, "debug dgrad");
 }
 
-// training-mode BN over NHWC rows: forward (batch statistics -> y = [relu](z*scale + shift [+ res])) and, when dy_dev is given,
-// backward (dz, optional masked gradient g, dgamma, dbeta).  stats_out (optional): [mean C | biased var C | run_mean C | run_var C]
-// after one update from running (0, 1).
+namespace {
+// a BnView over caller data: scratch per-channel buffers and reduction workspace, running statistics starting from (0, 1)
+int dbg_bn_view(DbgScratch& sc, hipStream_t st, const float* z, const float* gamma, const float* beta, float* dgamma, float* dbeta, int64_t rows,
+                int B, int Ho, int Wo, int C, BnView* v) {
+  float *partial, *buf;
+  int rc;
+  if ((rc = sc.get(&partial, (int64_t)RED_NB * 2 * 512)) || (rc = sc.get(&buf, 9 * (int64_t)C))) return rc;
+  *v = {z, gamma, beta, buf + 7 * C, buf + 8 * C, dgamma, dbeta,
+        BnBufs{buf, buf + C, buf + 2 * C, buf + 3 * C, buf + 4 * C, buf + 5 * C, buf + 6 * C}, rows, C, B, Ho, Wo, partial};
+  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, v->run_mean, (int64_t)C, 0.0f);
+  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, v->run_var, (int64_t)C, 1.0f);
+  return DH_OK;
+}
+}  // namespace
+
+// training-mode BN over NHWC rows through the engine's launch code (tr_bn_forward / tr_bn_backward): forward (batch statistics ->
+// y = [relu](z*scale + shift [+ res])) and, when dy_dev is given, backward (dz, optional masked gradient g, dgamma, dbeta).
+// relu: 0 none, 1 ReLU with the backward pattern read from y, 2 ReLU with the pattern recomputed from z (what the engine does for a BN
+// whose output goes straight into a ReLU: no residual, no masked gradient).  stats_out (optional): [mean C | invstd C | run_mean C |
+// run_var C] after one update from running (0, 1).
 extern "C" int dh_debug_bn_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* res_dev, int32_t relu,
                                float* y_dev, const float* dy_dev, float* dz_dev, float* g_dev, float* dgamma_dev, float* dbeta_dev,
                                float* stats_out_dev, int64_t rows, int32_t C, void* stream) {
   DH_REQUIRE(z_dev && gamma_dev && beta_dev && y_dev && rows > 0 && C % 4 == 0 && C <= 512 && 256 % (C / 4) == 0, "debug bn: bad arguments");
+  DH_REQUIRE(relu >= 0 && relu <= 2, "debug bn: relu=%d (0 none, 1 pattern from y, 2 pattern recomputed from z)", relu);
+  DH_REQUIRE(relu != 2 || (!res_dev && !g_dev), "debug bn: relu=2 (pattern recomputed from z) takes neither res_dev nor g_dev");
+  DH_REQUIRE(!dy_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn: backward outputs missing");
   hipStream_t st = dh::as_stream(stream);
   DbgScratch sc;
-  float *partial, *buf;
+  BnView v;
   int rc;
-  if ((rc = sc.get(&partial, (int64_t)RED_NB * 2 * 512)) || (rc = sc.get(&buf, 9 * (int64_t)C))) return rc;
-  float *mean = buf, *invstd = buf + C, *scale = buf + 2 * C, *shift = buf + 3 * C, *k0 = buf + 4 * C, *k1 = buf + 5 * C, *k2 = buf + 6 * C,
-        *rm = buf + 7 * C, *rv = buf + 8 * C;
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, rm, (int64_t)C, 0.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, rv, (int64_t)C, 1.0f);
-  const int rpi = 256 / (C / 4);
-  const int nb = (int)std::min<int64_t>(RED_NB, (rows + rpi - 1) / rpi);
-  // the statistics as tr_bn_forward takes them: one pass {sum z, sum z^2}, one finalize launch
-  hipLaunchKernelGGL((col_reduce_kernel<3>), dim3(nb), dim3(256), 0, st, z_dev, nullptr, nullptr, nullptr, nullptr, rows, C, 0, partial);
-  hipLaunchKernelGGL(bn_stat_finalize_onepass_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, partial, nb, C, (double)rows, mean, invstd,
-                     gamma_dev, beta_dev, scale, shift, rm, rv);
-  const int64_t n4 = rows * C / 4;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, z_dev, scale, shift, res_dev, y_dev, n4, C, relu);
-  if (dy_dev) {
-    DH_REQUIRE(dz_dev && dgamma_dev && dbeta_dev, "debug bn: backward outputs missing");
-    hipLaunchKernelGGL((col_reduce_kernel<2>), dim3(nb), dim3(256), 0, st, z_dev, dy_dev, y_dev, mean, invstd, rows, C, relu, partial);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, partial, nb, C, (double)rows, gamma_dev, mean, invstd,
-                       dgamma_dev, dbeta_dev, k0, k1, k2);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(n4)), dim3(256), 0, st, dy_dev, y_dev, z_dev, k0, k1, k2, dz_dev, g_dev, n4, C, relu);
-  }
+  if ((rc = dbg_bn_view(sc, st, z_dev, gamma_dev, beta_dev, dgamma_dev, dbeta_dev, rows, 0, 0, 0, C, &v))) return rc;
+  if ((rc = tr_bn_forward(v, res_dev, relu != 0, y_dev, st))) return rc;
+  if (dy_dev && (rc = tr_bn_backward(v, dy_dev, relu == 1 ? y_dev : nullptr, relu != 0, dz_dev, g_dev, st))) return rc;
   if (stats_out_dev) {
-    (void)hipMemcpyAsync(stats_out_dev, mean, C * 4, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(stats_out_dev + C, invstd, C * 4, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(stats_out_dev + 2 * C, rm, 2 * (size_t)C * 4, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(stats_out_dev, v.bn.mean, C * 4, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(stats_out_dev + C, v.bn.invstd, C * 4, hipMemcpyDeviceToDevice, st);
+    (void)hipMemcpyAsync(stats_out_dev + 2 * C, v.run_mean, 2 * (size_t)C * 4, hipMemcpyDeviceToDevice, st);
   }
   DH_LAUNCH_CHECK();
   return dbg_finish(st, "debug bn");
 }
 
-// The stem's fused tail of the float32 engine on caller data (the launches of tr_bn_forward with a pooled target and of
+// The stem's fused tail of the float32 engine on caller data, through the engine's launch code (tr_bn_forward with a pooled target,
 // tr_bn_pool_backward): pooled [B][Hp][Wp][C] = maxpool3x3/2(relu(bn(z))) with batch statistics + first-maximum positions (uint8), and,
 // when dpool_dev is given, dz [B][Hi][Wi][C], dgamma, dbeta with the maxpool's gradient gathered inside the BN backward passes.
 extern "C" int dh_debug_bn_pool_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, float* pooled_dev, uint8_t* idx_dev,
@@ -2072,33 +1942,11 @@ extern "C" int dh_debug_bn_pool_f32(const float* z_dev, const float* gamma_dev, 
   DH_REQUIRE(!dpool_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn pool: backward outputs missing");
   hipStream_t st = dh::as_stream(stream);
   DbgScratch sc;
-  float *partial, *buf;
+  BnView v;
   int rc;
-  if ((rc = sc.get(&partial, (int64_t)RED_NB * 2 * 512)) || (rc = sc.get(&buf, 9 * (int64_t)C))) return rc;
-  float *mean = buf, *invstd = buf + C, *scale = buf + 2 * C, *shift = buf + 3 * C, *k0 = buf + 4 * C, *k1 = buf + 5 * C, *k2 = buf + 6 * C,
-        *rm = buf + 7 * C, *rv = buf + 8 * C;
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, rm, (int64_t)C, 0.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, rv, (int64_t)C, 1.0f);
-  const int64_t rows = (int64_t)B * Hi * Wi;
-  const int rpi = 256 / (C / 4);
-  const int nb = (int)std::min<int64_t>(RED_NB, (rows + rpi - 1) / rpi);
-  const int Hp = (Hi + 2 - 3) / 2 + 1, Wp = (Wi + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL((col_reduce_kernel<3>), dim3(nb), dim3(256), 0, st, z_dev, nullptr, nullptr, nullptr, nullptr, rows, C, 0, partial);
-  hipLaunchKernelGGL(bn_stat_finalize_onepass_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, partial, nb, C, (double)rows, mean, invstd,
-                     gamma_dev, beta_dev, scale, shift, rm, rv);
-  hipLaunchKernelGGL(bn_apply_pool_kernel, dim3(grid_for((int64_t)B * Hp * Wp * (C / 4))), dim3(256), 0, st, z_dev, scale, shift, pooled_dev, idx_dev,
-                     B, Hi, Wi, C, Hp, Wp);
-  if (dpool_dev) {
-    const int64_t blocks4 = (int64_t)B * ((Hi + 1) / 2) * ((Wi + 1) / 2);
-    const int nb2 = (int)std::min<int64_t>(RED_NB, (blocks4 + rpi - 1) / rpi);
-    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(nb2), dim3(256), 0, st, z_dev, dpool_dev, idx_dev, mean, invstd, scale, shift, B, Hi, Wi, C, Hp,
-                       Wp, partial);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, partial, nb2, C, (double)rows, gamma_dev, mean, invstd,
-                       dgamma_dev, dbeta_dev, k0, k1, k2);
-    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(grid_for(blocks4 * C / 4)), dim3(256), 0, st, z_dev, dpool_dev, idx_dev, k0, k1, k2, scale, shift,
-                       dz_dev, B, Hi, Wi, C, Hp, Wp);
-  }
-  DH_LAUNCH_CHECK();
+  if ((rc = dbg_bn_view(sc, st, z_dev, gamma_dev, beta_dev, dgamma_dev, dbeta_dev, (int64_t)B * Hi * Wi, B, Hi, Wi, C, &v))) return rc;
+  if ((rc = tr_bn_forward(v, nullptr, true, nullptr, st, pooled_dev, idx_dev))) return rc;
+  if (dpool_dev && (rc = tr_bn_pool_backward(v, dpool_dev, idx_dev, dz_dev, st))) return rc;
   return dbg_finish(st, "debug bn pool");
 }
 

@@ -17,7 +17,8 @@
 // transposed (1x1) / flipped-transposed (3x3) weights, wgrad = pixel-reduction GEMM through transposed LDS reads.
 // The parameter arenas (masters Pm, gradients G, Adam moments M / V) are laid out in BACKWARD order (fc first, stem
 // last): gradient buckets complete front to back while the backward pass runs, which is what the bucketed, overlapped
-// data-parallel all-reduce needs (dh_train2_set_bucket_callback).
+// data-parallel all-reduce needs (dh_train2_set_buckets).  The parameter store, the buckets, the Adam launch and the side
+// stream's hand-off are train_core.inc's, shared with the float32 engine.
 #include <type_traits>
 
 struct T2Conv {
@@ -34,30 +35,18 @@ struct T2Conv {
 };
 struct T2Block { int conv[3] = {-1, -1, -1}; int nconv = 0; int ds = -1; };
 
-typedef void (*dh_bucket_cb)(int32_t bucket, int64_t offset, int64_t count, void* user);
-
-struct dh_train2 {
+struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order: every completion item is one convolution (or fc)
   std::string arch;
-  int n_classes = 0, feat = 0, dev = 0;
+  int n_classes = 0, feat = 0;
   std::vector<T2Conv> convs;     // index 0 = stem
   std::vector<T2Block> blocks;
-  std::map<std::string, std::pair<int64_t, int64_t>> slot, rslot;
-  std::vector<std::pair<int64_t, int>> order;   // (arena offset after this item, conv index or -1 for fc): completion order of the backward pass
-  int64_t n_params = 0, n_running = 0;
-  float *Pm = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *R = nullptr;
   float *ones = nullptr, *zeros = nullptr, *partial = nullptr;
-  std::vector<void*> allocs, shape_allocs;
-  bool shape_phase = false;
   int B = 0, P = 0;
   bf16_t* X1 = nullptr;          // pooled stem output = input of the first block
   uint8_t* pool_idx = nullptr;
   float *pooled = nullptr;
   bf16_t* GB[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // gradient ping-pong buffers (largest activation each)
-  // weight gradients beside the dgrad / BN-backward chain (ResNet-50): a second stream, the dZ buffer alternates between two, and
-  // an event per buffer says when the weight-gradient kernels that read it are done
-  hipStream_t side = nullptr;
-  hipEvent_t ev_dz = nullptr, ev_join = nullptr;
-  bool side_wgrad = false;
+  bool side_wgrad = false;  // weight gradients beside the dgrad / BN-backward chain, on TrainStore::side; every convolution owns its dZ buffer
   bool fold = true;         // small maps: the BN apply passes add the partial rows themselves, no finalize launch (bn_fold.inc; DH_T2_FOLD=0 at create: A/B, tests)
   bool join_fused = true;   // the downsample branch's BN is applied inside the join BN's pass (DH_T2_JOIN=0 at create: it writes its own Y; A/B, tests)
   float* stem_slabs = nullptr;
@@ -69,11 +58,6 @@ struct dh_train2 {
   PackDesc* pack_desc = nullptr;   // device table of t2_pack_all (one launch packs every conv)
   int pack_blocks = 0;
   std::vector<int> pack_blk0;      // first workgroup of every conv's descriptor (+ the total), host copy
-  int64_t adam_t = 0;
-  // data-parallel buckets
-  dh_bucket_cb cb = nullptr;
-  void* cb_user = nullptr;
-  std::vector<std::pair<int64_t, int64_t>> buckets;   // (offset, count), in completion order
 };
 
 namespace {
@@ -97,13 +81,6 @@ int g_abl_consumer_ks = 0;   // kernel size of the convolution that consumes the
 #define DH_ABL_SKIP_APPLY() false
 #define DH_ABL_SKIP_STATS(c) false
 #endif
-
-int t2_alloc(dh_train2* t, void** p, size_t bytes) {
-  DH_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-  (t->shape_phase ? t->shape_allocs : t->allocs).push_back(*p);
-  return DH_OK;
-}
-template <typename V> int t2_allocT(dh_train2* t, V** p, int64_t n) { return t2_alloc(t, reinterpret_cast<void**>(p), (size_t)std::max<int64_t>(n, 1) * sizeof(V)); }
 
 void t2_topology(dh_train2* t) {
   t->convs.clear(); t->blocks.clear();
@@ -147,27 +124,26 @@ void t2_topology(dh_train2* t) {
   }
 }
 
-// arenas in backward-completion order: fc, then blocks last to first (inside a block: last conv ... first conv, downsample), stem
+// arenas in backward-completion order: fc, then blocks last to first (inside a block: last conv ... first conv, downsample), stem;
+// each of them is one completion item
 void t2_layout(dh_train2* t) {
-  int64_t off = 0, roff = 0;
-  auto add = [&](const std::string& k, int64_t cnt) { t->slot[k] = {off, cnt}; off += (cnt + 3) & ~(int64_t)3; };
-  auto radd = [&](const std::string& k, int64_t cnt) { t->rslot[k] = {roff, cnt}; roff += (cnt + 3) & ~(int64_t)3; };
+  int64_t done = 0;   // the arena up to here is covered by items
+  auto item_done = [&]() { t->items.push_back({done, t->n_params - done}); done = t->n_params; };
   auto add_conv = [&](int i) {
     const T2Conv& c = t->convs[i];
-    add(c.bn + ".weight", c.cout); add(c.bn + ".bias", c.cout);
-    add(c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
-    radd(c.bn + ".running_mean", c.cout); radd(c.bn + ".running_var", c.cout);
-    t->order.push_back({off, i});
+    store_add(*t, c.bn + ".weight", c.cout); store_add(*t, c.bn + ".bias", c.cout);
+    store_add(*t, c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
+    store_radd(*t, c.bn + ".running_mean", c.cout); store_radd(*t, c.bn + ".running_var", c.cout);
+    item_done();
   };
-  add("fc.weight", (int64_t)t->n_classes * t->feat); add("fc.bias", t->n_classes);
-  t->order.push_back({off, -1});
+  store_add(*t, "fc.weight", (int64_t)t->n_classes * t->feat); store_add(*t, "fc.bias", t->n_classes);
+  item_done();
   for (int b = (int)t->blocks.size() - 1; b >= 0; --b) {
     const T2Block& blk = t->blocks[b];
     for (int i = blk.nconv - 1; i >= 0; --i) add_conv(blk.conv[i]);
     if (blk.ds >= 0) add_conv(blk.ds);
   }
   add_conv(0);
-  t->n_params = off; t->n_running = roff;
 }
 
 // packs the weights of convs [i0, i1) (all of them by default)
@@ -624,11 +600,9 @@ int t2_stem_wgrad(const bf16_t* dz, const float* x, float* slabs, int B, int P, 
   return DH_OK;
 }
 
-int t2_free_shape(dh_train2* t) {
-  for (void* q : t->shape_allocs) (void)hipFree(q);
-  t->shape_allocs.clear();
+void t2_free_shape(dh_train2* t) {
+  store_free_shape(*t);
   t->B = t->P = 0;
-  return DH_OK;
 }
 
 // activations / workspaces of a batch shape (the arenas and packed weights are shape-independent)
@@ -648,9 +622,9 @@ int t2_shape(dh_train2* t, int B, int P) {
     maxact = std::max(maxact, std::max(nout, (int64_t)B * hi * hi * std::max(c.cin, 8)));
     maxact = std::max(maxact, (int64_t)B * hi * hi * c.cout);   // zero-upsampled gradient of a stride-2 conv
     int r;
-    if ((r = t2_allocT(t, &c.Z, nout)) || (r = t2_allocT(t, &c.Y, nout))) return r;
-    if (top && (r = t2_allocT(t, &c.Ybits, nout / 8))) return r;
-    if (t->side_wgrad && i > 0 && (r = t2_allocT(t, &c.dZ, nout))) return r;
+    if ((r = store_alloc(*t, &c.Z, nout)) || (r = store_alloc(*t, &c.Y, nout))) return r;
+    if (top && (r = store_alloc(*t, &c.Ybits, nout / 8))) return r;
+    if (t->side_wgrad && i > 0 && (r = store_alloc(*t, &c.dZ, nout))) return r;
     return DH_OK;
   };
   if ((rc = setup(0, P))) return done(rc);
@@ -665,9 +639,9 @@ int t2_shape(dh_train2* t, int B, int P) {
     H = h;
   }
   const int64_t S1 = (int64_t)B * H2 * H2 * 64;
-  if ((rc = t2_allocT(t, &t->X1, S1)) || (rc = t2_allocT(t, &t->pool_idx, S1)) || (rc = t2_allocT(t, &t->pooled, (int64_t)B * t->feat)))
+  if ((rc = store_alloc(*t, &t->X1, S1)) || (rc = store_alloc(*t, &t->pool_idx, S1)) || (rc = store_alloc(*t, &t->pooled, (int64_t)B * t->feat)))
     return done(rc);
-  for (int i = 0; i < 6; ++i) if ((rc = t2_allocT(t, &t->GB[i], maxact))) return done(rc);
+  for (int i = 0; i < 6; ++i) if ((rc = store_alloc(*t, &t->GB[i], maxact))) return done(rc);
   // slab buffer of the weight gradients: the largest n_slabs * weights over the layers (a single slab goes straight to G)
   t->B = B; t->P = P;
   int64_t need = 0;
@@ -677,15 +651,8 @@ int t2_shape(dh_train2* t, int B, int P) {
     if (q.n_slabs > 1) need = std::max(need, (int64_t)q.n_slabs * t->convs[i].cout * t->convs[i].cin * t->convs[i].ks * t->convs[i].ks);
   }
   t->wgrad_slab_floats = need;
-  if ((rc = t2_allocT(t, &t->wgrad_slabs, need))) return done(rc);
+  if ((rc = store_alloc(*t, &t->wgrad_slabs, need))) return done(rc);
   return done(DH_OK);
-}
-
-void t2_fire_buckets(dh_train2* t, int64_t done_off, size_t* next) {
-  while (*next < t->buckets.size() && t->buckets[*next].first + t->buckets[*next].second <= done_off) {
-    if (t->cb) t->cb((int32_t)*next, t->buckets[*next].first, t->buckets[*next].second, t->cb_user);
-    ++*next;
-  }
 }
 
 }  // namespace
@@ -696,26 +663,24 @@ extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_cla
   DH_REQUIRE(n_classes > 0 && n_classes <= 1024, "train2 create: n_classes=%d", n_classes);
   if (int erc = dh::env_check()) return erc;   // a mistyped DH_* switch stops here, named by dh_last_error()
   auto* t = new dh_train2();
-  t->arch = arch; t->n_classes = n_classes; t->dev = current_device();
+  t->arch = arch; t->n_classes = n_classes;
   t2_topology(t);
   t2_layout(t);
   int rc;
-  auto fail = [&](int r) { for (void* q : t->allocs) (void)hipFree(q); delete t; return r; };
-  if ((rc = t2_allocT(t, &t->Pm, t->n_params)) || (rc = t2_allocT(t, &t->G, t->n_params)) || (rc = t2_allocT(t, &t->M, t->n_params)) ||
-      (rc = t2_allocT(t, &t->V, t->n_params)) || (rc = t2_allocT(t, &t->R, t->n_running)) || (rc = t2_allocT(t, &t->ones, 2048)) ||
-      (rc = t2_allocT(t, &t->zeros, 2048)) || (rc = t2_allocT(t, &t->partial, T2_PARTIAL_FLOATS)) ||
-      (rc = t2_allocT(t, &t->stem_slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160))) return fail(rc);
-  for (float* a : {t->Pm, t->G, t->M, t->V}) if (hipMemset(a, 0, t->n_params * 4) != hipSuccess) return fail(DH_EHIP);
-  if (hipMemset(t->R, 0, t->n_running * 4) != hipSuccess || hipMemset(t->zeros, 0, 2048 * 4) != hipSuccess) return fail(DH_EHIP);
+  auto fail = [&](int r) { store_free_all(*t); delete t; return r; };
+  if ((rc = store_alloc_arenas(*t, nullptr)) || (rc = store_alloc(*t, &t->ones, 2048)) ||
+      (rc = store_alloc(*t, &t->zeros, 2048)) || (rc = store_alloc(*t, &t->partial, T2_PARTIAL_FLOATS)) ||
+      (rc = store_alloc(*t, &t->stem_slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160))) return fail(rc);
   hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, nullptr, t->ones, (int64_t)2048, 1.0f);
+  if (hipMemsetAsync(t->zeros, 0, 2048 * 4, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return fail(DH_EHIP);   // the caller's streams need not be ordered behind the null stream
   for (T2Conv& c : t->convs) {
-    const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;
-    if (c.ks == 7) { if ((rc = t2_alloc(t, &c.wp_f, 7 * 2 * 2 * FRAG_BYTES))) return fail(rc); }
-    else if ((rc = t2_alloc(t, &c.wp_f, nw * 2)) || (rc = t2_alloc(t, &c.wp_d, nw * 2))) return fail(rc);
+    const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;   // operands in bf16
+    if (c.ks == 7) { if ((rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_f), 7 * 2 * 2 * FRAG_BYTES / 2))) return fail(rc); }
+    else if ((rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_f), nw)) || (rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_d), nw))) return fail(rc);
     float** bb[7] = {&c.bnb.mean, &c.bnb.invstd, &c.bnb.scale, &c.bnb.shift, &c.bnb.k0, &c.bnb.k1, &c.bnb.k2};
-    for (auto q : bb) if ((rc = t2_allocT(t, q, c.cout))) return fail(rc);
+    for (auto q : bb) if ((rc = store_alloc(*t, q, c.cout))) return fail(rc);
   }
-  t->buckets.assign(1, {0, t->n_params});
+  store_set_buckets(*t, 0, nullptr, nullptr, nullptr);   // one bucket until the caller cuts its own
   // The weight-gradient kernels (one workgroup per CU, bound by their operand ingest) run on a side stream next to the HBM-bound
   // BN backward and the dgrad of the following layers.  Round 2 handed every convolution over by itself (two events per
   // convolution: ResNet-50 8.84 -> 8.56 ms per step, ResNet-18 slower); with one hand-off per block and a dZ buffer per
@@ -723,16 +688,7 @@ extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_cla
   t->side_wgrad = dh::env_int("DH_T2_SIDE") != 0;
   t->join_fused = dh::env_int("DH_T2_JOIN") != 0;
   t->fold = dh::env_int("DH_T2_FOLD") != 0;
-  if (t->side_wgrad) {
-    int pr_lo = 0, pr_hi = 0;   // the side stream is filler next to the critical path: lowest priority
-    (void)hipDeviceGetStreamPriorityRange(&pr_lo, &pr_hi);
-    if (pr_lo == pr_hi || hipStreamCreateWithPriority(&t->side, hipStreamNonBlocking, pr_lo) != hipSuccess) {
-      (void)hipGetLastError();   // the failed attempt's error is sticky: without this the next DH_LAUNCH_CHECK reports it as a launch failure
-      if (hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking) != hipSuccess) return fail(DH_EHIP);   // (no priorities on this device: a plain stream)
-    }
-    for (hipEvent_t* e : {&t->ev_dz, &t->ev_join})
-      if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(DH_EHIP);
-  }
+  if (t->side_wgrad && (rc = store_open_side(*t))) return fail(rc);
   *out = t;
   return DH_OK;
 }
@@ -740,56 +696,33 @@ extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_cla
 extern "C" void dh_train2_destroy(dh_train2* t) {
   if (!t) return;
   (void)hipDeviceSynchronize();
-  for (void* q : t->allocs) (void)hipFree(q);
-  for (void* q : t->shape_allocs) (void)hipFree(q);
-  for (hipEvent_t e : {t->ev_dz, t->ev_join}) if (e) (void)hipEventDestroy(e);
-  if (t->side) (void)hipStreamDestroy(t->side);
+  store_free_all(*t);
   delete t;
 }
 
-// kind: 0 parameter, 1 gradient, 2 running statistic; to_lib != 0 copies caller -> library.  `ptr` may be host or device memory.
+// store_tensor on the engine's arenas; a pushed parameter makes the packed bf16 operands stale
 extern "C" int dh_train2_tensor(dh_train2* t, const char* name, int32_t kind, void* ptr, int64_t n_elem, int32_t to_lib, void* stream) {
   DH_REQUIRE(t && name && ptr && kind >= 0 && kind <= 2, "train2 tensor: bad arguments");
-  if (std::string(name).find("num_batches_tracked") != std::string::npos) return DH_OK;
-  float* base = kind == 0 ? t->Pm : kind == 1 ? t->G : t->R;
-  const auto& table = kind == 2 ? t->rslot : t->slot;
-  auto it = table.find(name);
-  DH_REQUIRE(it != table.end(), "train2 tensor: unknown tensor '%s' (kind %d)", name, kind);
-  DH_REQUIRE(it->second.second == n_elem, "train2 tensor: '%s' has %lld elements, got %lld", name, (long long)it->second.second, (long long)n_elem);
-  hipStream_t st = dh::as_stream(stream);
-  if (to_lib) { DH_HIP(hipMemcpyAsync(base + it->second.first, ptr, n_elem * 4, hipMemcpyDefault, st)); if (kind == 0) t->packed = false; }
-  else DH_HIP(hipMemcpyAsync(ptr, base + it->second.first, n_elem * 4, hipMemcpyDefault, st));
-  return DH_OK;
+  const int rc = store_tensor(*t, "train2 tensor", name, kind, ptr, n_elem, to_lib, dh::as_stream(stream));
+  if (rc == DH_OK && to_lib && kind == 0 && !strstr(name, "num_batches_tracked")) t->packed = false;
+  return rc;
 }
 
 extern "C" int dh_train2_flat(dh_train2* t, int32_t kind, void** ptr_out, int64_t* n_out) {
   DH_REQUIRE(t && ptr_out && n_out && kind >= 0 && kind <= 2, "train2 flat: bad arguments");
-  *ptr_out = kind == 0 ? t->Pm : kind == 1 ? t->G : t->R;
-  *n_out = kind == 2 ? t->n_running : t->n_params;
+  store_flat(*t, kind, ptr_out, n_out);
   return DH_OK;
 }
 
-// Gradient buckets for the data-parallel all-reduce: the gradient arena is cut into buckets of about `bucket_bytes`
-// (whole tensors; 0 = one bucket) in the order in which the backward pass completes them.  `cb` (may be NULL) is called on
-// the calling thread from inside dh_train2_backward right after the kernels that finish a bucket have been enqueued on the
-// backward stream: the caller records an event there and starts that bucket's all-reduce on a side stream.
+// Gradient buckets for the data-parallel all-reduce (store_set_buckets has the contract): prefixes of the backward-ordered arena
 extern "C" int dh_train2_set_buckets(dh_train2* t, int64_t bucket_bytes, dh_bucket_cb cb, void* user, int32_t* n_buckets_out) {
   DH_REQUIRE(t && bucket_bytes >= 0, "train2 buckets: bad arguments");
-  t->cb = cb; t->cb_user = user;
-  t->buckets.clear();
-  int64_t start = 0;
-  for (size_t i = 0; i < t->order.size(); ++i) {
-    const int64_t end = t->order[i].first;
-    const bool last = i + 1 == t->order.size();
-    if (last || (bucket_bytes > 0 && (end - start) * 4 >= bucket_bytes)) { t->buckets.push_back({start, end - start}); start = end; }
-  }
-  if (n_buckets_out) *n_buckets_out = (int32_t)t->buckets.size();
+  store_set_buckets(*t, bucket_bytes, cb, user, n_buckets_out);
   return DH_OK;
 }
 extern "C" int dh_train2_bucket(dh_train2* t, int32_t i, int64_t* offset, int64_t* count) {
-  DH_REQUIRE(t && offset && count && i >= 0 && (size_t)i < t->buckets.size(), "train2 bucket: index out of range");
-  *offset = t->buckets[i].first; *count = t->buckets[i].second;
-  return DH_OK;
+  DH_REQUIRE(t, "train2 bucket: index out of range");
+  return store_bucket(*t, "train2 bucket", i, offset, count);
 }
 
 // bf16 wire format for gradient buckets (both engines' arenas: offsets and counts are multiples of 4 elements, 16-byte aligned):
@@ -882,20 +815,13 @@ extern "C" int dh_train2_forward(dh_train2* t, const float* x, int64_t n, int32_
 }
 
 namespace {
-struct AdamArgs { float lr, beta1, beta2, eps, bc1, bc2s; };
-void t2_adam_range(dh_train2* t, const AdamArgs& a, int64_t off, int64_t n, hipStream_t st) {
-  if (n <= 0) return;
-  if (!(g_t2_abl & 8)) hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, st, t->Pm + off, t->G + off, t->M + off, t->V + off, n, a.lr, a.beta1, a.beta2,
-                     a.eps, a.bc1, a.bc2s);
-}
-
 // `fused` (single-rank training): the Adam update and the bf16 repack of a block's tensors follow that block's weight gradients on
 // the side stream, instead of one update of the whole arena after the pass (same arithmetic per element: identical parameters).
 int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamArgs* fused) {
   const int B = t->B, ncls = t->n_classes;
   int rc;
-  size_t next_bucket = 0, item = 0;
-  auto mark_done = [&]() { t2_fire_buckets(t, t->order[item].first, &next_bucket); ++item; };
+  store_begin_backward(*t);
+  auto mark_done = [&]() { store_mark_done(*t); };
   const T2Conv& lastc = t->convs[t->blocks.back().conv[t->blocks.back().nconv - 1]];
   const int HW = lastc.Ho * lastc.Wo;
   hipLaunchKernelGGL(fc_wgrad_kernel, dim3((ncls * t->feat + 255) / 256), dim3(256), 0, st, dlogits, t->pooled, B, t->feat, ncls,
@@ -917,22 +843,20 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   int64_t adam_off = 0;   // fused optimiser: the arena up to here has been updated
   auto flush_side = [&]() -> int {   // hand the queued weight gradients to the side stream
     if (pending.empty()) return DH_OK;
-    DH_HIP(hipEventRecord(t->ev_dz, st));
-    DH_HIP(hipStreamWaitEvent(t->side, t->ev_dz, 0));
+    int r = side_handoff(*t, st);
+    if (r) return r;
     int lo = (int)t->convs.size(), hi = -1;
     for (const PendingW& w : pending) {
-      int r = t2_wgrad(t, *w.c, w.xin, w.dz, t->side);
-      if (r) return r;
+      if ((r = t2_wgrad(t, *w.c, w.xin, w.dz, t->side))) return r;
       const int ci = (int)(w.c - t->convs.data());
       lo = std::min(lo, ci); hi = std::max(hi, ci);
     }
     if (fused) {   // every gradient of the items marked done so far is complete once the side stream gets here
-      const int64_t upto = t->order[item - 1].first;
+      const int64_t upto = t->items[t->items_done - 1].first + t->items[t->items_done - 1].second;
       DH_REQUIRE(hi - lo + 1 == (int)pending.size(), "train2 backward: the convolutions of a hand-off are not a contiguous range");
-      t2_adam_range(t, *fused, adam_off, upto - adam_off, t->side);
+      if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, upto - adam_off, t->side);
       adam_off = upto;
-      int r = (g_t2_abl & 8) ? DH_OK : t2_pack(t, t->side, lo, hi + 1);
-      if (r) return r;
+      if (!(g_t2_abl & 8) && (r = t2_pack(t, t->side, lo, hi + 1))) return r;
     }
     pending.clear();
     return DH_OK;
@@ -940,16 +864,9 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   auto join_side = [&]() -> int {   // everything handed to the side stream so far precedes what the main stream does next
     if (!side) return DH_OK;
     int r = flush_side();
-    if (r) return r;
-    DH_HIP(hipEventRecord(t->ev_join, t->side));
-    DH_HIP(hipStreamWaitEvent(st, t->ev_join, 0));
-    return DH_OK;
+    return r ? r : side_join(*t, st);
   };
-  // a bucket completes with the item about to be marked done: its gradients must precede the caller's event
-  auto bucket_due = [&]() {
-    return t->cb != nullptr && next_bucket < t->buckets.size() &&
-           t->buckets[next_bucket].first + t->buckets[next_bucket].second <= t->order[item].first;
-  };
+  auto bucket_due = [&]() { return store_bucket_due(*t); };
   int top_rows = 0;   // rows of BN-backward sums the last dgrad GEMM left for the NEXT block's join BN (0: none)
   hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits, t->Pm + t->slot["fc.weight"].first, HW, t->feat, ncls, dOut);
   DH_LAUNCH_CHECK();
@@ -1023,7 +940,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
     if ((rc = join_side())) return rc;   // the optimiser (and the last bucket) follow on the main stream
     mark_done();
     if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
-      t2_adam_range(t, *fused, adam_off, t->n_params - adam_off, st);
+      if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, t->n_params - adam_off, st);
       if ((rc = adam_off == 0 ? t2_pack(t, st) : t2_pack(t, st, 0, 1))) return rc;
       DH_LAUNCH_CHECK();
     }
@@ -1043,10 +960,8 @@ extern "C" int dh_train2_backward(dh_train2* t, const float* dlogits, void* stre
 extern "C" int dh_train2_backward_adam(dh_train2* t, const float* dlogits, float lr, float beta1, float beta2, float eps, int64_t step,
                                        void* stream) {
   DH_REQUIRE(t && dlogits && t->B > 0 && t->last_training, "train2 backward: no training forward has run");
-  DH_REQUIRE(t->cb == nullptr, "train2 backward_adam: gradient buckets are armed (data-parallel steps call backward and adam_step)");
-  if (step <= 0) step = t->adam_t + 1;
-  t->adam_t = step;
-  const AdamArgs a{lr, beta1, beta2, eps, 1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step))};
+  DH_REQUIRE(t->bucket_cb == nullptr, "train2 backward_adam: gradient buckets are armed (data-parallel steps call backward and adam_step)");
+  const AdamArgs a = adam_args(*t, lr, beta1, beta2, eps, step);
   int rc = t2_backward(t, dlogits, dh::as_stream(stream), &a);
   if (rc == DH_OK) t->packed = true;
   return rc;
@@ -1055,11 +970,7 @@ extern "C" int dh_train2_backward_adam(dh_train2* t, const float* dlogits, float
 extern "C" int dh_train2_adam_step(dh_train2* t, float lr, float beta1, float beta2, float eps, int64_t step, void* stream) {
   DH_REQUIRE(t, "train2 adam: null handle");
   hipStream_t st = dh::as_stream(stream);
-  if (step <= 0) step = t->adam_t + 1;
-  t->adam_t = step;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(t->n_params)), dim3(256), 0, st, t->Pm, t->G, t->M, t->V, t->n_params, lr, beta1, beta2, eps, bc1, bc2s);
+  adam_range(*t, adam_args(*t, lr, beta1, beta2, eps, step), 0, t->n_params, st);
   DH_LAUNCH_CHECK();
   return t2_pack_all(t, st);
 }
@@ -1244,9 +1155,7 @@ extern "C" int dh_debug_bn2_bf16(const uint16_t* z_dev, const uint16_t* res_dev,
     DH_HIP(hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st));
     DH_HIP(hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
-  rc = dbg_finish(st, "debug bn2");
-  t.Pm = t.G = t.R = nullptr;
-  return rc;
+  return dbg_finish(st, "debug bn2");
 }
 
 // The stem's fused tail on caller data, through the engine's launch code (t2_bn_fwd with a pooled target, t2_bn_pool_bwd):
@@ -1283,10 +1192,8 @@ extern "C" int dh_debug_bn2_pool_bf16(const uint16_t* z_dev, const float* gamma_
     if (!rc && (hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
                 hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)) rc = DH_EHIP;
   }
-  if (!rc) rc = dbg_finish(st, "debug bn2 pool");
-  else (void)hipStreamSynchronize(st);
-  t.Pm = t.G = t.R = nullptr;
-  return rc;
+  if (rc) { (void)hipStreamSynchronize(st); return rc; }
+  return dbg_finish(st, "debug bn2 pool");
 }
 
 // The bf16 engine's stem weight gradient on caller data: dz bf16 [B][P/2][P/2][64] (NHWC), x float32 [B][3][P][P] -> dW float32 [64][3][7][7]

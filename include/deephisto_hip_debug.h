@@ -102,9 +102,11 @@ int dh_debug_stem_pool_bf16(dh_resnet18* net, const uint8_t* slide_dev, int64_t 
  * (all tensors float32 on the device, activations NHWC; each call allocates its own scratch and synchronises):
  *   wgrad       dW[cout][cin][ks][ks] from x [B][Hi][Wi][cin] and dz [B][Ho][Wo][cout]; mode 1 forces the per-tap kernel
  *   stem_wgrad  dW[64][3][7][7] from the NCHW image and dz [B][P/2][P/2][64]
- *   dgrad       dX from dz and the weights [cout][cin][ks][ks] (+ res): stride 2 = zero-upsampled gradient (3x3) /
- *               low-resolution product scattered back (1x1)
+ *   dgrad       dX from dz and the weights [cout][cin][ks][ks] (+ res): stride 2 = the four parity classes of dX over dz
+ *               itself (3x3) / low-resolution product scattered back (1x1)
  *   bn          training-mode BN forward (+ res, ReLU) and, when dy is given, backward (dz, masked gradient g, dgamma, dbeta);
+ *               relu: 0 none, 1 ReLU with the backward pattern read from y, 2 ReLU with the pattern recomputed from z (the
+ *               engine's path for a BN that feeds a ReLU directly; res_dev and g_dev must be NULL, refused otherwise);
  *               stats_out = [mean | invstd | running_mean | running_var] after one update from (0, 1)
  *   maxpool     3x3/2 forward and (dy given) backward through the recorded first-maximum positions */
 int dh_debug_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi,

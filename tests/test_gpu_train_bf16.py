@@ -377,6 +377,60 @@ def test_bucket_layout_and_callback_order(dev):
     assert "fc.weight" in sd_first
 
 
+# (offset, count) of every gradient bucket in completion order, recorded from the engines before they shared one bucket rule
+# (5 classes): float32 ResNet-18 cuts suffixes of a forward-ordered arena, the bf16 engine prefixes of a backward-ordered one
+RECORDED_BUCKETS = {
+    ("resnet18/f32", 0):
+        [(0, 11179080)],
+    ("resnet18/f32", 1048576):
+        [(6455872, 4723208), (2782784, 3673088), (1602112, 1180672), (683072, 919040), (387648, 295424), (83520, 304128), (0,
+        83520)],
+    ("resnet18/f32", 26214400):
+        [(2782784, 8396296), (0, 2782784)],
+    ("resnet18/bf16", 0):
+        [(0, 11179080)],
+    ("resnet18/bf16", 1048576):
+        [(0, 2362888), (2362888, 2360320), (4723208, 2360320), (7083528, 1180672), (8264200, 722432), (8986632, 590336), (9576968,
+        590336), (10167304, 295424), (10462728, 328704), (10791432, 267136), (11058568, 120512)],
+    ("resnet18/bf16", 26214400):
+        [(0, 7083528), (7083528, 4095552)],
+    ("resnet50/bf16", 0):
+        [(0, 23518280)],
+    ("resnet50/bf16", 1048576):
+        [(0, 1062920), (1062920, 2360320), (3423240, 1049600), (4472840, 1052672), (5525512, 2360320), (7885832, 1049600), (8935432,
+        1052672), (9988104, 2360320), (12348424, 525312), (12873736, 2101248), (14974984, 264192), (15239176, 590336), (15829512,
+        262656), (16092168, 264192), (16356360, 590336), (16946696, 262656), (17209352, 264192), (17473544, 590336), (18063880,
+        262656), (18326536, 264192), (18590728, 590336), (19181064, 262656), (19443720, 264192), (19707912, 590336), (20298248,
+        262656), (20560904, 264192), (20825096, 590336), (21415432, 657920), (22073352, 280064), (22353416, 280064), (22633480,
+        280064), (22913544, 379392), (23292936, 225344)],
+    ("resnet50/bf16", 26214400):
+        [(0, 7885832), (7885832, 7089152), (14974984, 6572032), (21547016, 1971264)],
+}
+
+
+@pytest.mark.parametrize("cfg", ["resnet18/f32", "resnet18/bf16", "resnet50/bf16"])
+def test_bucket_ranges_and_firing_order_are_the_recorded_ones(dev, cfg):
+    """Both engines cut their buckets by one rule from their completion items: the lists are the recorded ones at 0 (one bucket), 1 MiB
+    and 25 MiB, and a backward pass fires each bucket once, in that order."""
+    from deephisto_amd._lib import BUCKET_CB
+    from deephisto_amd.models.patch_cls_simple.model import get_model
+    arch, dtype = cfg.split("/")
+    m = (get_model(5, "f32") if dtype == "f32" else get_model(5, "bf16", arch=arch)).to(dev).train()
+    eng = _engine(m)
+    logits = eng.forward(torch.rand(2, 3, 64, 64).to(dev), True, pull_stats=False)
+    dl = torch.zeros_like(logits)
+    for bucket_bytes in (0, 1024 * 1024, 25 * 1024 * 1024):
+        want = RECORDED_BUCKETS[cfg, bucket_bytes]
+        assert eng.bucket_ranges(bucket_bytes) == want
+        seen = []
+        cb = BUCKET_CB(lambda b, off, cnt, _u: seen.append((b, off, cnt)))
+        eng._call("set_buckets", bucket_bytes, cb, None, None)
+        eng._call("backward", dl.data_ptr(), None)
+        eng._call("set_buckets", 0, None, None, None)
+        torch.cuda.synchronize()
+        assert seen == [(i, o, c) for i, (o, c) in enumerate(want)]
+
+
 @pytest.mark.parametrize("arch,B,P", [("resnet50", 2, 256), ("resnet50", 3, 128), ("resnet18", 5, 224), ("resnet50", 1, 160)])
 def test_shape_sweep_forward_backward(dev, arch, B, P):
     """Other patch sizes / batch sizes (odd maps: 160 -> 5x5, 224 -> 7x7; 256 -> the 64-pixel-wide wgrad rows; batch 1): forward

@@ -127,8 +127,10 @@ def test_dgrad_paths(dev, ks, stride, cin, cout, B, H, res):
 
 
 @pytest.mark.parametrize("C,B,H,relu,res", [(64, 4, 28, True, False), (128, 3, 14, True, True), (512, 6, 7, False, False),
-                                            (256, 2, 56, True, True)])
+                                            (256, 2, 56, True, True), (64, 2, 8, 2, False)])
 def test_bn_forward_backward_kernels(dev, C, B, H, relu, res):
+    """relu: False / True (backward pattern read from y) / 2 (pattern recomputed from z: the engine's mode for every block's first BN;
+    no residual, no masked gradient g -- 128 rows = eight reduce workgroups at C = 64)."""
     from deephisto_amd._lib import check, lib
     g = torch.Generator().manual_seed(C + H)
     z = (torch.randn(B, C, H, H, generator=g, dtype=torch.float64) * 1.7 + 0.4).requires_grad_(True)
@@ -150,9 +152,15 @@ def test_bn_forward_backward_kernels(dev, C, B, H, relu, res):
     st = torch.empty(4 * C, device=dev)
     gmd, btd = gamma.detach().to(dev, torch.float32), beta.detach().to(dev, torch.float32)
     rd = _nhwc(r, dev) if res else None
-    check(lib().dh_debug_bn_f32(zd.data_ptr(), gmd.data_ptr(), btd.data_ptr(), rd.data_ptr() if res else None, 1 if relu else 0,
-                                yd.data_ptr(), dyd.data_ptr(), dzd.data_ptr(), gd.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                st.data_ptr(), rows, C, None), "bn")
+    check(lib().dh_debug_bn_f32(zd.data_ptr(), gmd.data_ptr(), btd.data_ptr(), rd.data_ptr() if res else None, int(relu),
+                                yd.data_ptr(), dyd.data_ptr(), dzd.data_ptr(), gd.data_ptr() if relu != 2 else None, dg.data_ptr(),
+                                db.data_ptr(), st.data_ptr(), rows, C, None), "bn")
+    if relu == 2:   # the same inputs with the pattern read from y: the recomputed pattern is bit-identical (comment at col_reduce_kernel)
+        y1, dz1 = torch.empty_like(zd), torch.empty_like(zd)
+        dg1, db1 = torch.empty_like(dg), torch.empty_like(db)
+        check(lib().dh_debug_bn_f32(zd.data_ptr(), gmd.data_ptr(), btd.data_ptr(), None, 1, y1.data_ptr(), dyd.data_ptr(), dz1.data_ptr(),
+                                    gd.data_ptr(), dg1.data_ptr(), db1.data_ptr(), None, rows, C, None), "bn relu=1")
+        assert torch.equal(y1, yd) and torch.equal(dz1, dzd) and torch.equal(dg1, dg) and torch.equal(db1, db)
     assert _rel(_nchw(yd), y.detach()) <= TOL
     # the ReLU pattern of the float32 forward can differ from float64 where |pre-activation| ~ 1e-7: compare the backward
     # with torch's pattern imposed on the few such elements excluded (none in practice at these sizes)
