@@ -106,6 +106,8 @@ SIGNATURES = {
     "dh_stain_apply": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _i32, _p, _i32, _p, _p]),
     "dh_resample_area": (C.c_int, [_p, _i64, _i64, _i32, _i32, _p, _i64, _i64, _p]),
     "dh_slide_dihedral": (C.c_int, [_p, _i64, _i64, _i32, _p, _p]),
+    "dh_quality_tile_stats": (C.c_int, [_p, _i64, _i64, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "dh_quality_flags": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
     "dh_profile_start":(C.c_int, [_i32, _i32]),
     "dh_profile_stop": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }

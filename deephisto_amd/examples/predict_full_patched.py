@@ -29,6 +29,7 @@ from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
 from ..predict import (_SIDE_STREAMS, _forward_streamed, _side_stream, exchange_logits, predict_full_patched,  # noqa: F401  (exported here)
                        predict_random_patched, shard_range)
 from ..psimage_compat import Patch, open_slide
+from ..quality import QualityFilter, score_quality, sharpness, sharpness_summary  # noqa: F401  (exported here)
 from ..regions import (SlideRegions, clean_map, export_annotation, extract_regions, label_components,  # noqa: F401  (exported here)
                        region_table, save_regions, trace_polygons)
 from ..scoring import SlideScore, confusion, rasterize_annotation, save_score, score_prediction  # noqa: F401  (exported here)
@@ -222,6 +223,37 @@ def _tissue_from_args(ap, args) -> TissueFilter | None:
         ap.error(f"--tissue {args.tissue} / --tissue_min_fraction {args.tissue_min_fraction}: {e}")
 
 
+def _quality_from_args(ap, args) -> QualityFilter | None:
+    """The QualityFilter of --min_sharpness / --max_ink / --quality_fill (any of them switches it on), or None; a bad
+    combination is an argparse error."""
+    if args.min_sharpness is None and args.max_ink is None and args.quality_fill is None:
+        if args.quality_json:
+            ap.error("--quality_json needs --min_sharpness, --max_ink or --quality_fill")
+        return None
+    if args.random_sampler:
+        ap.error("the quality filter works on the dense sampler's grid; it cannot be combined with --random_sampler")
+    if args.ondisk:
+        ap.error("the quality filter needs the slide resident in HBM; it cannot be combined with --ondisk")
+    labels = {a.label: a.id for a in AnnoDescription.with_known_colors(KNOWN_COLORS).anno_classes}
+    spelled = args.quality_fill if args.quality_fill is not None else "-1"
+    if spelled in labels:
+        fill = labels[spelled]
+    elif spelled == "-1":
+        fill = -1
+    else:
+        ap.error(f"--quality_fill must be one of {', '.join(labels)} or -1, not {spelled!r}")
+    try:
+        filt = QualityFilter(0 if args.min_sharpness is None else args.min_sharpness,
+                             1.0 if args.max_ink is None else args.max_ink, fill_class=fill)
+    except ValueError as e:
+        ap.error(f"--min_sharpness {args.min_sharpness} / --max_ink {args.max_ink}: {e}")
+    if not 0 < args.patch_size <= 1024:
+        ap.error(f"the quality filter takes --patch_size in [1, 1024], not {args.patch_size}")
+    if args.tissue_filter is not None and args.tissue_filter.fill_class != filt.fill_class:
+        ap.error(f"--tissue_fill {args.tissue_fill} and --quality_fill {spelled} must name the same class")
+    return filt
+
+
 def _stain_from_args(ap, args) -> StainNormalizer | None:
     """The StainNormalizer of the --stain flags, or None for `--stain off`; a bad combination is an argparse error."""
     if args.stain == "off":
@@ -311,6 +343,14 @@ def _build_parser():
     ap.add_argument("--tissue_min_fraction", type=float, default=0.25,
                     help="share of a tile's pixels that must be tissue (0.25: a conventional default, not validated here)")
     ap.add_argument("--tissue_fill", default="-1", help="class label for cells no kept tile covers, or -1 (no class)")
+    ap.add_argument("--min_sharpness", type=int, default=None, metavar="N",
+                    help="reject out-of-focus tiles: Laplacian variance of the luma over a tile's tissue pixels below N grey levels "
+                         "squared (0..1040400; dense branch only; --quality_json reports the slide's quartiles)")
+    ap.add_argument("--max_ink", type=float, default=None, metavar="F",
+                    help="reject tiles with more than the share F of pen-mark or very dark pixels (0..1)")
+    ap.add_argument("--quality_fill", default=None, help="class label for cells no kept tile covers, or -1 (as --tissue_fill)")
+    ap.add_argument("--quality_json", default=None, metavar="PATH",
+                    help="with the quality filter: thresholds, counts and the sharpness quartiles of the scored tiles as JSON (rank 0)")
     ap.add_argument("--pyramid", action="store_true",
                     help="--layer L of a --synthetic slide or a .npy image is the slide at 1/L of its resolution, area-averaged on the "
                          "device (PyramidSlide); without it such a slide has one layer, whatever --layer says")
@@ -340,12 +380,13 @@ def _build_parser():
 
 def _check_args(ap, args, model=None) -> None:
     """The flag checkers, before the process group or any GPU is touched; leaves the TissueFilter (or None) in
-    `args.tissue_filter`, the StainNormalizer (or None) in `args.stain_norm`, the TestTimeAugmenter (or None) in `args.tta_aug`
+    `args.tissue_filter`, the QualityFilter (or None) in `args.quality_filter`, the StainNormalizer (or None) in `args.stain_norm`, the TestTimeAugmenter (or None) in `args.tta_aug`
     and the records of --anno (or None) in `args.anno_records`.  `model`: the module injected into main, if any."""
     _regions_from_args(ap, args)
     _pyramid_from_args(ap, args)
     args.stain_norm = _stain_from_args(ap, args)
     args.tissue_filter = _tissue_from_args(ap, args)
+    args.quality_filter = _quality_from_args(ap, args)
     args.tta_aug = _tta_from_args(ap, args, model)
     args.anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
@@ -390,11 +431,19 @@ def _run(args, model, device, rank, world):
         smp = FullImageDenseSampler(img, layer=args.layer, patch_size=args.patch_size, batch_size=args.batch_size,
                                     mode=mode, stride=args.stride, device=device)
         info: dict = {}
+        qinfo: dict = {}
         out = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
-                                   tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug)
+                                   tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug,
+                                   quality=args.quality_filter, quality_info=qinfo)
         pred, proba = out if args.proba else (out, None)
         if args.tissue_filter is not None and rank == 0:
             print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
+        if args.quality_filter is not None and rank == 0:
+            print(f"quality: {qinfo['n_kept']} of {qinfo['n_tiles']} tiles pass, {qinfo['rejected_blur']} blurred "
+                  f"(min_sharpness {qinfo['min_sharpness']}), {qinfo['rejected_ink']} ink-marked "
+                  f"(more than {qinfo['max_ink_pixels']} pixels)", flush=True)
+            if args.quality_json:
+                _save_quality(args.quality_json, args.quality_filter, qinfo)
         return pred, proba, smp, img, stem
     if world > 1:
         raise RuntimeError("--random_sampler draws tiles from a running coverage map (one process); "
@@ -414,6 +463,19 @@ def _run(args, model, device, rank, world):
         pred = predictor.process()
         proba = predictor.process_proba() if args.proba else None
     return pred, proba, smp, img, stem
+
+
+def _save_quality(path, filt: QualityFilter, qinfo: dict) -> None:
+    """--quality_json: the filter's thresholds, the counts and the five-number summary of the scored tiles' sharpness."""
+    import json
+
+    doc = dict(min_sharpness=qinfo["min_sharpness"], max_ink_fraction=filt.max_ink_fraction, max_ink_pixels=qinfo["max_ink_pixels"],
+               ink_chroma=filt.ink_chroma, ink_margin=filt.ink_margin, dark_max=filt.dark_max, fill_class=filt.fill_class,
+               threshold=qinfo["threshold"], n_tiles=qinfo["n_tiles"], n_kept=qinfo["n_kept"],
+               rejected_blur=qinfo["rejected_blur"], rejected_ink=qinfo["rejected_ink"],
+               sharpness=sharpness_summary(qinfo["stats"]))
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    Path(path).write_text(json.dumps(doc, indent=1) + "\n")
 
 
 def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
@@ -472,6 +534,10 @@ def main(argv=None, model=None):
     `--arch auto` reads the backbone from the checkpoint (ResNet-50 when it has `layer1.0.conv3.weight`).
     `--tissue otsu|<0..255>` classifies only the tiles that hold tissue (dense branch, resident slide; TissueFilter), with
     `--tissue_min_fraction` and `--tissue_fill` (a class label, or -1 for no class) for the cells no kept tile covers.
+    `--min_sharpness N` and `--max_ink F` leave out the out-of-focus and the ink-marked tiles among those (DESIGN.md section 4.16;
+    QualityFilter; dense branch, resident slide; either switches the filter on, as does `--quality_fill`, which must name the
+    class of `--tissue_fill` when both filters run); `--quality_json PATH` writes thresholds, counts and the quartiles of the
+    scored tiles' sharpness (rank 0), from which to pick N.
     `--proba` also computes the per-cell mean softmax probabilities (DESIGN.md section 4.8) and writes the confidence JPEG;
     `--heat LABEL ...` adds one heat map per class label; `--save_proba PATH` writes the probabilities as float16 PATH(.npy) and
     the hit counts as PATH_count.npy (rank 0).  The returned class map stays the argmax of the logit sums.

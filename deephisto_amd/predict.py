@@ -22,6 +22,7 @@ from ._lib import check
 from .models.patch_cls_simple.engine import ResNetHIP
 from .patch_samplers.full_samplers import FullImageDenseSampler
 from .stain import StainNormalizer
+from .quality import QualityFilter, check_fill_classes, score_quality
 from .tissue import TissueFilter, fill_uncovered, score_tiles
 from .tta import TestTimeAugmenter, as_augmenter, dihedral_view, map_origins_device, view_shape
 
@@ -146,7 +147,8 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
                          downscale: int = 16, micro_batch: int | None = None, group=None,
                          return_logits: bool = False, streams: int = 2, dedupe_padding: bool = False, timing: list | None = None,
                          tissue: TissueFilter | None = None, tissue_info: dict | None = None, return_proba: bool = False, *,
-                         tta: TestTimeAugmenter | None = None, tta_info: dict | None = None):
+                         tta: TestTimeAugmenter | None = None, tta_info: dict | None = None,
+                         quality: QualityFilter | None = None, quality_info: dict | None = None):
     """Device-resident whole-slide prediction (rows a1-a8 end to end).
 
     `model`: ResNet18HIP or ResNet50HIP; it names its own fused entry (`tiles_entry`) and launch size
@@ -183,6 +185,15 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
     origins; every rank transforms its own copy (the bytes are exact, nothing is exchanged).  Needs a resident slide.  `stain=`
     composes: the views are those of the normalised slide.  `tta_info`: a dict that receives views (names) and
     n_forward_tiles (tiles x views on this rank).  None leaves every code path and every bit as it is.
+    Keyword-only `quality`: a quality.QualityFilter: the tiles that survived the tissue stage (all unique
+    tiles without one) are measured on the device and the out-of-focus and ink-marked ones are left out; the composition of the
+    two stages is the kept list, which drives everything the tissue list drives above.  Sharpness is measured over the pixels
+    the tissue filter calls tissue (its resolved threshold; without a tissue filter over every pixel).  Uncovered cells get
+    `quality.fill_class`, which must equal `tissue.fill_class` when both are given.  Needs a resident dense sampler.  The sums
+    are computed once, on the slide the prediction reads (`stain=`: the normalised one; `tta=`: the untransformed one).
+    `quality_info`: a dict that receives threshold, min_sharpness, max_ink_pixels, n_tiles, n_kept, rejected_blur,
+    rejected_ink, stats (int64[n, 4]) and reason (uint8[n]) of the scored tiles, and kept: the final list, as int64 indices into
+    the unique tiles.  `tissue_info` keeps the tissue stage's list.  None leaves every code path and every bit as it is.
     Returns int64[h//d, w//d] on the device (and the float32[n_padded, n_cls] logits; rows of rejected tiles are NaN).
     """
     import torch.distributed as dist
@@ -196,6 +207,12 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
             raise ValueError("the tissue filter works on the dense sampler's grid only (not on the random sampler's branch)")
         if streamed:
             raise ValueError("the tissue filter needs an HBM-resident slide (ONDISK_MULTIPROC streams it)")
+    if quality is not None:
+        if not isinstance(sampler, FullImageDenseSampler):
+            raise ValueError("the quality filter works on the dense sampler's grid only (not on the random sampler's branch)")
+        if streamed:
+            raise ValueError("the quality filter needs an HBM-resident slide (ONDISK_MULTIPROC streams it)")
+        check_fill_classes(tissue, quality)
     slide = None if streamed else sampler.data_device
     dev = sampler.device if streamed else slide.device
     P = sampler.patch_size
@@ -209,6 +226,16 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
         kept = kept_idx_dev.cpu().numpy().astype(np.int64)
         if tissue_info is not None:
             tissue_info.update(info, kept=kept)
+    if quality is not None:
+        # the second stage runs over the tiles the first one kept; the final list is the composition of the two
+        t = -1 if tissue is None else info["threshold"]
+        scored = torch.from_numpy(origins[:n_unique]).to(dev) if kept is None else kept_yx_dev
+        q_idx_dev, kept_yx_dev, qinfo = score_quality(slide, scored, P, t, quality,
+                                                      origins[:n_unique] if kept is None else origins[:n_unique][kept])
+        q = q_idx_dev.cpu().numpy().astype(np.int64)
+        kept = q if kept is None else kept[q]
+        if quality_info is not None:
+            quality_info.update(qinfo, kept=kept)
     n_work = n_unique if kept is None else len(kept)
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
     world = dist.get_world_size(group) if distributed else 1
@@ -252,7 +279,8 @@ def predict_full_patched(sampler: FullImageDenseSampler, model, n_classes: int,
         timing.append(ev)
     else:
         logits_work = exchange_logits(local, n_work, group) if distributed else local[:n_work]
-    return _finish(sampler, logits_work, kept, kept_yx_dev, downscale, dedupe_padding, tissue, return_logits, return_proba)
+    return _finish(sampler, logits_work, kept, kept_yx_dev, downscale, dedupe_padding, tissue if quality is None else quality,
+                   return_logits, return_proba)
 
 
 def _forward_views(tta, fwd, fwd_name, handles, lanes, slide, o_dev, P, mb, local, n_classes):
@@ -297,7 +325,7 @@ def _forward_views(tta, fwd, fwd_name, handles, lanes, slide, o_dev, P, mb, loca
 def _finish(sampler, logits_work, kept, kept_yx_dev, downscale, dedupe_padding, tissue, return_logits, return_proba):
     """The tail of predict_full_patched: `logits_work` holds one row per tile that ran (`kept`, or every unique tile for None: the
     unfiltered run is the filtered one with every tile kept).  Ordered accumulation over accumulation_list and argmax; with a
-    tissue filter the fill of the cells no kept tile covers; the probabilities over the same list (uncovered cells: count 0 and
+    tile filter (`tissue`: the TissueFilter or QualityFilter that names the fill class) the fill of the cells no kept tile covers; the probabilities over the same list (uncovered cells: count 0 and
     the fill class); the logits scattered back to the padded list (NaN rows for rejected tiles)."""
     origins, n_unique, P = sampler.origins, sampler.n_tiles, sampler.patch_size
     h, w, dev = sampler.h, sampler.w, logits_work.device

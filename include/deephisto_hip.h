@@ -505,6 +505,29 @@ int dh_resample_area(const uint8_t* src_dev, int64_t h, int64_t w, int32_t num, 
  *     pointer, dst == src or any overlap of the two ranges of 3 * h * w bytes. */
 int dh_slide_dihedral(const uint8_t* src_dev, int64_t h, int64_t w, int32_t view, uint8_t* dst_dev, void* stream);
 
+/* ---- q1: tile quality: out-of-focus and ink-marked tiles -----------------------
+ * Not in the reference, which classifies every tile.  Integer work only, so the result is exact.  Per pixel
+ * (R, G, B) of slide_dev = uint8[h][w][3] (any alignment): luma Y = (77 R + 150 G + 29 B + 128) >> 8;
+ * c = max - min of the three; tissue: c > threshold (-1..255; -1: every pixel); ink: (c > ink_chroma and
+ * G - min(R, B) >= ink_margin) or max(R, G, B) <= dark_max (ink_chroma, ink_margin in 0..255, dark_max in
+ * -1..255; -1 switches the dark clause off).  L = 4 Y - the four neighbours' Y; a neighbour outside the slide
+ * is the edge pixel (clamped coordinates), a neighbour outside the tile is the slide's pixel.
+ * dh_quality_tile_stats: stats_dev = int64[n][4], per window of side patch <= 1024 at yx_dev[i] (int32[n][2],
+ *   (y, x), any origin with 0 <= y <= h-P, 0 <= x <= w-P): n_t = tissue pixels, S1 = sum of L and S2 = sum of
+ *   L*L over the tissue pixels, n_ink = ink pixels over all P*P.  A device origin outside the slide gets four
+ *   times -1 and reads nothing.  When yx_host_check != NULL (the same n pairs on the host) every origin is
+ *   checked before any launch.
+ * dh_quality_flags: reason_dev[i] (uint8) = 2 (blur) when n_t*S2 - S1*S1 < min_sharpness * n_t*n_t (n_t == 0:
+ *   when min_sharpness > 0), | 4 (ink) when n_ink > max_ink_pixels; keep_dev[i] (int32) = 1 when the mask is 0,
+ *   else 0: dh_tissue_select(keep_dev, yx_dev, n, 1, ...) compacts the kept tiles in order.  The products stay
+ *   below 2^63 for sums of tiles with patch <= 1024 and min_sharpness in [0, 1020^2], which is all the
+ *   comparison is defined for.  Sums of -1 give reason 255 and keep -1, which dh_tissue_select refuses. */
+int dh_quality_tile_stats(const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                          const int32_t* yx_host_check, int64_t n, int32_t patch, int32_t threshold, int32_t ink_chroma,
+                          int32_t ink_margin, int32_t dark_max, int64_t* stats_dev, void* stream);
+int dh_quality_flags(const int64_t* stats_dev, int64_t n, int64_t min_sharpness, int64_t max_ink_pixels,
+                     uint8_t* reason_dev, int32_t* keep_dev, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------
  * Times the dominant kernel (3x3 stride-1 conv, ~85 % of the model FLOPs) with HIP
  * events recorded on the launch stream around every `sample_every`-th launch (at most
