@@ -1169,6 +1169,7 @@ struct dh_train : TrainStore {   // the arena is in FORWARD order: the backward 
   int pack_blocks = 0, pack_nd = 0;
   std::vector<int> pack_blk0;     // first workgroup of every descriptor (+ the total), host copy; descriptor j = conv j + 1
   const float* x_in = nullptr;  // input of the last forward (caller memory; must stay alive until backward)
+  bool bwd_done = false;        // a backward pass has run since the last forward: every dZ buffer holds THIS step's gradient (debug tap)
   // TrainStore::side: the weight gradients are handed over once per residual block: they fill the CUs the persistent
   // convolution launches leave idle in their last round of tiles.  DH_T1_SIDE=0: everything on the caller's stream.
 };
@@ -1540,7 +1541,7 @@ extern "C" int dh_resnet18_forward_train(dh_resnet18* net, const float* x, int64
   hipStream_t st = dh::as_stream(stream);
   const int B = (int)n;
   const UnitAffine u{t->ones, t->zeros};
-  t->x_in = x;
+  t->x_in = x; t->bwd_done = false;
   // stem: raw conv (unit scale, zero shift, no ReLU) -> batch-stat BN + ReLU -> maxpool
   {
     TrainConv& tc = t->tc[0];
@@ -1705,6 +1706,7 @@ int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const Ad
       if (adam_end == t->n_params && (rc = tr_pack(net, st, 1, (int)net->convs.size()))) return rc;
     }
   }
+  t->bwd_done = true;
   return DH_OK;
 }
 }  // namespace
@@ -1770,6 +1772,33 @@ extern "C" int dh_resnet18_train_flat(dh_resnet18* net, int32_t kind, void** ptr
   DH_REQUIRE(net && net->train && ptr_out && n_out && kind >= 0 && kind <= 2, "train flat: bad arguments / no training state");
   store_flat(*net->train, kind, ptr_out, n_out);
   return DH_OK;
+}
+
+// Test hook: float32 copy of a tensor the last training forward / backward left in memory (dh_train2_debug_act of the float32 engine):
+// what = 0 Z, 1 Y, 2 dZ of conv `conv_name` (dZ as the weight-gradient kernel read it; the stem's lives in BIG1, which nothing else
+// uses), 3 the pooled block input X1 (under "conv1").  Read-only: the stem's Y, which the engine never stores, is refused.
+extern "C" int dh_resnet18_train_debug_act(dh_resnet18* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream) {
+  DH_REQUIRE(net && net->train && conv_name && out_dev && net->train->B > 0 && net->train->x_in, "train debug: bad arguments / no training forward");
+  DH_REQUIRE(what >= 0 && what <= 3, "train debug: what = %d (0 Z, 1 Y, 2 dZ, 3 X1)", what);
+  const dh_train* t = net->train;
+  for (size_t i = 0; i < net->convs.size(); ++i)
+    if (net->convs[i].name == conv_name) {
+      const TrainConv& tc = t->tc[i];
+      DH_REQUIRE(what != 3 || i == 0, "train debug: what = 3 (X1, the pooled block input) goes with 'conv1', not '%s'", conv_name);
+      DH_REQUIRE(what != 1 || i != 0, "train debug: what = 1 (Y) of 'conv1' is not kept (the stem pools in its BN pass: what = 3)");
+      const int H2 = (tc.Ho + 2 - 3) / 2 + 1;
+      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * tc.Ho * tc.Wo * net->convs[i].cout;
+      DH_REQUIRE(n == n_elem, "train debug: n_elem = %lld, '%s' (what = %d) has %lld elements", (long long)n_elem, conv_name, what, (long long)n);
+      if (what == 2) {
+        DH_REQUIRE(t->side != nullptr, "train debug: what = 2 (dZ) needs the per-convolution dZ buffers of the side-stream engine (created with DH_T1_SIDE=0)");
+        DH_REQUIRE(t->bwd_done, "train debug: what = 2 (dZ): no backward has run since the last forward");
+      }
+      const float* src = what == 0 ? tc.Z : what == 1 ? tc.Y : what == 3 ? t->X1 : i == 0 ? t->BIG1 : tc.dZ;
+      DH_HIP(hipMemcpyAsync(out_dev, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, dh::as_stream(stream)));
+      return DH_OK;
+    }
+  dh::set_error("train debug: unknown conv_name '%s'", conv_name);
+  return DH_EINVAL;
 }
 
 // =====================================================================================

@@ -54,6 +54,7 @@ struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order
   int64_t wgrad_slab_floats = 0;
   const float* x_in = nullptr;
   bool last_training = false;
+  bool bwd_done = false;    // a backward pass has run since the last forward: every dZ buffer holds THIS step's gradient (dh_train2_debug_act)
   bool packed = false;
   PackDesc* pack_desc = nullptr;   // device table of t2_pack_all (one launch packs every conv)
   int pack_blocks = 0;
@@ -759,7 +760,7 @@ extern "C" int dh_train2_forward(dh_train2* t, const float* x, int64_t n, int32_
   if (!t->packed && (rc = t2_pack_all(t, st))) return rc;
   const int B = (int)n;
   const bool tr = training != 0;
-  t->x_in = x; t->last_training = tr;
+  t->x_in = x; t->last_training = tr; t->bwd_done = false;
   {   // stem: raw conv -> BN + ReLU -> maxpool
     T2Conv& c = t->convs[0];
     StemParams sp;
@@ -945,6 +946,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
       DH_LAUNCH_CHECK();
     }
   }
+  t->bwd_done = true;
   return DH_OK;
 }
 }  // namespace
@@ -975,21 +977,33 @@ extern "C" int dh_train2_adam_step(dh_train2* t, float lr, float beta1, float be
   return t2_pack_all(t, st);
 }
 
-// Test hook: float32 copy of an intermediate tensor of the last forward / backward: what = 0 Z, 1 Y of conv `conv_name`.
+// Test hook: float32 copy of a tensor the last forward / backward left in memory: what = 0 Z, 1 Y, 2 dZ of conv `conv_name` (dZ: the
+// gradient with respect to Z as the weight-gradient kernel read it; the stem's lives in GB[2], which the side-stream engine uses for
+// nothing else), 3 the pooled block input X1 (under "conv1").  Read-only but for what = 1 on the stem, which rebuilds Y from Z.
 extern "C" int dh_train2_debug_act(dh_train2* t, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream) {
   DH_REQUIRE(t && conv_name && out_dev && t->B > 0, "train2 debug: bad arguments / no forward");
+  DH_REQUIRE(what >= 0 && what <= 3, "train2 debug: what = %d (0 Z, 1 Y, 2 dZ, 3 X1)", what);
+  hipStream_t st = dh::as_stream(stream);
   for (const T2Conv& c : t->convs)
     if (c.name == conv_name) {
-      const int64_t n = (int64_t)t->B * c.Ho * c.Wo * c.cout;
-      DH_REQUIRE(n == n_elem, "train2 debug: '%s' has %lld elements, got %lld", conv_name, (long long)n, (long long)n_elem);
-      if (what == 1 && &c == &t->convs[0])   // the stem's normalised map is not kept (bn2_apply_pool_kernel): made here from Z and the saved coefficients
-        hipLaunchKernelGGL(bn2_apply_kernel, dim3(grid_for(n / 8)), dim3(256), 0, dh::as_stream(stream), c.Z, c.bnb.scale, c.bnb.shift,
+      const bool stem = &c == &t->convs[0];
+      DH_REQUIRE(what != 3 || stem, "train2 debug: what = 3 (X1, the pooled block input) goes with 'conv1', not '%s'", conv_name);
+      const int H2 = (c.Ho + 2 - 3) / 2 + 1;
+      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * c.Ho * c.Wo * c.cout;
+      DH_REQUIRE(n == n_elem, "train2 debug: n_elem = %lld, '%s' (what = %d) has %lld elements", (long long)n_elem, conv_name, what, (long long)n);
+      const bf16_t* src = what == 0 ? c.Z : what == 1 ? c.Y : what == 3 ? t->X1 : stem ? t->GB[2] : c.dZ;
+      if (what == 2) {
+        DH_REQUIRE(t->side_wgrad, "train2 debug: what = 2 (dZ) needs the per-convolution dZ buffers of the side-stream engine (created with DH_T2_SIDE=0)");
+        DH_REQUIRE(t->bwd_done, "train2 debug: what = 2 (dZ): no backward has run since the last forward");
+      }
+      if (what == 1 && stem)   // the stem's normalised map is not kept (bn2_apply_pool_kernel): made here from Z and the saved coefficients
+        hipLaunchKernelGGL(bn2_apply_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, c.Z, c.bnb.scale, c.bnb.shift,
                            static_cast<const bf16_t*>(nullptr), c.Y, n / 8, c.cout, 1);
-      hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n)), dim3(256), 0, dh::as_stream(stream), what == 0 ? c.Z : c.Y, out_dev, n);
+      hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, src, out_dev, n);
       DH_LAUNCH_CHECK();
       return DH_OK;
     }
-  dh::set_error("train2 debug: unknown conv '%s'", conv_name);
+  dh::set_error("train2 debug: unknown conv_name '%s'", conv_name);
   return DH_EINVAL;
 }
 

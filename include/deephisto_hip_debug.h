@@ -16,8 +16,17 @@
 extern "C" {
 #endif
 
-/* test hook: float32 copy of conv `conv_name`'s raw output (what = 0) or BN/ReLU output (what = 1) of the last forward */
+/* Taps of the training engines: float32 copy of a tensor the last forward / backward left in device memory, channels last.
+ *   what = 0  Z  of conv `conv_name`: its raw output [B][Ho][Wo][cout]
+ *   what = 1  Y: the BN (+ identity) (+ ReLU) output (bf16 stem: rebuilt from Z, the one tap that writes; float32 stem: refused, not kept)
+ *   what = 2  dZ: the gradient with respect to Z exactly as the conv's weight-gradient kernel read it, [B][Ho][Wo][cout].  Only engines
+ *             created with the side stream (DH_T2_SIDE / DH_T1_SIDE, the default) keep a dZ per conv, and only between a backward and
+ *             the next forward is it this step's: refused otherwise.
+ *   what = 3  with conv_name "conv1": X1, the pooled block input [B][H2][H2][64]; refused for any other name.
+ * Refused with DH_EINVAL (dh_last_error names the argument): an unknown conv_name, what outside 0..3, n_elem other than the tensor's size.
+ * Stream-ordered, no synchronisation.  dh_train2_debug_act: the bf16 engine; dh_resnet18_train_debug_act: the float32 engine. */
 int dh_train2_debug_act(dh_train2* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream);
+int dh_resnet18_train_debug_act(dh_resnet18* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream);
 
 /* test hooks of the engine's GEMM-shaped kernels on caller data (bf16 bits as uint16; synchronise; `repeat` launches for timing):
  * gemm1x1: out[M][N] = A[rows][K] . W[N][K]^T (+ res), stride 2 = row gather (b, 2 oy, 2 ox) from [B][Hi][Wi][K];
