@@ -143,6 +143,7 @@ DEBUG_SIGNATURES = {
     "dh_debug_bn_pool_f32": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "dh_debug_stamps": (C.c_int, [_i32, _p]),
     "dh_debug_stem_strip_width": (C.c_int, [_i32]),
+    "dh_debug_last_conv3": (C.c_int, [_p, _p]),
     "dh_debug_env_knobs": (C.c_int, [C.c_char_p, _i64]),
     "dh_debug_coverage_set_map": (C.c_int, [_p, _p, _p]),
     "dh_debug_resnet18_forward_tap": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, C.c_char_p, _p, _i32, _p, _i64, _p, _p]),

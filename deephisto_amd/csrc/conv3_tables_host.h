@@ -32,7 +32,7 @@ constexpr int kChunkBytes = 64;   // channel bytes of one pixel staged per pass 
 struct TileDesc { int x, y, z, w; };   // {cout block | valid << 16 | mask row << 20, window byte offset, output element offset, residual element offset}
 
 struct HostTables {
-  std::vector<int> lane;        // [threads][3 NT + MAXJ] = {out_rel[NT], base_lin[NT], res_rel[NT], rel_off[MAXJ]}
+  std::vector<int> lane;        // [threads][2 NT + NB + MAXJ] = {out_rel[NT], base_lin[NB], res_rel[NT], rel_off[MAXJ]}; NB = NT (M16: 2 NT)
   std::vector<TileDesc> tile;   // [iters][grid]
   std::vector<unsigned> mask;   // [mask rows][threads]: bits 0..MAXJ-1 window piece j inside the image, bit 16 + nt: pixel nt exists
   int grid = 0, threads = 0, lane_stride = 0, mask_rows = 0;
@@ -175,13 +175,92 @@ inline std::vector<int> deal_fit_pixels(int imgs, int th, int tw, int ip, int hp
   return slot;
 }
 
+// M16 (conv3x3.inc: the stage's MFMAs are 16x16x32): lane l = (column c = l & 15, group G = l >> 4) reads, per tap, the 16-byte chunk slot
+// sigma(G) = (0, 2, 1, 3)[G] of the pixel in column c of each 16-pixel tile.  A ds_read_b128 is served in four groups of 16 lanes:
+// columns X = {0-3, 12-15} of an even G with columns Y = {4-11} of the odd G beside it, and Y of the even with X of the odd.  The bank group
+// (address bits 4..7) of slot s of window pixel w is (w & 3, s ^ ((w >> 2) & 3)), and slot s ^ 2 of pixel w shares it with slot s of pixel
+// w + 8 (mod 16).  The two G of a service group differ by exactly that 2, so a 16-pixel tile is read without conflicts, at every tap shift,
+// when the window indices mod 16 of its X columns and those of its Y columns + 8 are sixteen different values.
+// deal_m16_columns places the 16 pixels of one 32x32x16 service group (they have 16 different residues wherever that dealing is
+// conflict-free) on the columns of one tile: residues r and r + 8 on the same side, two pixels of one residue on opposite sides.  For rows of
+// >= 16 consecutive pixels this is the identity but for columns 8-11 and 12-15, which trade their pixel quads.  A column without a pixel
+// (fit tiles) reads a window index < 16 of a residue that is still free.
+// win[i]: window index of pixel i of the group, or -1.  Returns col[c] = i (or -1) and fills base[c] = the window index column c reads.
+inline std::array<int, 16> deal_m16_columns(const std::array<int, 16>& win, std::array<int, 16>* base) {
+  static const int xs[8] = {0, 1, 2, 3, 12, 13, 14, 15}, ys[8] = {4, 5, 6, 7, 8, 9, 10, 11};
+  std::array<int, 16> col;
+  col.fill(-1);
+  int nx = 0, ny = 0;
+  bool used_e[16] = {false};
+  auto put = [&](int i, bool y) {
+    col[y ? ys[ny++] : xs[nx++]] = i;
+    used_e[(win[i] + (y ? 8 : 0)) & 15] = true;
+  };
+  std::vector<int> cls[8];
+  for (int i = 0; i < 16; ++i) if (win[i] >= 0) cls[win[i] & 7].push_back(i);
+  std::vector<int> left;
+  // two pixels of ONE residue: one on each side
+  for (auto& c : cls)
+    for (size_t a = 0; a < c.size(); ++a)
+      for (size_t b = a + 1; b < c.size(); ++b)
+        if (c[a] >= 0 && c[b] >= 0 && ((win[c[a]] ^ win[c[b]]) & 15) == 0 && nx < 8 && ny < 8 && !used_e[win[c[a]] & 15] && !used_e[(win[c[b]] + 8) & 15]) {
+          put(c[a], false); put(c[b], true); c[a] = c[b] = -1;
+        }
+  // residues r and r + 8: both on one side
+  for (auto& c : cls)
+    for (size_t a = 0; a < c.size(); ++a)
+      for (size_t b = a + 1; b < c.size(); ++b)
+        if (c[a] >= 0 && c[b] >= 0 && ((win[c[a]] ^ win[c[b]]) & 15) == 8) {
+          const bool fx = nx + 2 <= 8 && !used_e[win[c[a]] & 15] && !used_e[win[c[b]] & 15];
+          const bool fy = ny + 2 <= 8 && !used_e[(win[c[a]] + 8) & 15] && !used_e[(win[c[b]] + 8) & 15];
+          if (!fx && !fy) continue;
+          put(c[a], !fx); put(c[b], !fx); c[a] = c[b] = -1;
+        }
+  // singles, then whatever could not be placed without a conflict
+  for (int pass = 0; pass < 2; ++pass)
+    for (auto& c : cls)
+      for (int& i : c) {
+        if (i < 0) continue;
+        const bool fx = nx < 8 && (pass || !used_e[win[i] & 15]), fy = ny < 8 && (pass || !used_e[(win[i] + 8) & 15]);
+        if (!fx && !fy) continue;
+        put(i, !fx); i = -1;
+      }
+  for (int c = 0; c < 16; ++c) {
+    if (col[c] >= 0) { (*base)[c] = win[col[c]]; continue; }
+    const bool y = c >= 4 && c < 12;
+    int e = 0;
+    while (e < 16 && used_e[e]) ++e;
+    if (e < 16) used_e[e] = true;
+    (*base)[c] = e < 16 ? ((e + (y ? 8 : 0)) & 15) : 0;
+  }
+  return col;
+}
+// bank conflicts of the M16 window reads of one wave-instruction: extra 16-byte bank-group hits over the four service groups.  bl[l]: the
+// window index lane l reads (base_lin + tap offset).
+inline int m16_read_conflicts(const int (&bl)[64]) {
+  int extra = 0;
+  for (int sg = 0; sg < 4; ++sg) {   // service group: half-wave sg >> 1; (sg & 1) == 0: X of the even G + Y of the odd G, 1: the other way
+    int cnt[16] = {0};
+    for (int ll = 0; ll < 32; ++ll) {
+      const bool in_a = ll < 4 || (ll >= 12 && ll < 16) || (ll >= 20 && ll < 28);
+      if (in_a != ((sg & 1) == 0)) continue;
+      const int l = (sg >> 1) * 32 + ll, G = l >> 4, slot = ((G & 1) << 1) | (G >> 1), w = bl[l];
+      ++cnt[((w & 3) << 2) | (slot ^ ((w >> 2) & 3))];
+    }
+    for (int b = 0; b < 16; ++b) extra += cnt[b] > 1 ? cnt[b] - 1 : 0;
+  }
+  return extra;
+}
+
 // Returns nullptr, or the reason the shape cannot be scheduled.  `grid_override` > 0: the launch's share of a merged launch.
 // HALF: half-chunk stages of the wide stride-2 variant -- a window piece (1 KiB) is 32 pixels x 32 bytes (lane l: pixel l >> 1, landing
 // slot l & 1, which holds global slot (l & 1) ^ ((pixel >> 3) & 1)); waves pair up on pixels although each owns two cout tiles.
-template <int STRIDE, int NT, int WAVES, int ESZ, int MT, class P, bool HALF = false>
+template <int STRIDE, int NT, int WAVES, int ESZ, int MT, class P, bool HALF = false, bool M16 = false>
 const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out) {
+  static_assert(!M16 || (STRIDE == 1 && !HALF && ESZ == 2), "M16: the stride-1 bf16 kernels");
   constexpr int MAXJ = max_window_pieces<STRIDE, NT, WAVES>();
-  const int threads = WAVES * 64, stride = 3 * NT + MAXJ;
+  constexpr int NB = M16 ? 2 * NT : NT;
+  const int threads = WAVES * 64, stride = 2 * NT + NB + MAXJ;
   // Invariants the KERNEL relies on and cannot check, stated where its addresses are made:
   //  * at least two channel stages per tile: the mask word of the NEXT tile is fetched by the cursor step that enters the second stage
   //    of the current one (conv3x3.inc, `if (L_ch == 1) fetch_mask()`); with a single stage every tile after the first would reuse tile
@@ -232,13 +311,27 @@ const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out
       if (p.TW == 16) return (in_a ? 0 : 16) + rank;
       return (in_a ? 0 : 8) + (rank < 8 ? rank : rank + 8);   // TW == 8: A -> rows 0, 2; B -> rows 1, 3
     };
+    auto slot_pixel = [&](int tile32, int ll) { return p.FIT ? fit_slot[(size_t)tile32 * 32 + ll] : tile32 * 32 + lane_pos(ll); };
+    auto win_of = [&](int pidx) {
+      const int img = pidx / (p.TH * p.TW), rem = pidx % (p.TH * p.TW);
+      return img * IP + (rem / p.TW) * STRIDE * p.HP + rem % p.TW;
+    };
     for (int nt = 0; nt < NT; ++nt) {
       const int tile32 = (MT == 2 && !HALF ? wave : wave >> 1) * NT + nt;   // MT == 1 / HALF: wave pairs share pixels
-      int pidx = tile32 * 32 + lane_pos(l & 31);
-      if (p.FIT) pidx = fit_slot[(size_t)tile32 * 32 + (l & 31)];
+      int pidx = slot_pixel(tile32, l & 31);
+      if (M16) {   // 16-pixel tile 2 nt + q = the pixels of service group q of that 32-slot tile, columns dealt by deal_m16_columns
+        static const int grp[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+        for (int q = 0; q < 2; ++q) {
+          std::array<int, 16> win16, base16;
+          for (int i = 0; i < 16; ++i) { const int px = slot_pixel(tile32, grp[q][i]); win16[i] = px < 0 ? -1 : win_of(px); }
+          const std::array<int, 16> col = deal_m16_columns(win16, &base16);
+          row[NT + 2 * nt + q] = base16[l & 15];
+          if (q == ((l >> 4) & 1)) pidx = col[l & 15] < 0 ? -1 : slot_pixel(tile32, grp[q][col[l & 15]]);   // the pixel this lane stores
+        }
+      }
       if (pidx < 0) {   // FIT: a slot without a pixel -- never valid (image index IMGS), addresses harmless
         pix[(size_t)tid * NT + nt] = {0, 0, p.IMGS};
-        row[nt] = 0; row[NT + nt] = 0; row[2 * NT + nt] = 0;
+        row[nt] = 0; if (!M16) row[NT + nt] = 0; row[NT + NB + nt] = 0;
         continue;
       }
       const int img = pidx / (p.TH * p.TW), rem = pidx % (p.TH * p.TW);
@@ -247,10 +340,10 @@ const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out
       const int64_t orel = (int64_t)img * p.o_img + (int64_t)ty * p.o_row + (int64_t)tx * p.o_px;   // relative to the tile's origin
       if (orel < 0 || orel > INT32_MAX) return "conv3x3: per-lane output offset does not fit 31 bits";
       row[nt] = (int)orel;
-      row[NT + nt] = img * IP + ty * STRIDE * p.HP + tx;
+      if (!M16) row[NT + nt] = img * IP + ty * STRIDE * p.HP + tx;
       const int64_t rrel = (int64_t)img * p.o_img + (int64_t)ty * p.r_row + (int64_t)tx * p.r_px;   // the residual's own layout
       if (rrel < 0 || rrel > INT32_MAX) return "conv3x3: per-lane residual offset does not fit 31 bits";
-      row[2 * NT + nt] = (int)rrel;
+      row[NT + NB + nt] = (int)rrel;
     }
     // window DMA: instruction i = wave + WAVES*j fills LDS pixels 16i..16i+15; lane l fills LDS slot (l&3)
     // of pixel 16i + l/4 with GLOBAL slot (l&3) ^ swizzle(pixel)
@@ -265,7 +358,7 @@ const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out
       const int g = HALF ? (l & 1) ^ ((px >> 3) & 1) : (l & 3) ^ ((px >> 2) & 3);
       const int64_t roff = (int64_t)img * img_in_bytes + ((int64_t)(hy - 1) * p.Wi + hx - 1) * p.in_px_bytes + g * 16;
       if (live && (roff < INT32_MIN || roff > INT32_MAX)) return "conv3x3: per-lane window offset does not fit 32 bits";
-      row[3 * NT + j] = live ? (int)roff : 0;   // (dead pieces are never dereferenced: their mask bit is clear in every row)
+      row[2 * NT + NB + j] = live ? (int)roff : 0;   // (dead pieces are never dereferenced: their mask bit is clear in every row)
       win[(size_t)tid * MAXJ + j] = {hy, hx, img, live ? 1 : 0};
     }
   }

@@ -168,15 +168,24 @@ template <int CLS> struct TapSet {
 // instead of 37 KB for 128) and a workgroup owns 128 couts (the four 32-cout MFMA row tiles of a tap are one 4 KiB slab, so the
 // weight image per stage stays 36 + 4 KiB).  Wave = (pixel group of 64 = wave >> 1, cout half = wave & 1): MT = 2 row tiles x NT = 2
 // pixel tiles, four LDS fragment reads per four MFMAs as in the stride-1 kernel.
-template <typename T, int STRIDE, int NT, int WAVES, bool STAMP, bool DS, int MT, bool WRES = false, int CLS = -1, bool HALF = false>
+//
+// M16 (bf16, stride 1, CLS < 0): the stage's MFMAs are v_mfma_f32_16x16x32_bf16 -- one 64-byte channel chunk of a tap is ONE k-step of 32 channels
+// instead of two of 16 on 32x32x16.  Same wave tile (MT x NT blocks of 32 couts x 32 pixels = 2 x 2 tiles of 16 x 16 each), same LDS images, same
+// MFMA cycles; the smaller shape costs less energy per FLOP and the chip holds a higher clock under it (DESIGN.md 4.2).  Lane l = (column c = l & 15,
+// group G = l >> 4): operands are the 8 channels of chunk slot sigma(G) = (0, 2, 1, 3)[G] of cout 16 m + c (A) / of the pixel in column c (B);
+// D holds couts 16 m + 4 G + {0..3} of that pixel.  Which pixel a column of a 16-pixel tile stands for is dealt by the host so that the window
+// reads stay conflict-free (conv3_tables_host.h, M16).
+template <typename T, int STRIDE, int NT, int WAVES, bool STAMP, bool DS, int MT, bool WRES = false, int CLS = -1, bool HALF = false, bool M16 = false>
 __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg, const int nwg, const int n_iters, const int* __restrict__ lane_tab,
                                              const int4* __restrict__ tile_tab, const unsigned* __restrict__ mask_tab) {
   static_assert(!DS || STRIDE == 2, "the fused downsample rides on the stride-2 kernel");
   static_assert(CLS < 0 || (STRIDE == 1 && !DS && !WRES && CLS <= 4), "parity classes: stride-1 kernel, streamed weights");
   static_assert(CLS != 4 || NT == 1, "all four classes at once: four accumulator sets, 256-pixel tiles at most");
   static_assert(!HALF || (STRIDE == 2 && DS && MT == 2 && NT == 2 && WAVES == 8 && !WRES && CLS < 0 && sizeof(T) == 2), "HALF: the wide stride-2 variant");
+  static_assert(!M16 || (sizeof(T) == 2 && STRIDE == 1 && CLS < 0 && !DS && !HALF), "M16: the stride-1 bf16 kernels on whole-chunk stages");
   typedef TapSet<CLS> TS;
-  constexpr int KSTEPS = (HALF ? 1 : 2) * TS::N;   // k-steps per stage: two per tap (HALF stages: one)
+  constexpr int KSTEPS = (HALF || M16 ? 1 : 2) * TS::N;   // k-steps per stage: two per tap (HALF stages, M16: one)
+  constexpr int NB = M16 ? 2 * NT : NT;                  // window fragments (pixel tiles) per k-step
 
   static_assert(MT == 1 || MT == 2, "MT");
   constexpr int ESZ = ElemTraits<T>::ESZ;
@@ -191,6 +200,7 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   const unsigned long long t_entry = STAMP ? __builtin_readcyclecounter() : 0ull;
   const unsigned long long rt_entry = STAMP ? __builtin_amdgcn_s_memrealtime() : 0ull;  // 100 MHz
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
+  const int G = lane >> 4;   // M16: the lane's k group (operands) / group of four couts (accumulators)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int mt0 = HALF ? 2 * (wave & 1) : MT == 2 ? 0 : (wave & 1);   // first cout tile of this wave
   const int win_bytes = (p.IMGS * p.HR * p.HP + p.WTAIL) * STAGE_PX_BYTES;
@@ -206,13 +216,15 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
 
   // ---- tile-independent per-lane geometry: built once per layer shape on the HOST (integer
   // divisions by run-time tile dimensions cost ~40 VALU each; ~30 of them used to sit in this prologue)
-  int out_rel[NT], base_lin[NT], res_rel[NT], rel_off[MAXJ];
+  int out_rel[NT], base_lin[NB], res_rel[NT], rel_off[MAXJ];
   {
-    const int* row = lane_tab + tid * (3 * NT + MAXJ);
+    const int* row = lane_tab + tid * (2 * NT + NB + MAXJ);
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) { out_rel[nt] = row[nt]; base_lin[nt] = row[NT + nt]; res_rel[nt] = row[2 * NT + nt]; }
+    for (int nt = 0; nt < NT; ++nt) { out_rel[nt] = row[nt]; res_rel[nt] = row[NT + NB + nt]; }
 #pragma unroll
-    for (int j = 0; j < MAXJ; ++j) rel_off[j] = row[3 * NT + j];
+    for (int nb = 0; nb < NB; ++nb) base_lin[nb] = row[NT + nb];
+#pragma unroll
+    for (int j = 0; j < MAXJ; ++j) rel_off[j] = row[2 * NT + NB + j];
   }
 
   // ---- cursors --------------------------------------------------------------------------------
@@ -266,7 +278,7 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   // (pieces are issued one at a time between the k-steps of the compute stage's MFMAs, so the
   //  vector-memory issue cost hides under the matrix pipe)
   constexpr int NP = WJ + MAXJ + 1;
-  constexpr int DMA_SPREAD = 10;
+  constexpr int DMA_SPREAD = M16 ? 5 : 10;   // (an M16 k-step is a whole tap)
   auto dma_piece = [&](bool on, int buf, int tile_parity, int q) __attribute__((always_inline)) {
     if (!on) return;
     if ((DH_ABL & 2) && q < WJ + MAXJ) return;
@@ -294,6 +306,13 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   f32x16 acc[MT][NT];
   f32x16 acc_ds[MT][NT];  // fused 1x1 downsample (DS variants; dead otherwise)
   f32x16 acc_c[3][MT][NT];  // classes 1..3 of the all-classes stride-2 data gradient (CLS == 4; dead otherwise)
+  f32x4 acc4[MT][NT][4];    // M16: block (ml, nt) as 2 x 2 tiles of 16 couts x 16 pixels, [2 * cout half + pixel half] (acc is dead then)
+  // value 4 g + i of block (ml, nt): 32x32x16 -- cout 8 g + 4 h + i of pixel slot (nt, lane & 31); M16 -- cout 16 (g >> 1) + 4 G + i of column lane & 15
+  // of pixel tile 2 nt + (g & 1)
+  auto acc_at = [&](auto& A, int ml, int nt, int idx) __attribute__((always_inline)) -> float {
+    if constexpr (M16) return A[ml][nt][idx >> 2][idx & 3];
+    else return A[ml][nt][idx];
+  };
   auto zero_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -301,6 +320,7 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
       for (int j = 0; j < NT; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
+          if constexpr (M16) { acc4[i][j][r >> 2][r & 3] = 0.f; continue; }
           acc[i][j][r] = 0.f;
           if constexpr (DS) acc_ds[i][j][r] = 0.f;
           if constexpr (CLS == 4) { acc_c[0][i][j][r] = 0.f; acc_c[1][i][j][r] = 0.f; acc_c[2][i][j][r] = 0.f; }
@@ -326,9 +346,12 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   // would be 8-byte accesses, so the two half-waves trade halves (v_permlane32_swap): for a pair of groups
   // (2p, 2p+1) lane h=0 ends up with all 8 couts of group 2p and lane h=1 with all 8 of group 2p+1 ->
   // one 16-byte store (and one 16-byte residual load) per pair.  The swap is its own inverse.
+  // M16: the two values of a pair belong to the pixel tiles 2 nt and 2 nt + 1 and lanes G, G ^ 1 trade (v_permlane16_swap): lane G ends up with
+  // all 8 couts 16 m + 8 (G >> 1) ... of ITS pixel, the one in column lane & 15 of tile 2 nt + (G & 1) -- the same 16-byte accesses at the same
+  // "+ h * 8" (G >> 1 == h), one pixel per lane and n-tile as before.
   auto swap_pair = [&](uint32_t& a, uint32_t& b) __attribute__((always_inline)) {
-    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0]; b = r[1];
+    if constexpr (M16) { const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false); a = r[0]; b = r[1]; }
+    else { const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false); a = r[0]; b = r[1]; }
   };
   auto prefetch_residual = [&]() __attribute__((always_inline)) {  // residual tile of the COMPUTE tile
 #pragma unroll
@@ -360,7 +383,7 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   // direct: the residual is loaded here (no prefetch registers; the all-classes variant has four output tiles per window tile)
   // HR (std::true_type / false_type): with / without a residual, as two instantiations -- the choice is uniform for the launch, and as a run-time
   // test inside the element loops the compiler turned it into per-element selects (66 v_cndmask + 79 v_mov per tile on top of ~250 useful VALU)
-  auto epilogue_of = [&](auto HR, f32x16 (&A)[MT][NT], const float* ss, const T* res, bool relu, T* out, bool direct = false)
+  auto epilogue_of = [&](auto HR, auto& A, const float* ss, const T* res, bool relu, T* out, bool direct = false)
       __attribute__((always_inline)) {  // of the DONE tile
     // (std::integral_constant<int, 2>: decided at run time, as before -- the float32 and all-classes variants, whose register budget is full: the two
     // instantiations cost them 4-46 spilled registers)
@@ -386,15 +409,15 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
             if (has_res) { swap_pair(ra[0], rb[0]); swap_pair(ra[1], rb[1]); }  // back to per-lane ownership
 #pragma unroll
             for (int gg = 0; gg < 2; ++gg) {
-              const int g = 2 * pr + gg, col = mt * 32 + g * 8 + 4 * h;
+              const int g = 2 * pr + gg, col = M16 ? mt * 32 + pr * 16 + 4 * G : mt * 32 + g * 8 + 4 * h;
               const float4 sc = *reinterpret_cast<const float4*>(ss + col);       // LDS: not on the vmcnt
               const float4 sh = *reinterpret_cast<const float4*>(ss + SSH + col);  // queue of the stores
               // pairs throughout: v_pk_fma_f32, v_pk_add_f32, v_cvt_pk_bf16_f32 (RNE), v_pk_max_i16
               typedef float f32x2_t __attribute__((ext_vector_type(2)));
               typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
               typedef short i16x2_t __attribute__((ext_vector_type(2)));
-              f32x2_t v01 = __builtin_elementwise_fma(f32x2_t{A[ml][nt][4 * g + 0], A[ml][nt][4 * g + 1]}, f32x2_t{sc.x, sc.y}, f32x2_t{sh.x, sh.y});
-              f32x2_t v23 = __builtin_elementwise_fma(f32x2_t{A[ml][nt][4 * g + 2], A[ml][nt][4 * g + 3]}, f32x2_t{sc.z, sc.w}, f32x2_t{sh.z, sh.w});
+              f32x2_t v01 = __builtin_elementwise_fma(f32x2_t{acc_at(A, ml, nt, 4 * g + 0), acc_at(A, ml, nt, 4 * g + 1)}, f32x2_t{sc.x, sc.y}, f32x2_t{sh.x, sh.y});
+              f32x2_t v23 = __builtin_elementwise_fma(f32x2_t{acc_at(A, ml, nt, 4 * g + 2), acc_at(A, ml, nt, 4 * g + 3)}, f32x2_t{sc.z, sc.w}, f32x2_t{sh.z, sh.w});
               if (has_res) {
                 const uint32_t rx = gg ? rb[0] : ra[0], ry = gg ? rb[1] : ra[1];
                 v01 += f32x2_t{bf16_bits_to_f32(rx & 0xFFFFu), bf16_bits_to_f32(rx >> 16)};
@@ -421,8 +444,8 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
             const int col = mt * 32 + g * 8 + 4 * h;
             const float4 sc = *reinterpret_cast<const float4*>(ss + col);
             const float4 sh = *reinterpret_cast<const float4*>(ss + SSH + col);
-            float v[4] = {__builtin_fmaf(A[ml][nt][4 * g + 0], sc.x, sh.x), __builtin_fmaf(A[ml][nt][4 * g + 1], sc.y, sh.y),
-                          __builtin_fmaf(A[ml][nt][4 * g + 2], sc.z, sh.z), __builtin_fmaf(A[ml][nt][4 * g + 3], sc.w, sh.w)};
+            float v[4] = {__builtin_fmaf(acc_at(A, ml, nt, 4 * g + 0), sc.x, sh.x), __builtin_fmaf(acc_at(A, ml, nt, 4 * g + 1), sc.y, sh.y),
+                          __builtin_fmaf(acc_at(A, ml, nt, 4 * g + 2), sc.z, sh.z), __builtin_fmaf(acc_at(A, ml, nt, 4 * g + 3), sc.w, sh.w)};
             if (has_res) {
               if (direct) {
                 float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -452,6 +475,10 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
 #pragma unroll
       for (int c = 1; c < 4; ++c) epilogue_of(at_run_time{}, acc_c[c - 1], ss, res ? res + p.cls_base[c] : res, p.relu != 0, out + p.cls_base[c], true);
     } else if constexpr (ESZ != 2) epilogue_of(std::integral_constant<int, 2>{}, acc, ss, res, p.relu != 0, out);
+    else if constexpr (M16) {
+      if (res) epilogue_of(std::true_type{}, acc4, ss, res, p.relu != 0, out);
+      else epilogue_of(std::false_type{}, acc4, ss, res, p.relu != 0, out);
+    }
     else if (res) epilogue_of(std::true_type{}, acc, ss, res, p.relu != 0, out);
     else epilogue_of(std::false_type{}, acc, ss, res, p.relu != 0, out);
     if constexpr (DS) epilogue_of(std::false_type{}, acc_ds, ss + 2 * SSH, (const T*)nullptr, false, ds_out);  // BN only: no ReLU, no residual
@@ -469,17 +496,21 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   // registers to spare at all and keep the per-k-step form.
   constexpr bool HOIST = DH_CONV_HOIST && sizeof(T) == 2 && CLS < 0;
   static_assert(!HOIST || MAXJ * WAVES * 1024 <= 65536, "HOIST: a staged window (<= MAXJ * WAVES DMA pieces of 1 KiB) must fit 16-bit offsets");
-  constexpr int NTOFF = NT == 2 ? 9 : 5;
+  // M16: the lane reads chunk slot sigma(G) of NB pixels per tap, all 32 channels in one k-step (no parity flip): NB halves per tap, 9 NB / 2 registers
+  constexpr int NTOFF = M16 ? 9 * NB / 2 : NT == 2 ? 9 : 5;
   uint32_t toffp[NTOFF];
   {
     auto tap_off = [&](int nt, int t9) __attribute__((always_inline)) {
       const int kh = t9 / 3, kw = t9 % 3;
       const int tap_lin = STRIDE == 1 ? kh * p.HP + kw : kh * p.HP + (kw & 1) * p.HPH + (kw >> 1);
+      if constexpr (M16) return (uint32_t)lds_slot_addr(base_lin[nt] + tap_lin, ((G & 1) << 1) | (G >> 1));
       return (uint32_t)(HALF ? lds_slot_addr_half(base_lin[nt] + tap_lin, h) : lds_slot_addr(base_lin[nt] + tap_lin, h));
     };
 #pragma unroll
     for (int i = 0; i < NTOFF; ++i) {
       if constexpr (!HOIST) toffp[i] = 0u;
+      else if constexpr (M16 && NB == 4) toffp[i] = tap_off(2 * (i & 1), i >> 1) | (tap_off(2 * (i & 1) + 1, i >> 1) << 16);
+      else if constexpr (M16) toffp[i] = tap_off(0, i) | (tap_off(1, i) << 16);
       else if constexpr (NT == 2) toffp[i] = tap_off(0, i) | (tap_off(1, i) << 16);
       else toffp[i] = tap_off(0, 2 * i) | ((2 * i + 1 < 9 ? tap_off(0, 2 * i + 1) : 0u) << 16);
     }
@@ -513,6 +544,59 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
     const char* w_lds = WRES ? smem + chunk * WTOT : smem + buf * buf_bytes;
     const char* a_lds = WRES ? smem + ring_off + buf * buf_bytes : w_lds + WTOT;
     (void)chunk;
+    if constexpr (M16) {
+      // A-major: the NB window fragments of a tap stay live while the 2 MT weight fragments (16 couts x 32 channels each) pass one at a time,
+      // each read one ahead of the NB MFMAs -- on NB independent accumulators -- that it feeds.
+      static_assert(HOIST, "M16 reads the window through the hoisted offsets");
+      const unsigned wbase = lds_addr_of(a_lds);
+      auto read_b = [&](int t, uint4 (&b)[NB]) __attribute__((always_inline)) {
+        if constexpr (NB == 4) {
+          const unsigned pk0 = toffp[2 * t], pk1 = toffp[2 * t + 1];
+          b[0] = *lds_ptr128(add_half16<0>(wbase, pk0)); b[1] = *lds_ptr128(add_half16<1>(wbase, pk0));
+          b[2] = *lds_ptr128(add_half16<0>(wbase, pk1)); b[3] = *lds_ptr128(add_half16<1>(wbase, pk1));
+        } else {
+          const unsigned pk = toffp[t];
+          b[0] = *lds_ptr128(add_half16<0>(wbase, pk)); b[1] = *lds_ptr128(add_half16<1>(wbase, pk));
+        }
+      };
+      // slab image [k-step][mt][lane][16 B] of the 32x32x16 lanes: (cout c, chunk slot s) sits at k-step s >> 1, lane (s & 1) * 32 + (c & 31)
+      const char* wl = w_lds + (G & 1) * 2 * FRAG_BYTES + ((G >> 1) * 32 + (lane & 15)) * 16 + mt0 * FRAG_BYTES;
+      auto read_a = [&](int t, int m) __attribute__((always_inline)) {
+        return *reinterpret_cast<const uint4*>(wl + t * SLAB_TAP + (m >> 1) * FRAG_BYTES + (m & 1) * 256);
+      };
+      uint4 bc[NB];
+      read_b(0, bc);
+      uint4 an = read_a(0, 0);
+      __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+      for (int k = 0; k < KSTEPS; ++k) {
+        if (k == (3 * KSTEPS + 4) / 8) __builtin_amdgcn_s_setprio(2);
+        if (k == (5 * KSTEPS + 4) / 8) __builtin_amdgcn_s_setprio(1);
+        if (k == (7 * KSTEPS + 4) / 8) __builtin_amdgcn_s_setprio(0);
+        uint4 bn[NB];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) bn[n] = bc[n];
+        if (k + 1 < KSTEPS) read_b(k + 1, bn);
+#pragma unroll
+        for (int m = 0; m < 2 * MT; ++m) {
+          const uint4 ac = an;
+          if (m + 1 < 2 * MT) an = read_a(k, m + 1);
+          else if (k + 1 < KSTEPS) an = read_a(k + 1, 0);
+#pragma unroll
+          for (int n = 0; n < NB; ++n)
+            acc4[m >> 1][n >> 1][(m & 1) * 2 + (n & 1)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                __builtin_bit_cast(bf16x8, ac), __builtin_bit_cast(bf16x8, bc[n]), acc4[m >> 1][n >> 1][(m & 1) * 2 + (n & 1)], 0, 0, 0);
+        }
+        constexpr int SPREAD = KSTEPS < DMA_SPREAD ? KSTEPS : DMA_SPREAD;
+        if (k < SPREAD)
+#pragma unroll
+          for (int q = (k * NP) / SPREAD; q < ((k + 1) * NP) / SPREAD; ++q) dma_piece(dma_on, dma_buf, dma_parity, q);
+#pragma unroll
+        for (int n = 0; n < NB; ++n) bc[n] = bn[n];
+      }
+      __builtin_amdgcn_s_setprio(0);
+      return;
+    }
     int bl[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -669,9 +753,9 @@ __device__ __forceinline__ void conv3x3_body(const Conv3Params& p, const int wg,
   }
 }
 
-template <typename T, int STRIDE, int NT, int WAVES, bool STAMP, bool DS, int MT, bool WRES = false, int CLS = -1, bool HALF = false>
+template <typename T, int STRIDE, int NT, int WAVES, bool STAMP, bool DS, int MT, bool WRES = false, int CLS = -1, bool HALF = false, bool M16 = false>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void conv3x3_kernel(const Conv3Params p) {
-  conv3x3_body<T, STRIDE, NT, WAVES, STAMP, DS, MT, WRES, CLS, HALF>(p, (int)blockIdx.x, (int)gridDim.x, p.iters, p.lane_tab, p.tile_tab, p.mask_tab);
+  conv3x3_body<T, STRIDE, NT, WAVES, STAMP, DS, MT, WRES, CLS, HALF, M16>(p, (int)blockIdx.x, (int)gridDim.x, p.iters, p.lane_tab, p.tile_tab, p.mask_tab);
 }
 
 // All four parity classes of a stride-2 data gradient in ONE launch: workgroups [first[k], first[k + 1]) run class order[k] = {3, 1, 2, 0}[k]

@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <set>
@@ -37,6 +38,7 @@
 #include "conv3_tables_host.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
@@ -796,9 +798,9 @@ struct Conv3Tables { int* lane = nullptr; int4* tile = nullptr; unsigned* mask =
 std::map<std::vector<int>, Conv3Tables> g_conv3_tables;
 constexpr size_t CONV3_TABLE_CAP = 256;
 
-template <int STRIDE, int NT, int WAVES, int ESZ, int MT, bool HALF = false>
+template <int STRIDE, int NT, int WAVES, int ESZ, int MT, bool HALF = false, bool M16 = false>
 int conv3_tables(const Conv3Params& p, int ncb, int groups_img, Conv3Tables* out, int grid_override = 0) {
-  const std::vector<int> key = {current_device(), STRIDE, NT, WAVES, MT + (HALF ? 100 : 0), ESZ, p.TH, p.TW, p.IMGS, p.HR, p.HC, p.HP, p.HPH, p.Hi, p.Wi,
+  const std::vector<int> key = {current_device(), STRIDE, NT, WAVES, MT + (HALF ? 100 : 0) + (M16 ? 200 : 0), ESZ, p.TH, p.TW, p.IMGS, p.HR, p.HC, p.HP, p.HPH, p.Hi, p.Wi,
                                 p.Cin, p.B, p.tiles_y, p.tiles_x, ncb, p.n_win_instr, p.WTAIL, p.FIT, p.IP, p.in_px_bytes, p.Ho, p.Wo, p.Cout, p.out_px,
                                 p.out_cb, (int)(p.o_img & 0x7FFFFFFF), (int)(p.o_img >> 31), p.o_row, p.o_px, p.o_base, grid_override, p.iters,
                                 p.r_row, p.r_px, p.r_cb, p.r_base};
@@ -810,7 +812,7 @@ int conv3_tables(const Conv3Params& p, int ncb, int groups_img, Conv3Tables* out
     g_conv3_tables.clear();
   }
   dh_conv3::HostTables ht;   // pure integer host code (conv3_tables_host.h; swept under sanitizers by tests/test_conv_tables_host.py)
-  if (const char* why = dh_conv3::build_tables<STRIDE, NT, WAVES, ESZ, MT, Conv3Params, HALF>(p, ncb, grid_override, &ht)) { dh::set_error("%s", why); return DH_EINVAL; }
+  if (const char* why = dh_conv3::build_tables<STRIDE, NT, WAVES, ESZ, MT, Conv3Params, HALF, M16>(p, ncb, grid_override, &ht)) { dh::set_error("%s", why); return DH_EINVAL; }
   static_assert(sizeof(dh_conv3::TileDesc) == sizeof(int4), "tile descriptor = int4");
   const std::vector<int>& lane = ht.lane;
   const std::vector<dh_conv3::TileDesc>& tile = ht.tile;
@@ -828,7 +830,7 @@ int conv3_tables(const Conv3Params& p, int ncb, int groups_img, Conv3Tables* out
   return DH_OK;
 }
 
-template <typename T, int STRIDE, int NT, int WAVES, bool DS = false, int MT = 2, bool WRES = false, int CLS = -1, bool HALF = false>
+template <typename T, int STRIDE, int NT, int WAVES, bool DS = false, int MT = 2, bool WRES = false, int CLS = -1, bool HALF = false, bool M16 = false>
 int launch_conv3x3_cfg(Conv3Params& p, const ConvLayer& L, hipStream_t st) {
   constexpr int STAGE_PX_BYTES = HALF ? CHUNK_BYTES / 2 : CHUNK_BYTES, CO_BLK = HALF ? 128 : 64;
   const int win_px = p.IMGS * p.HR * p.HP + p.WTAIL;
@@ -851,7 +853,7 @@ int launch_conv3x3_cfg(Conv3Params& p, const ConvLayer& L, hipStream_t st) {
   DH_REQUIRE(!WRES || grid % (L.cout / 64) == 0, "conv3x3: resident weights need a fixed cout block per workgroup");
   p.iters = (p.ntiles + grid - 1) / grid;
   Conv3Tables tb;
-  int rc = conv3_tables<STRIDE, NT, WAVES, (int)sizeof(T), MT, HALF>(p, L.cout / CO_BLK, groups, &tb);
+  int rc = conv3_tables<STRIDE, NT, WAVES, (int)sizeof(T), MT, HALF, M16>(p, L.cout / CO_BLK, groups, &tb);
   if (rc) return rc;
   p.lane_tab = tb.lane; p.tile_tab = tb.tile; p.mask_tab = tb.mask;
   if constexpr (CLS >= 0) {   // parity class of a stride-2 data gradient: no cycle-stamped twin
@@ -860,10 +862,10 @@ int launch_conv3x3_cfg(Conv3Params& p, const ConvLayer& L, hipStream_t st) {
     DH_LAUNCH_CHECK();
     return DH_OK;
   }
-  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF>), 160 * 1024)) ||
-      (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF>), 160 * 1024))) return rc;
-  if (p.stamps) hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF>), dim3(grid), dim3(WAVES * 64), lds, st, p);
-  else hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF>), dim3(grid), dim3(WAVES * 64), lds, st, p);
+  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF, M16>), 160 * 1024)) ||
+      (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF, M16>), 160 * 1024))) return rc;
+  if (p.stamps) hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF, M16>), dim3(grid), dim3(WAVES * 64), lds, st, p);
+  else hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF, M16>), dim3(grid), dim3(WAVES * 64), lds, st, p);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -874,6 +876,16 @@ inline bool s2_wide_eligible(const ConvLayer& c1, const ConvLayer& ds, int esz, 
   static const bool on = dh::env_int("DH_CONV_S2_WIDE") != 0;
   return on && esz == 2 && c1.w2_dev && ds.w2_dev && c1.cout % 128 == 0 && Wo > 4;
 }
+
+// MFMA shape of a stride-1 bf16 layer (conv3x3.inc, M16): 16x16x32 where the same-box per-layer A/B wins (profiles/conv_mfma16.txt): 64 -> 64, 256 -> 256
+// and 512 -> 512 (-2.0 / -3.2 / -4.9 % kernel time); 128 -> 128 measured -0.9 and -0.3 % on two boxes, a wash under the stamped build, and stays on
+// 32x32x16.  A function of the channel counts ONLY -- never of B, H, W or the tile variant: one layer gives the same bits at every launch size.
+// DH_CONV_MFMA16=0: 32x32x16 everywhere; so does a -DDH_CONV_HOIST=0 build (M16 reads the window through the hoisted offsets only).
+inline bool conv3_mfma16_layer(int cin, int cout) {
+  static const bool on = dh::env_int("DH_CONV_MFMA16") != 0;
+  return DH_CONV_HOIST && on && cin == cout && (cin == 64 || cin == 256 || cin == 512);
+}
+std::atomic<int> g_last_conv3_variant{-1}, g_last_conv3_mfma{0};   // dh_debug_last_conv3: tile variant / MFMA shape (M of MxMxK) of the last 3x3 launch
 
 // CLS >= 0: parity class (CLS >> 1, CLS & 1) of a stride-2 data gradient -- `in` = dZ [B][Hi][Wi][L.cin], Ho x Wo = the class's
 // rows x columns, out = the FULL-SIZE dX [B][full_h][full_w][L.cout] (NHWC), of which the class owns pixels (2 i + py, 2 j + px).
@@ -951,17 +963,34 @@ int launch_conv3x3(const ConvLayer& L, const void* in, const void* res, void* ou
     if ((rc = maybe_sample(variant == 0 && CLS < 0))) return rc;
     // weights resident in LDS when the layer has one cout block and its slabs fit beside the window ring (bf16 64 -> 64)
     const size_t wres_lds = (size_t)L.cin * sizeof(T) / CHUNK_BYTES * 9 * SLAB_TAP + 2 * (((size_t)(p.IMGS * p.HR * p.HP + p.WTAIL) * CHUNK_BYTES + 1023) & ~(size_t)1023) + 1024;
+    g_last_conv3_variant = -1; g_last_conv3_mfma = 32;
     if constexpr (CLS >= 0)
       rc = variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, false, CLS>(p, L, st)
          : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8, false, 2, false, CLS>(p, L, st)
                         : launch_conv3x3_cfg<T, 1, 1, 8, false, 1, false, CLS>(p, L, st);
-    else if (variant == 0 && sizeof(T) == 2 && wres_lds <= 160 * 1024)
-      rc = launch_conv3x3_cfg<T, 1, 2, 8, false, 2, true>(p, L, st);
-    else
-    rc = variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8>(p, L, st)
-       : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8>(p, L, st)
-                      : launch_conv3x3_cfg<T, 1, 1, 8, false, 1>(p, L, st);
+    else {
+      constexpr bool BF16 = sizeof(T) == 2;
+      const bool wres = BF16 && variant == 0 && wres_lds <= 160 * 1024;
+      bool m16 = false;
+#if DH_CONV_HOIST
+      if constexpr (BF16) m16 = conv3_mfma16_layer(L.cin, L.cout);
+#endif
+      g_last_conv3_variant = variant; g_last_conv3_mfma = m16 ? 16 : 32;
+      if constexpr (BF16 && DH_CONV_HOIST) {
+        if (m16)
+          rc = wres         ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, true, -1, false, true>(p, L, st)
+             : variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, false, -1, false, true>(p, L, st)
+             : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8, false, 2, false, -1, false, true>(p, L, st)
+                            : launch_conv3x3_cfg<T, 1, 1, 8, false, 1, false, -1, false, true>(p, L, st);
+      }
+      if (!m16)
+        rc = wres         ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, BF16>(p, L, st)
+           : variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8>(p, L, st)
+           : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8>(p, L, st)
+                          : launch_conv3x3_cfg<T, 1, 1, 8, false, 1>(p, L, st);
+    }
   } else {
+    g_last_conv3_variant = -1; g_last_conv3_mfma = 32;
     // round 4: the wide variant (128 couts x 256 pixels per workgroup on half-chunk stages; conv3x3.inc, HALF) where its packing exists
     // (bf16 inference, fused downsample, cout % 128 == 0) and the map is at least 16 pixels wide.  DH_CONV_S2_WIDE=0: the 128-pixel kernel
     static const bool s2_wide = dh::env_int("DH_CONV_S2_WIDE") != 0;
@@ -1719,6 +1748,14 @@ extern "C" int dh_debug_stamps(int32_t enable, unsigned long long* out64_host) {
     DH_HIP(hipMemcpy(out64_host, g_stamps_dev, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     DH_HIP(hipMemset(g_stamps_dev, 0, 64 * sizeof(unsigned long long)));
   }
+  return DH_OK;
+}
+
+// Test hook: tile variant (0 / 1 / 2 = 512 / 256 / 128 pixels; -1: not a plain stride-1 launch) and MFMA shape (16: 16x16x32, 32: 32x32x16) of the
+// process's last 3x3 convolution launch.
+extern "C" int dh_debug_last_conv3(int32_t* variant, int32_t* mfma_m) {
+  DH_REQUIRE(variant && mfma_m, "dh_debug_last_conv3: null argument");
+  *variant = g_last_conv3_variant; *mfma_m = g_last_conv3_mfma;
   return DH_OK;
 }
 

@@ -143,6 +143,9 @@ int dh_debug_stem_strip_width(int32_t pooled_columns);
 /* dh_debug_stamps: switch the 3x3-conv kernel to its cycle-stamped diagnostic variant and/or read
  * (and clear) its 8x8 table of summed phase cycles; out64_host may be NULL. */
 int dh_debug_stamps(int32_t enable, unsigned long long* out64_host);
+/* dh_debug_last_conv3: what the process's last 3x3 convolution launch ran -- *variant: the stride-1 tile variant (0 / 1 / 2 = 512 / 256 / 128
+ * pixels per workgroup; -1: a stride-2 launch or a parity class of a data gradient), *mfma_m: 16 = 16x16x32 MFMAs, 32 = 32x32x16. */
+int dh_debug_last_conv3(int32_t* variant, int32_t* mfma_m);
 /* dh_debug_env_knobs: the table of every environment variable the library reads (csrc/env_knobs.h), one "NAME default lo hi read"
  * line per knob, NUL-terminated, into buf_host[cap]; INTEGRATION.md lists the same table (tests/test_abi.py compares them). */
 int dh_debug_env_knobs(char* buf_host, int64_t cap);
