@@ -1,0 +1,256 @@
+// Embedding rows for MI355X (gfx950, wave64): what a prototype (nearest-class-mean) scorer needs on top of
+// the per-tile features of dh_resnet*_features_tiles.
+//   dh_embed_normalize    row / sqrt(sum row^2): one wave per row, lane sums in column order, one butterfly over the wave
+//   dh_embed_scores       scale * feat . proto^T: a skinny f32 GEMM, 32 rows x 64 prototypes per workgroup through LDS
+//   dh_embed_class_sums   per-class sums of labelled rows in a fixed chunked order + int64 counts
+// No atomics, and every reduction has one fixed order that the launch geometry cannot change: a row's result is the same bits
+// whatever n, the row's place and the grid are (the house rule of the canvas kernels).
+//
+// The arithmetic of dh_embed_scores at the slide's size (n = 198 916, D = 2048, K = 64): 26 G FMA against 1.6 GB of feature reads.
+// The card's f32 vector peak (157.3 TFLOPS = 78.6 T FMA/s packed, half that with plain v_fma_f32) makes that 0.33-0.67 ms, its HBM
+// ~0.33 ms: the two are of one size, so plain FMAs are enough (the f32 MFMA runs at the vector peak's rate, not above it).  What
+// decides is the LDS: a thread owns 2 rows x 4 prototypes, so a float4 step along D costs 6 ds_read_b128 for 32 FMAs.  Measured:
+// 1.06 ms, 24.6 T FMA/s.
+#include <algorithm>
+
+#include "dh_common.h"
+
+namespace {
+
+constexpr int SC_ROWS = 32;    // rows of a workgroup's tile
+constexpr int SC_K = 64;       // prototypes of a workgroup's tile: all of them (K <= 64)
+constexpr int SC_CK = 64;      // columns per LDS stage (D % 64 == 0)
+constexpr int SC_LD = SC_CK + 4;   // padded row of the LDS tiles: prototype rows k, k + 1, ... start 4 banks apart
+constexpr int CHUNK = DH_EMBED_CHUNK_ROWS;
+
+// One wave per row.  Lane l adds the squares of columns l, l + 64, ... in that order; the butterfly leaves every lane with the same sum
+// (a + b == b + a).  In place is safe: a lane writes only the elements it alone reads.
+__global__ __launch_bounds__(256) void embed_normalize_kernel(const float* in, int64_t n, int D, float* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < n; row += (int64_t)gridDim.x * 4) {
+    const float* src = in + row * D;
+    float* dst = out + row * D;
+    float s = 0.f;
+    for (int c = lane; c < D; c += 64) { const float v = src[c]; s = __builtin_fmaf(v, v, s); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float norm = sqrtf(s);
+    for (int c = lane; c < D; c += 64) { const float v = src[c]; dst[c] = s > 0.f ? v / norm : 0.f; }
+  }
+}
+
+// The global loads of one LDS stage (columns c0 .. c0 + 63): float4 number q of a tile is (row q / 16, columns 4 (q % 16) ..); a thread
+// moves numbers tid and tid + 256 of the features and tid + 256 j, j < 4, of the prototypes.  Rows past n and prototypes past K are
+// loaded from the last real one (in bounds) and zeroed.
+struct ScStage { float4 f0, f1, p0, p1, p2, p3; };
+__device__ __forceinline__ float4 sc_load(const float* __restrict__ base, int64_t row, int64_t last, int D, int col) {
+  const float4 v = *reinterpret_cast<const float4*>(base + (row <= last ? row : last) * D + col);
+  return row <= last ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ ScStage sc_fetch(const float* __restrict__ feat, const float* __restrict__ proto, int64_t n, int D, int K,
+                                            int64_t row0, int c0, int tid) {
+  const int r = tid >> 4, col = c0 + (tid & 15) * 4;
+  ScStage g;
+  g.f0 = sc_load(feat, row0 + r, n - 1, D, col);
+  g.f1 = sc_load(feat, row0 + r + 16, n - 1, D, col);
+  g.p0 = sc_load(proto, r, K - 1, D, col);
+  g.p1 = sc_load(proto, r + 16, K - 1, D, col);
+  g.p2 = sc_load(proto, r + 32, K - 1, D, col);
+  g.p3 = sc_load(proto, r + 48, K - 1, D, col);
+  return g;
+}
+
+// One workgroup per 32 rows.  Thread (rt = tid / 16, kt = tid % 16) owns rows rt and rt + 16 of the tile and prototypes kt, kt + 16,
+// kt + 32, kt + 48: eight accumulators, each ONE chain of fused multiply-adds over c = 0 .. D - 1 in ascending order.  Feature and
+// prototype columns go through LDS 64 at a time; the next stage's global loads are issued before the current stage's arithmetic.
+// Rows past n and prototypes past K are zero in LDS and never stored.
+__global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                           const float* __restrict__ proto, int K, float scale,
+                                                           float* __restrict__ scores) {
+  __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
+  __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
+  const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
+  const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  ScStage g = sc_fetch(feat, proto, n, D, K, row0, 0, tid);
+  float* const st_f = &s_f[rt * SC_LD + kt * 4];   // where this thread parks its loads: (row tid / 16 [+ 16 j], columns 4 (tid % 16) ..)
+  float* const st_p = &s_p[rt * SC_LD + kt * 4];
+  for (int c0 = 0; c0 < D; c0 += SC_CK) {
+    __syncthreads();   // the previous stage's readers are done
+    *reinterpret_cast<float4*>(st_f) = g.f0;
+    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = g.f1;
+    *reinterpret_cast<float4*>(st_p) = g.p0;
+    *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
+    *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
+    *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
+    __syncthreads();
+    if (c0 + SC_CK < D) g = sc_fetch(feat, proto, n, D, K, row0, c0 + SC_CK, tid);
+    if (kt < K) {   // a thread none of whose prototypes exists (K <= 16 leaves kt >= K idle) has nothing to add
+#pragma unroll 4
+      for (int c = 0; c < SC_CK; c += 4) {
+        float4 f[2], p[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(rt + 16 * i) * SC_LD + c]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const float4*>(&s_p[(kt + 16 * j) * SC_LD + c]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float t = acc[i][j];
+            t = __builtin_fmaf(f[i].x, p[j].x, t);
+            t = __builtin_fmaf(f[i].y, p[j].y, t);
+            t = __builtin_fmaf(f[i].z, p[j].z, t);
+            t = __builtin_fmaf(f[i].w, p[j].w, t);
+            acc[i][j] = t;
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t row = row0 + rt + 16 * i;
+    if (row >= n) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = kt + 16 * j;
+      if (k < K) scores[row * K + k] = scale * acc[i][j];
+    }
+  }
+}
+
+// Stage 1, one workgroup per (chunk of 1024 rows, slab of 256 columns).  The chunk's labels are sorted by class in LDS, stably (thread k
+// scans them in row order), so class k's rows are idx[start[k] .. start[k + 1]) in ascending order; thread c then adds, class by class,
+// those rows' column c into ONE accumulator from 0 and writes partial[chunk][k][c], zeros included.  The slab-0 workgroup also writes the
+// chunk's per-class row counts (int32, behind the partials).
+__global__ __launch_bounds__(256) void embed_class_partial_kernel(const float* __restrict__ feat, const int32_t* __restrict__ label,
+                                                                  int64_t n, int D, int K, float* __restrict__ partial,
+                                                                  int32_t* __restrict__ chunk_count) {
+  __shared__ int32_t s_lab[CHUNK];
+  __shared__ int32_t s_idx[CHUNK];
+  __shared__ int32_t s_cnt[64], s_start[65];
+  const int tid = threadIdx.x;
+  const int64_t chunk = blockIdx.x, base = chunk * CHUNK;
+  const int rows = (int)std::min<int64_t>(CHUNK, n - base);
+  for (int r = tid; r < rows; r += 256) s_lab[r] = label[base + r];
+  __syncthreads();
+  if (tid < K) {
+    int cnt = 0;
+    for (int r = 0; r < rows; ++r) cnt += s_lab[r] == tid ? 1 : 0;
+    s_cnt[tid] = cnt;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int p = 0;
+    for (int k = 0; k < K; ++k) { s_start[k] = p; p += s_cnt[k]; }
+    s_start[K] = p;   // <= rows
+  }
+  __syncthreads();
+  if (tid < K) {
+    int p = s_start[tid];
+    for (int r = 0; r < rows; ++r)
+      if (s_lab[r] == tid) s_idx[p++] = r;
+    if (blockIdx.y == 0) chunk_count[chunk * K + tid] = s_cnt[tid];
+  }
+  __syncthreads();
+  const int c = blockIdx.y * 256 + tid;
+  if (c >= D) return;
+  const float* col = feat + base * D + c;
+  for (int k = 0; k < K; ++k) {
+    const int beg = s_start[k], end = s_start[k + 1];
+    float acc = 0.f;
+    int j = beg;
+    for (; j + 8 <= end; j += 8) {   // eight loads in flight, added in row order
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)s_idx[j + u] * D];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc = acc + v[u];
+    }
+    for (; j < end; ++j) acc = acc + col[(int64_t)s_idx[j] * D];
+    partial[(chunk * K + k) * D + c] = acc;
+  }
+}
+
+// Stage 2, one thread per (class, column): the partials of all chunks, added in ascending chunk order from 0; the first K threads also
+// add up the counts.
+__global__ __launch_bounds__(256) void embed_class_final_kernel(const float* __restrict__ partial, const int32_t* __restrict__ chunk_count,
+                                                                int64_t n_chunks, int D, int K, float* __restrict__ sums,
+                                                                int64_t* __restrict__ counts) {
+  const int i = blockIdx.x * 256 + threadIdx.x;   // K * D <= 64 * 4096
+  if (i < K * D) {
+    float acc = 0.f;
+    for (int64_t ch = 0; ch < n_chunks; ++ch) acc = acc + partial[ch * K * D + i];
+    sums[i] = acc;
+  }
+  if (i < K) {
+    int64_t cnt = 0;
+    for (int64_t ch = 0; ch < n_chunks; ++ch) cnt += chunk_count[ch * K + i];
+    counts[i] = cnt;
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int check_dims(const char* what, int64_t n, int32_t D, int32_t K) {
+  DH_REQUIRE(n >= 0 && n <= ((int64_t)1 << 40), "%s: n = %lld out of range [0, 2^40]", what, (long long)n);
+  DH_REQUIRE(D >= 64 && D <= 4096 && D % 64 == 0, "%s: D = %d unsupported (64 <= D <= 4096, D %% 64 == 0)", what, D);
+  DH_REQUIRE(K >= 1 && K <= 64, "%s: K = %d out of range [1, 64]", what, K);
+  return DH_OK;
+}
+
+}  // namespace
+
+extern "C" int dh_embed_normalize(const float* in, int64_t n, int32_t D, float* out, void* stream) {
+  if (int rc = check_dims("dh_embed_normalize", n, D, 1)) return rc;
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(in && out, "dh_embed_normalize: null in_dev or out_dev");
+  DH_REQUIRE(aligned16(in) && aligned16(out), "dh_embed_normalize: in_dev / out_dev not 16-byte aligned");
+  const int grid = (int)std::min<int64_t>((n + 3) / 4, 1 << 20);
+  hipLaunchKernelGGL(embed_normalize_kernel, dim3(grid), dim3(256), 0, dh::as_stream(stream), in, n, D, out);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_embed_scores(const float* feat, int64_t n, int32_t D, const float* proto, int32_t K, float scale, float* scores,
+                               void* stream) {
+  if (int rc = check_dims("dh_embed_scores", n, D, K)) return rc;
+  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_scores: n = %lld exceeds one launch", (long long)n);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(feat && proto && scores, "dh_embed_scores: null feat_dev, proto_dev or scores_dev");
+  DH_REQUIRE(aligned16(feat) && aligned16(proto), "dh_embed_scores: feat_dev / proto_dev not 16-byte aligned");
+  const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
+  hipLaunchKernelGGL(embed_scores_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, proto, K, scale, scores);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int64_t dh_embed_class_work_size(int64_t n, int32_t D, int32_t K) {
+  if (check_dims("dh_embed_class_work_size", n, D, K)) return -1;
+  const int64_t n_chunks = (n + CHUNK - 1) / CHUNK;
+  return std::max<int64_t>(4, n_chunks * K * ((int64_t)D + 1));   // partials float32[n_chunks][K][D], then counts int32[n_chunks][K]
+}
+
+extern "C" int dh_embed_class_sums(const float* feat, const int32_t* label, int64_t n, int32_t D, int32_t K, float* sums,
+                                   int64_t* counts, float* work, void* stream) {
+  if (int rc = check_dims("dh_embed_class_sums", n, D, K)) return rc;
+  const int64_t n_chunks = (n + CHUNK - 1) / CHUNK;
+  DH_REQUIRE(n_chunks <= 0x7fffffff, "dh_embed_class_sums: n = %lld exceeds one launch", (long long)n);
+  DH_REQUIRE(sums && counts && work, "dh_embed_class_sums: null sums_dev, counts_dev or work_dev");
+  DH_REQUIRE(n == 0 || (feat && label), "dh_embed_class_sums: null feat_dev or label_dev");
+  hipStream_t st = dh::as_stream(stream);
+  int32_t* chunk_count = reinterpret_cast<int32_t*>(work + n_chunks * K * D);
+  if (n_chunks) {
+    hipLaunchKernelGGL(embed_class_partial_kernel, dim3((unsigned)n_chunks, (D + 255) / 256), dim3(256), 0, st, feat, label, n, D, K,
+                       work, chunk_count);
+    DH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(embed_class_final_kernel, dim3((K * D + 255) / 256), dim3(256), 0, st, work, chunk_count, n_chunks, D, K, sums,
+                     counts);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}

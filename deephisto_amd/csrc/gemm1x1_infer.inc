@@ -169,8 +169,12 @@ __global__ __launch_bounds__(256, NMT == 2 ? 4 : 2) void gemm1x1_infer_kernel(co
 // Global average pool over the 2048 channels of the last block (blocked layout) + fc, one workgroup per image: thread t owns channels
 // 8t .. 8t+7 and adds the pixels in index order; the fc dot products are summed per thread (8 channels), per wave (shuffle tree) and over
 // the 4 waves in a fixed order.  No atomics: the logits of an image do not depend on the launch.
+// FEAT: the pooled vector also goes to feat[image][2048] (dh_resnet50_features_tiles), and a null `logits` skips the fc; pooled values
+// and logits are those of the FEAT = false instantiation, which forward / forward_tiles launch.
+template <bool FEAT = false>
 __global__ __launch_bounds__(256) void r50_head_kernel(const bf16_t* __restrict__ in, int HW, const float* __restrict__ fc_w,
-                                                       const float* __restrict__ fc_b, int n_cls, float* __restrict__ logits) {
+                                                       const float* __restrict__ fc_b, int n_cls, float* __restrict__ logits,
+                                                       float* __restrict__ feat = nullptr) {
   constexpr int C = 2048;
   __shared__ float red[4];
   const int b = blockIdx.x, tid = threadIdx.x, c0 = tid * 8;
@@ -187,6 +191,12 @@ __global__ __launch_bounds__(256) void r50_head_kernel(const bf16_t* __restrict_
   const float inv = 1.0f / (float)HW;
 #pragma unroll
   for (int e = 0; e < 8; ++e) s[e] *= inv;
+  if constexpr (FEAT) {
+    float4* dst = reinterpret_cast<float4*>(feat + (int64_t)b * C + c0);
+    dst[0] = make_float4(s[0], s[1], s[2], s[3]);
+    dst[1] = make_float4(s[4], s[5], s[6], s[7]);
+    if (!logits) return;   // uniform for the launch
+  }
   for (int k = 0; k < n_cls; ++k) {
     const float* wk = fc_w + (int64_t)k * C + c0;
     const float4 w0 = *reinterpret_cast<const float4*>(wk), w1 = *reinterpret_cast<const float4*>(wk + 4);

@@ -113,7 +113,7 @@ int r50_gemm(const ConvLayer& L, const bf16_t* in, const bf16_t* res, bf16_t* ou
 }
 
 int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w, const int32_t* yx,
-                     int B, int P, float* logits, hipStream_t st, Tap* tap = nullptr) {
+                     int B, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
   const int H2 = P / 4;   // stem 7x7/2 -> P/2, maxpool 3x3/2 -> P/4 (P % 32 == 0)
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t px = (size_t)B * H2 * H2 * 2;   // bytes per channel of a stage-1 map
@@ -157,7 +157,10 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
     if ((rc = tap_after<__bf16>(tap, c3.name, X, c3.cout, Ho, Ho, 32, st))) return rc;
     H = Ho;
   }
-  hipLaunchKernelGGL(r50_head_kernel, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits);
+  if (feat)   // dh_resnet50_features_tiles: the same head, the pooled vector stored as well
+    hipLaunchKernelGGL(r50_head_kernel<true>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits, feat);
+  else
+    hipLaunchKernelGGL(r50_head_kernel<false>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -281,6 +284,27 @@ extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide,
                "the %lldx%lld slide", (long long)i, y, x, P, (long long)h, (long long)w);
   }
   return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st);
+}
+
+// forward_tiles with the pooled 2048-vector of every tile stored as well (the tap one step before the logits); logits may be NULL.
+// feat_dev must be 16-byte aligned (rows of 2048 floats are written as float4).
+extern "C" int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                                          int32_t P, float* feat, float* logits, void* stream) {
+  if (int rc = r50_check_forward(net, n, P, feat, "resnet50 features_tiles")) return rc;
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(slide && yx, "resnet50 features_tiles: null slide or origins");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(feat) & 15) == 0, "resnet50 features_tiles: feat_dev is not 16-byte aligned");
+  DH_REQUIRE(h >= P && w >= P, "resnet50 features_tiles: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
+  hipStream_t st = dh::as_stream(stream);
+  net->yx_host.resize((size_t)n * 2);
+  DH_HIP(hipMemcpyAsync(net->yx_host.data(), yx, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  DH_HIP(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t y = net->yx_host[2 * i], x = net->yx_host[2 * i + 1];
+    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "resnet50 features_tiles: origin %lld (y=%d, x=%d) puts a %d-pixel tile "
+               "outside the %lldx%lld slide", (long long)i, y, x, P, (long long)h, (long long)w);
+  }
+  return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, nullptr, feat);
 }
 
 // Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (Tap above), and a conv's

@@ -457,12 +457,14 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ in, 
 
 // ---------------------------------------------------------------------------
 // global average pool + fc: one workgroup per image; f32 arithmetic.
+// FEAT: the pooled vector also goes to feat[image][C] (dh_resnet18_features_tiles), and a null `logits` skips the fc; the pooled
+// values and the logits are those of the FEAT = false instantiation, which forward / forward_tiles launch.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool FEAT = false>
 __global__ __launch_bounds__(256) void avgpool_fc_kernel(const T* __restrict__ in, int HW, int C, int blocked,
                                                          const float* __restrict__ fc_w,
                                                          const float* __restrict__ fc_b, int n_cls,
-                                                         float* __restrict__ logits) {
+                                                         float* __restrict__ logits, float* __restrict__ feat = nullptr) {
   // one workgroup per image; lane = 16 bytes of channels, waves split the pixels (C == 512:
   // bf16 -> 64 lanes x 8 channels per pixel; f32 -> 128 lanes x 4 channels, 2 pixel groups)
   constexpr int EPV = 16 / (int)sizeof(T);
@@ -498,6 +500,10 @@ __global__ __launch_bounds__(256) void avgpool_fc_kernel(const T* __restrict__ i
     float t = 0.f;
     for (int g = 0; g < groups; ++g) t += part[g][c];
     pooled[c] = t * inv;
+    if constexpr (FEAT) feat[(int64_t)b * C + c] = t * inv;
+  }
+  if constexpr (FEAT) {
+    if (!logits) return;   // uniform for the launch
   }
   __syncthreads();
   for (int k = 0; k < n_cls; ++k) {
@@ -1302,7 +1308,7 @@ int tap_check(const int32_t* sel_dev, int32_t k, int64_t n, float* out_dev, cons
 
 template <typename T>
 int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
-                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st, Tap* tap = nullptr) {
+                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
   const int B = (int)n64;
   const int esz = (int)sizeof(T);
   const int H1 = (P + 6 - 7) / 2 + 1;       // stem out
@@ -1415,8 +1421,12 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
       ci += has_ds ? 3 : 2;
     }
   }
-  hipLaunchKernelGGL((avgpool_fc_kernel<T>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
-                     512, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits);
+  if (feat)   // dh_resnet18_features_tiles: the same head, the pooled vector stored as well
+    hipLaunchKernelGGL((avgpool_fc_kernel<T, true>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
+                       512, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
+  else
+    hipLaunchKernelGGL((avgpool_fc_kernel<T, false>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
+                       512, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -1556,6 +1566,22 @@ extern "C" int dh_resnet18_forward_tiles(dh_resnet18* net, const uint8_t* slide,
   return net->dtype == DH_DTYPE_F32
              ? forward_impl<float>(net, nullptr, slide, h, w, yx, n, P, logits, st)
              : forward_impl<__bf16>(net, nullptr, slide, h, w, yx, n, P, logits, st);
+}
+
+// forward_tiles with the pooled 512-vector of every tile stored as well (the tap one step before the logits); logits may be NULL
+extern "C" int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
+                                          const int32_t* yx, int64_t n, int32_t P, float* feat, float* logits,
+                                          void* stream) {
+  int rc = check_forward_args(net, n, P, feat);
+  if (rc) return rc;
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(slide && yx, "resnet18 features_tiles: null slide or origins");
+  DH_REQUIRE(h >= P && w >= P, "resnet18 features_tiles: patch %d does not fit %lldx%lld", P,
+             (long long)h, (long long)w);
+  hipStream_t st = dh::as_stream(stream);
+  return net->dtype == DH_DTYPE_F32
+             ? forward_impl<float>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat)
+             : forward_impl<__bf16>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat);
 }
 
 // ---------------------------------------------------------------------------

@@ -10,6 +10,9 @@ the fast path used by bench.py, and `predict_random_patched(...)`; `ImagePredict
 slide's polygon annotation; the CLI does so with `--anno PATH [--score_json PATH]`.
 `extract_regions(pred, ...)` (deephisto_amd.regions) lists a map's connected regions, removes the small
 ones and traces them into polygons; the CLI does so with `--regions_json`, `--min_region [--clean_rounds]`, `--export_anno`.
+`extract_embeddings(sampler, model, ...)` (deephisto_amd.embeddings) hands out the per-tile feature vectors of
+the same plan, and `PrototypeClassifier` scores them against class prototypes; the CLI does so with `--save_embeddings PATH` and
+`--prototypes PATH`.
 `main` calls `predict_full_patched` and `predict_random_patched` through this module's globals (tests replace them here).
 """
 from __future__ import annotations
@@ -23,6 +26,7 @@ import torch
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, check  # noqa: F401  (exported here)
 from ..anno.utils import AnnoDescription
+from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embeddings, tile_labels  # noqa: F401  (exported here)
 from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
@@ -309,6 +313,23 @@ def _proba_from_args(ap, args) -> None:
             ap.error(f"--heat labels must be out of {', '.join(KNOWN_COLORS)}, not {lb!r}")
 
 
+def _embeddings_from_args(ap, args) -> None:
+    """Checks --save_embeddings / --prototypes; a bad combination is an argparse error."""
+    for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes)):
+        if not value:
+            continue
+        if args.random_sampler:
+            ap.error(f"{flag} works on the dense sampler's grid; it cannot be combined with --random_sampler")
+        if args.ondisk:
+            ap.error(f"{flag} needs the slide resident in HBM; it cannot be combined with --ondisk")
+        if args.tta != "off":
+            ap.error(f"{flag} stores one forward pass per tile; it cannot be combined with --tta")
+        if args.proba:
+            ap.error(f"{flag} finishes the class map from the stored logits; it cannot be combined with --proba")
+    if args.prototypes and not args.anno and not Path(args.prototypes).is_file():
+        ap.error(f"--prototypes {args.prototypes}: no such file (with --anno the prototypes are fitted and written there)")
+
+
 def _regions_from_args(ap, args) -> None:
     """Checks the region flags; a bad combination is an argparse error."""
     if args.clean_rounds is not None and args.min_region is None:
@@ -375,6 +396,12 @@ def _build_parser():
                     help="regions below CELLS cells take their large neighbours' class; writes {stem}_clean_mask.jpg, {stem}_clean_overlay.jpg")
     ap.add_argument("--clean_rounds", type=int, default=None, metavar="R", help="with --min_region: cleanup rounds (default 1)")
     ap.add_argument("--export_anno", default=None, metavar="PATH", help="the regions as polygons in the annotation's JSON format (rank 0)")
+    ap.add_argument("--save_embeddings", default=None, metavar="PATH",
+                    help="every classified tile's pooled feature vector (512 / 2048 floats), origins and logits as one .npz (rank 0); "
+                         "the class map comes from the same forward pass (dense branch, resident slide)")
+    ap.add_argument("--prototypes", default=None, metavar="PATH",
+                    help="nearest-class-mean scoring of the tile embeddings: with --anno, fit the class prototypes on this slide's "
+                         "annotated tiles and write them to PATH; without, load PATH and write {stem}_prototype_map.jpg")
     return ap
 
 
@@ -390,6 +417,7 @@ def _check_args(ap, args, model=None) -> None:
     args.tta_aug = _tta_from_args(ap, args, model)
     args.anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
+    _embeddings_from_args(ap, args)
 
 
 def _run(args, model, device, rank, world):
@@ -432,9 +460,21 @@ def _run(args, model, device, rank, world):
                                     mode=mode, stride=args.stride, device=device)
         info: dict = {}
         qinfo: dict = {}
-        out = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
-                                   tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug,
-                                   quality=args.quality_filter, quality_info=qinfo)
+        args.embeddings = None
+        if args.save_embeddings or args.prototypes:
+            # the same plan through the features entry; the map is finished from that pass's logits by predict_full_patched's tail
+            filt = args.quality_filter if args.quality_filter is not None else args.tissue_filter
+            emb = args.embeddings = extract_embeddings(smp, model, tissue=args.tissue_filter, tissue_info=info,
+                                                       quality=args.quality_filter, quality_info=qinfo, return_logits=True)
+            out = emb.class_map(args.downscale_vis, fill_class=-1 if filt is None else filt.fill_class)
+            if args.save_embeddings and rank == 0:
+                Path(args.save_embeddings).parent.mkdir(parents=True, exist_ok=True)
+                emb.save(args.save_embeddings)
+                print(f"embeddings: {len(emb)} tiles x {emb.width} floats -> {args.save_embeddings}", flush=True)
+        else:
+            out = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
+                                       tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug,
+                                       quality=args.quality_filter, quality_info=qinfo)
         pred, proba = out if args.proba else (out, None)
         if args.tissue_filter is not None and rank == 0:
             print(f"kept {info['n_kept']} of {info['n_tiles']} tiles, threshold {info['threshold']}", flush=True)
@@ -478,6 +518,29 @@ def _save_quality(path, filt: QualityFilter, qinfo: dict) -> None:
     Path(path).write_text(json.dumps(doc, indent=1) + "\n")
 
 
+def _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device) -> None:
+    """--prototypes: with --anno, fit the class prototypes on this slide's annotated tiles (the label of a tile is the annotation's
+    at the cell under its centre) and save them; without, load them and write the prototype class map over the slide."""
+    emb, n_cls = args.embeddings, len(anno_dsc.anno_classes)
+    if args.anno_records is not None:
+        truth, _ = rasterize_annotation(args.anno_records, anno_dsc, args.layer, smp.h, smp.w, args.downscale_vis, device=device)
+        pc = PrototypeClassifier(n_cls).fit(emb, tile_labels(emb, truth, args.downscale_vis))
+        Path(args.prototypes).parent.mkdir(parents=True, exist_ok=True)
+        pc.save(args.prototypes)
+        print(f"prototypes: {int(pc.counts.sum())} labelled tiles, per class {pc.counts.tolist()}, empty {pc.empty_classes} "
+              f"-> {args.prototypes}", flush=True)
+        return
+    pc = PrototypeClassifier.load(args.prototypes, device=device)
+    if pc.n_classes != n_cls or pc.prototypes.shape[1] != emb.width:
+        raise ValueError(f"--prototypes {args.prototypes}: {pc.n_classes} classes x {pc.prototypes.shape[1]} floats do not fit this "
+                         f"model and description ({n_cls} x {emb.width})")
+    pmap = pc.predict_map(emb, args.downscale_vis)
+    if not args.no_visualizations:
+        _, _, overlay = perform_and_save_visualizations(src, anno_dsc, pmap, stem=stem, save=False, device=device)
+        out_dir.mkdir(exist_ok=True, parents=True)
+        _save_jpeg(overlay, out_dir / f"{stem}_prototype_map.jpg")
+
+
 def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
     """What rank 0, where the map is whole, prints and writes after the prediction: the score, the JPEGs, the probability
     files, then the regions with the cleaned map's score and JPEGs."""
@@ -497,6 +560,8 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
                                         proba=proba, heat_classes=args.heat, truth=truth, outcome=outcome)
     if args.save_proba:
         save_proba(args.save_proba, proba)
+    if args.prototypes:
+        _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device)
     if not (args.regions_json or args.min_region is not None or args.export_anno):
         return
     res = extract_regions(pred, anno_dsc, args.layer, args.downscale_vis, min_cells=args.min_region or 0,
@@ -556,6 +621,12 @@ def main(argv=None, model=None):
     `--stain macenko` normalises the slide's stain appearance first (resident slide): the prediction, the
     tissue filter and the overlays all read the normalised slide; `--stain_target PATH` takes another slide's saved fit as the
     target instead of the default constants, `--save_stain_fit PATH` writes this slide's fit (rank 0).
+    `--save_embeddings PATH` writes every classified tile's pooled feature vector, origin, grid index and logits as one `.npz`
+    (rank 0; `SlideEmbeddings.load`); the class map is finished from the logits of that same forward pass
+    and is the map of a run without the flag, bit for bit.  `--prototypes PATH` with `--anno` fits one prototype per class on this
+    slide's annotated tiles and writes them; without `--anno` it loads them and writes `{stem}_prototype_map.jpg`, the
+    nearest-prototype class of every cell over the slide.  Both take the dense branch and a resident slide and are refused with
+    `--random_sampler`, `--ondisk`, `--tta` and `--proba`.
     `model`: an injected module (tests)."""
     from ..distributed import finalize, init_from_env
     from ..models.patch_cls_simple import utils

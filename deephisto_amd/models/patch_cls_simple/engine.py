@@ -346,6 +346,17 @@ class ResNetHIP(nn.Module):
         name = f"{self.ABI}_forward_tiles"
         return getattr(lib(), name), name
 
+    @property
+    def feature_width(self) -> int:
+        """Length of a tile's pooled feature vector, the input of `fc`: 512 (ResNet-18) or 2048 (ResNet-50)."""
+        return int(self.fc.in_features)
+
+    def features_entry(self):
+        """(ctypes entry, its name) of the fused gather + forward that also stores every tile's pooled features
+        (extract_embeddings' launches)."""
+        name = f"{self.ABI}_features_tiles"
+        return getattr(lib(), name), name
+
     def default_micro_batch(self) -> int:
         """Tiles per launch of the whole-slide paths: the most one inference launch takes."""
         return self.MAX_TILES
@@ -367,6 +378,27 @@ class ResNetHIP(nn.Module):
         check(fwd(h, slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n, int(patch),
                   out.data_ptr(), _stream(slide.device)), name)
         return out
+
+    def features_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, return_logits: bool = False):
+        """forward_tiles one step earlier: float32[n, feature_width], the global average pool of every tile's last activation (what
+        `fc` reads), in one launch; with `return_logits` also the float32[n, n_classes] logits of forward_tiles, bit for bit
+        (without it the fc is skipped)."""
+        if self.training:
+            raise NotImplementedError("features_tiles is an inference entry point; call .eval()")
+        if not (slide.is_cuda and origins_dev.is_cuda):
+            raise RuntimeError("slide and origins must live in GPU memory")
+        if slide.dtype != torch.uint8 or slide.dim() != 3 or not slide.is_contiguous():
+            raise ValueError("slide must be contiguous uint8[h, w, 3]")
+        if origins_dev.dtype != torch.int32 or origins_dev.dim() != 2 or origins_dev.shape[-1] != 2 or not origins_dev.is_contiguous():
+            raise ValueError("origins must be contiguous int32[n, 2]")
+        h = self.lane_handles(1)[0]
+        n = int(origins_dev.shape[0])
+        feat = torch.empty((n, self.feature_width), dtype=torch.float32, device=slide.device)
+        logits = torch.empty((n, self.n_classes), dtype=torch.float32, device=slide.device) if return_logits else None
+        fwd, name = self.features_entry()
+        check(fwd(h, slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n, int(patch),
+                  feat.data_ptr(), logits.data_ptr() if return_logits else None, _stream(slide.device)), name)
+        return (feat, logits) if return_logits else feat
 
     def forward_infer(self, x: torch.Tensor) -> torch.Tensor:
         """float32[n, 3, P, P] in [0, 1] on the GPU -> logits through the inference handle (`<ABI>_forward`): the same function as

@@ -297,6 +297,40 @@ int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64_
                               const int32_t* yx_dev, int64_t n, int32_t patch, float* logits_dev,
                               void* stream);
 
+/* ---- tile embeddings: the pooled features one step before the logits ----------
+ * forward_tiles with the global average pool of every tile's last stored activation written out as well:
+ * feat_dev[i][c] = mean over the pixels of channel c (torchvision's channel order), float32[n][512] for ResNet-18 and
+ * float32[n][2048] for ResNet-50 (16-byte aligned there).  Summation order and the 1/HW multiply are those of the head of
+ * forward_tiles, so logits_dev (float32[n][n_classes]) receives the bits forward_tiles writes; with logits_dev == NULL the
+ * fc is skipped.  Every argument check of the forward_tiles sibling applies (patch, launch limits, origins). */
+int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide_dev, int64_t h, int64_t w,
+                               const int32_t* yx_dev, int64_t n, int32_t patch, float* feat_dev,
+                               float* logits_dev, void* stream);
+int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64_t h, int64_t w,
+                               const int32_t* yx_dev, int64_t n, int32_t patch, float* feat_dev,
+                               float* logits_dev, void* stream);
+
+/* ---- e2: embedding rows: normalise, prototype scores, per-class sums -----------
+ * Row-major float32 on the device, no atomics.  A row's result depends on that row alone: not on n, not on the
+ * row's place in the launch, not on the grid.  D % 64 == 0 and 64 <= D <= 4096, 1 <= K <= 64; float pointers are
+ * 16-byte aligned.  Anything else is refused with DH_EINVAL and the argument's name in dh_last_error().  n = 0 is allowed.
+ * dh_embed_normalize: out[i] = in[i] / sqrt(sum_c in[i][c]^2); a row whose sum of squares is 0 stays all zero.
+ *   out_dev may be in_dev (in place); any other overlap is undefined.
+ * dh_embed_scores: scores[i][k] = scale * sum_c feat[i][c] * proto[k][c], one fused multiply-add per c in ascending c
+ *   from 0; proto_dev float32[K][D], scores_dev float32[n][K].
+ * dh_embed_class_sums: sums_dev[k] (float32[K][D]) = the sum of the rows i with label_dev[i] == k (int32[n]; labels
+ *   outside [0, K), -1 among them, are ignored), counts_dev[k] (int64[K]) their number.  The order is the contract:
+ *   rows are cut into chunks of DH_EMBED_CHUNK_ROWS; a chunk's partial starts at 0 and adds its rows in ascending
+ *   order; the result starts at 0 and adds the partials of ALL chunks in ascending chunk order (float32 throughout).
+ *   work_dev: float32[dh_embed_class_work_size(n, D, K)] scratch (16-byte aligned); the size is -1 for bad arguments. */
+#define DH_EMBED_CHUNK_ROWS 1024
+int dh_embed_normalize(const float* in_dev, int64_t n, int32_t D, float* out_dev, void* stream);
+int dh_embed_scores(const float* feat_dev, int64_t n, int32_t D, const float* proto_dev, int32_t K, float scale,
+                    float* scores_dev, void* stream);
+int64_t dh_embed_class_work_size(int64_t n, int32_t D, int32_t K);
+int dh_embed_class_sums(const float* feat_dev, const int32_t* label_dev, int64_t n, int32_t D, int32_t K,
+                        float* sums_dev, int64_t* counts_dev, float* work_dev, void* stream);
+
 /* ---- a7: training step (float32) -------------------------------------------------------
  * Replaces, for the same network, models/patch_cls_simple/train.py:168-172:
  *   outputs = model(inputs); loss = criterion(outputs, labels); loss.backward(); optimizer.step()
