@@ -3,6 +3,8 @@
 //   dh_embed_normalize    row / sqrt(sum row^2): one wave per row, lane sums in column order, one butterfly over the wave
 //   dh_embed_scores       scale * feat . proto^T: a skinny f32 GEMM, 32 rows x 64 prototypes per workgroup through LDS
 //   dh_embed_class_sums   per-class sums of labelled rows in a fixed chunked order + int64 counts
+//   dh_embed_assign       per row, the nearest of K centres and its squared distance: the scores tile for
+//                         K > 16, one row per lane against centres broadcast from LDS for K <= 16
 // No atomics, and every reduction has one fixed order that the launch geometry cannot change: a row's result is the same bits
 // whatever n, the row's place and the grid are (the house rule of the canvas kernels).
 //
@@ -123,6 +125,151 @@ __global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restri
   }
 }
 
+// ---- dh_embed_assign -------------------------------------------------------------------------------------
+// One squared distance: ONE accumulator from 0, for c ascending t = x[c] - m[c] (one subtract), acc = fma(t, t, acc).
+__device__ __forceinline__ float as_dist4(float4 x, float4 m, float acc) {
+  float t = x.x - m.x;
+  acc = __builtin_fmaf(t, t, acc);
+  t = x.y - m.y;
+  acc = __builtin_fmaf(t, t, acc);
+  t = x.z - m.z;
+  acc = __builtin_fmaf(t, t, acc);
+  t = x.w - m.w;
+  return __builtin_fmaf(t, t, acc);
+}
+
+// The choice is the lexicographic minimum of (dist, index): commutative and associative, so any order of taking it gives the same
+// pair.  A NaN distance compares false and never wins; neither does +inf against the start (+inf, -1).
+__device__ __forceinline__ void as_take(float& bd, int& bk, float d, int k) {
+  if (d < bd || (d == bd && k < bk)) { bd = d; bk = k; }
+}
+
+// K > 16: the tile of embed_scores_kernel (32 rows x 64 centres, thread (rt, kt) owns rows rt, rt + 16 and centres kt + 16 j), the inner
+// step a subtract and a fused multiply-add per element pair.  Centres past K are zero in LDS and never compared.  Epilogue: the
+// thread's minimum over its (up to) four centres, a butterfly over the 16 lanes of one rt, lane kt == 0 stores.
+__global__ __launch_bounds__(256) void embed_assign_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                           const float* __restrict__ centre, int K, int k0, int merge,
+                                                           int32_t* __restrict__ label, float* __restrict__ dist) {
+  __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
+  __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
+  const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
+  const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  ScStage g = sc_fetch(feat, centre, n, D, K, row0, 0, tid);
+  float* const st_f = &s_f[rt * SC_LD + kt * 4];
+  float* const st_p = &s_p[rt * SC_LD + kt * 4];
+  for (int c0 = 0; c0 < D; c0 += SC_CK) {
+    __syncthreads();   // the previous stage's readers are done
+    *reinterpret_cast<float4*>(st_f) = g.f0;
+    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = g.f1;
+    *reinterpret_cast<float4*>(st_p) = g.p0;
+    *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
+    *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
+    *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
+    __syncthreads();
+    if (c0 + SC_CK < D) g = sc_fetch(feat, centre, n, D, K, row0, c0 + SC_CK, tid);
+#pragma unroll 4
+    for (int c = 0; c < SC_CK; c += 4) {
+      float4 f[2], p[4];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(rt + 16 * i) * SC_LD + c]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const float4*>(&s_p[(kt + 16 * j) * SC_LD + c]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = as_dist4(f[i], p[j], acc[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t row = row0 + rt + 16 * i;
+    const bool live = row < n;   // uniform over the 16 lanes of one rt
+    float bd = __builtin_inff();
+    int bk = -1;
+    if (merge && live && kt == 0) { bd = dist[row]; bk = label[row]; }   // the held pair enters once; its index is the lower
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = kt + 16 * j;
+      if (k < K) as_take(bd, bk, acc[i][j], k0 + k);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const float od = __shfl_xor(bd, o, 64);
+      const int ok = __shfl_xor(bk, o, 64);
+      as_take(bd, bk, od, ok);
+    }
+    if (live && kt == 0) { dist[row] = bd; label[row] = bk; }
+  }
+}
+
+// K <= 16: one row per lane, so no lane waits on a centre that is not there.  A workgroup takes 256 rows; every wave stages its own
+// 64 rows x 64 columns in LDS by row-contiguous float4 loads (16 per lane and stage, the next stage's issued before this stage's
+// arithmetic) and reads its lane's row back into registers; the centres' 64 columns sit in LDS once per workgroup and every lane reads
+// the same address (a broadcast).  KC accumulators per lane, each one chain over c ascending; centres j >= K are skipped by a
+// branch the whole grid takes alike.
+constexpr int AS_ROWS = 256;   // rows of a workgroup's tile: one per thread
+constexpr int AS_KC = 16;      // centres of this instantiation
+
+__global__ __launch_bounds__(256) void embed_assign_rows_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                                const float* __restrict__ centre, int K, int k0, int merge,
+                                                                int32_t* __restrict__ label, float* __restrict__ dist) {
+  __shared__ __attribute__((aligned(16))) float s_f[AS_ROWS * SC_LD];
+  __shared__ __attribute__((aligned(16))) float s_p[AS_KC * SC_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t wrow0 = (int64_t)blockIdx.x * AS_ROWS + wave * 64;   // the wave's first row
+  float* const w_f = &s_f[wave * 64 * SC_LD];
+  const int lr = lane >> 4, lc = (lane & 15) * 4;   // float4 number q = lane + 64 u of the wave's stage: row 4 u + lr, columns lc ..
+  float acc[AS_KC];
+#pragma unroll
+  for (int j = 0; j < AS_KC; ++j) acc[j] = 0.f;
+  float4 g[16], gp;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) g[u] = sc_load(feat, wrow0 + 4 * u + lr, n - 1, D, lc);
+  gp = sc_load(centre, tid >> 4, K - 1, D, (tid & 15) * 4);
+  for (int c0 = 0; c0 < D; c0 += SC_CK) {
+    __syncthreads();   // the previous stage's readers are done
+#pragma unroll
+    for (int u = 0; u < 16; ++u) *reinterpret_cast<float4*>(&w_f[(4 * u + lr) * SC_LD + lc]) = g[u];
+    *reinterpret_cast<float4*>(&s_p[(tid >> 4) * SC_LD + (tid & 15) * 4]) = gp;
+    __syncthreads();
+    if (c0 + SC_CK < D) {
+#pragma unroll
+      for (int u = 0; u < 16; ++u) g[u] = sc_load(feat, wrow0 + 4 * u + lr, n - 1, D, c0 + SC_CK + lc);
+      gp = sc_load(centre, tid >> 4, K - 1, D, c0 + SC_CK + (tid & 15) * 4);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {   // 32 columns of the lane's row in registers at a time
+      float4 f[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = *reinterpret_cast<const float4*>(&w_f[lane * SC_LD + 32 * h + 4 * q]);
+#pragma unroll
+      for (int j = 0; j < AS_KC; ++j) {
+        if (j < K) {
+          float a = acc[j];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) a = as_dist4(f[q], *reinterpret_cast<const float4*>(&s_p[j * SC_LD + 32 * h + 4 * q]), a);
+          acc[j] = a;
+        }
+      }
+    }
+  }
+  const int64_t row = wrow0 + lane;
+  if (row >= n) return;
+  float bd = __builtin_inff();
+  int bk = -1;
+  if (merge) { bd = dist[row]; bk = label[row]; }
+#pragma unroll
+  for (int j = 0; j < AS_KC; ++j)
+    if (j < K) as_take(bd, bk, acc[j], k0 + j);
+  dist[row] = bd;
+  label[row] = bk;
+}
+
 // Stage 1, one workgroup per (chunk of 1024 rows, slab of 256 columns).  The chunk's labels are sorted by class in LDS, stably (thread k
 // scans them in row order), so class k's rows are idx[start[k] .. start[k + 1]) in ascending order; thread c then adds, class by class,
 // those rows' column c into ONE accumulator from 0 and writes partial[chunk][k][c], zeros included.  The slab-0 workgroup also writes the
@@ -225,6 +372,28 @@ extern "C" int dh_embed_scores(const float* feat, int64_t n, int32_t D, const fl
   DH_REQUIRE(aligned16(feat) && aligned16(proto), "dh_embed_scores: feat_dev / proto_dev not 16-byte aligned");
   const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
   hipLaunchKernelGGL(embed_scores_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, proto, K, scale, scores);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_embed_assign(const float* feat, int64_t n, int32_t D, const float* centres, int32_t K, int32_t k0, int32_t merge,
+                               int32_t* label, float* dist, void* stream) {
+  if (int rc = check_dims("dh_embed_assign", n, D, K)) return rc;
+  DH_REQUIRE(k0 >= 0 && k0 <= 0x7fffffff - 64, "dh_embed_assign: k0 = %d out of range [0, 2^31 - 65]", k0);
+  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_assign: n = %lld exceeds one launch", (long long)n);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(feat && centres && label && dist, "dh_embed_assign: null feat_dev, centres_dev, label_dev or dist_dev");
+  DH_REQUIRE(aligned16(feat) && aligned16(centres), "dh_embed_assign: feat_dev / centres_dev not 16-byte aligned");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(label) & 3) == 0 && (reinterpret_cast<uintptr_t>(dist) & 3) == 0,
+             "dh_embed_assign: label_dev / dist_dev not 4-byte aligned");
+  hipStream_t st = dh::as_stream(stream);
+  if (K <= AS_KC) {
+    const int64_t grid = (n + AS_ROWS - 1) / AS_ROWS;
+    hipLaunchKernelGGL(embed_assign_rows_kernel, dim3((unsigned)grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
+  } else {
+    const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
+    hipLaunchKernelGGL(embed_assign_kernel, dim3((unsigned)grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
+  }
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -12,7 +12,8 @@ slide's polygon annotation; the CLI does so with `--anno PATH [--score_json PATH
 ones and traces them into polygons; the CLI does so with `--regions_json`, `--min_region [--clean_rounds]`, `--export_anno`.
 `extract_embeddings(sampler, model, ...)` (deephisto_amd.embeddings) hands out the per-tile feature vectors of
 the same plan, and `PrototypeClassifier` scores them against class prototypes; the CLI does so with `--save_embeddings PATH` and
-`--prototypes PATH`.
+`--prototypes PATH`.  Without an annotation, `--clusters K` groups them by k-means (deephisto_amd.clustering)
+and paints the cluster map.
 `main` calls `predict_full_patched` and `predict_random_patched` through this module's globals (tests replace them here).
 """
 from __future__ import annotations
@@ -26,6 +27,7 @@ import torch
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, check  # noqa: F401  (exported here)
 from ..anno.utils import AnnoDescription
+from ..clustering import INITS as CLUSTER_INITS, KMeans, cluster_description, cluster_map  # noqa: F401  (exported here)
 from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embeddings, tile_labels  # noqa: F401  (exported here)
 from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
@@ -315,7 +317,8 @@ def _proba_from_args(ap, args) -> None:
 
 def _embeddings_from_args(ap, args) -> None:
     """Checks --save_embeddings / --prototypes; a bad combination is an argparse error."""
-    for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes)):
+    for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes),
+                        ("--clusters", args.clusters), ("--load_clusters", args.load_clusters)):
         if not value:
             continue
         if args.random_sampler:
@@ -328,6 +331,17 @@ def _embeddings_from_args(ap, args) -> None:
             ap.error(f"{flag} finishes the class map from the stored logits; it cannot be combined with --proba")
     if args.prototypes and not args.anno and not Path(args.prototypes).is_file():
         ap.error(f"--prototypes {args.prototypes}: no such file (with --anno the prototypes are fitted and written there)")
+    if args.clusters is not None and not 1 <= args.clusters <= 64:
+        ap.error(f"--clusters must be in 1 .. 64, not {args.clusters}")
+    if args.load_clusters:
+        if args.save_clusters or args.cluster_seed is not None or args.cluster_init is not None:
+            ap.error("--load_clusters applies a saved codebook: --save_clusters, --cluster_seed and --cluster_init belong to a fit")
+        if not Path(args.load_clusters).is_file():
+            ap.error(f"--load_clusters {args.load_clusters}: no such file")
+    elif args.clusters is None and (args.save_clusters or args.cluster_seed is not None or args.cluster_init is not None):
+        ap.error("--save_clusters, --cluster_seed and --cluster_init need --clusters")
+    if (args.clusters is not None or args.load_clusters) and args.min_region is not None:
+        ap.error("--min_region cleans the class map; with --clusters the region flags describe the cluster map as it is")
 
 
 def _regions_from_args(ap, args) -> None:
@@ -402,6 +416,15 @@ def _build_parser():
     ap.add_argument("--prototypes", default=None, metavar="PATH",
                     help="nearest-class-mean scoring of the tile embeddings: with --anno, fit the class prototypes on this slide's "
                          "annotated tiles and write them to PATH; without, load PATH and write {stem}_prototype_map.jpg")
+    ap.add_argument("--clusters", type=int, default=None, metavar="K",
+                    help="k-means over the tile embeddings of this pass (1 .. 64 clusters, no annotation needed): writes "
+                         "{stem}_clusters.jpg and {stem}_clusters.json (rank 0); --regions_json / --export_anno then describe the "
+                         "cluster map's regions, named cluster_0 ...")
+    ap.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="with --clusters: the seed of the k-means++ draws (default 0)")
+    ap.add_argument("--cluster_init", choices=list(CLUSTER_INITS), default=None, help="with --clusters: the seeding (default kmeans++)")
+    ap.add_argument("--save_clusters", default=None, metavar="PATH", help="with --clusters: the fitted codebook as one .npz (rank 0)")
+    ap.add_argument("--load_clusters", default=None, metavar="PATH",
+                    help="apply the codebook of an earlier --save_clusters to this slide instead of fitting (K comes from the file)")
     return ap
 
 
@@ -461,7 +484,7 @@ def _run(args, model, device, rank, world):
         info: dict = {}
         qinfo: dict = {}
         args.embeddings = None
-        if args.save_embeddings or args.prototypes:
+        if args.save_embeddings or args.prototypes or args.clusters is not None or args.load_clusters:
             # the same plan through the features entry; the map is finished from that pass's logits by predict_full_patched's tail
             filt = args.quality_filter if args.quality_filter is not None else args.tissue_filter
             emb = args.embeddings = extract_embeddings(smp, model, tissue=args.tissue_filter, tissue_info=info,
@@ -541,6 +564,43 @@ def _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device) -> None:
         _save_jpeg(overlay, out_dir / f"{stem}_prototype_map.jpg")
 
 
+def _clusters_rank0(args, src, stem, out_dir, device):
+    """--clusters / --load_clusters: fit k-means on this slide's embeddings (or apply a saved codebook), write
+    `{stem}_clusters.json` and, with visualisations, `{stem}_clusters.jpg`.  Returns (cluster map, its AnnoDescription)."""
+    import json
+
+    emb = args.embeddings
+    if args.load_clusters:
+        km = KMeans.load(args.load_clusters, device=device)
+        if km.centres_.shape[1] != emb.width or (args.clusters is not None and args.clusters != km.n_clusters):
+            raise ValueError(f"--load_clusters {args.load_clusters}: {km.n_clusters} clusters x {km.centres_.shape[1]} floats do not fit "
+                             f"this run ({'any' if args.clusters is None else args.clusters} x {emb.width})")
+        labels, dist = km.predict(emb, return_dist=True)
+        sizes = torch.bincount(labels[labels >= 0].to(torch.int64), minlength=km.n_clusters).cpu().numpy().tolist()
+        inertia = float(dist.double().sum())
+    else:
+        km = KMeans(args.clusters, init=args.cluster_init or "kmeans++", seed=args.cluster_seed or 0).fit(emb)
+        labels, sizes, inertia = km.labels_, km.counts_.tolist(), km.inertia_
+        if args.save_clusters:
+            Path(args.save_clusters).parent.mkdir(parents=True, exist_ok=True)
+            km.save(args.save_clusters)
+    K = km.n_clusters
+    print(f"clusters: {K} over {len(emb)} tiles, sizes {sizes}, inertia {inertia:.6g}, "
+          + (f"codebook {args.load_clusters}" if args.load_clusters else
+             f"{km.n_iter_} iterations, {'converged' if km.converged_ else 'not converged'}"), flush=True)
+    dsc = cluster_description(K)
+    cmap = cluster_map(emb, labels, K, args.downscale_vis)
+    out_dir.mkdir(exist_ok=True, parents=True)
+    doc = dict(n_clusters=K, n_tiles=len(emb), sizes=sizes, inertia=inertia, iterations=km.n_iter_, converged=km.converged_,
+               init=km.init, seed=km.seed, normalize=km.normalize, fitted_here=not args.load_clusters,
+               colors={a.label: list(a.color) for a in dsc.anno_classes})
+    (out_dir / f"{stem}_clusters.json").write_text(json.dumps(doc, indent=1) + "\n")
+    if not args.no_visualizations:
+        _, _, overlay = perform_and_save_visualizations(src, dsc, cmap, stem=stem, save=False, device=device)
+        _save_jpeg(overlay, out_dir / f"{stem}_clusters.jpg")
+    return cmap, dsc
+
+
 def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
     """What rank 0, where the map is whole, prints and writes after the prediction: the score, the JPEGs, the probability
     files, then the regions with the cleaned map's score and JPEGs."""
@@ -562,6 +622,8 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
         save_proba(args.save_proba, proba)
     if args.prototypes:
         _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device)
+    if args.clusters is not None or args.load_clusters:
+        pred, anno_dsc = _clusters_rank0(args, src, stem, out_dir, device)   # the region flags below describe the cluster map
     if not (args.regions_json or args.min_region is not None or args.export_anno):
         return
     res = extract_regions(pred, anno_dsc, args.layer, args.downscale_vis, min_cells=args.min_region or 0,
@@ -627,6 +689,11 @@ def main(argv=None, model=None):
     slide's annotated tiles and writes them; without `--anno` it loads them and writes `{stem}_prototype_map.jpg`, the
     nearest-prototype class of every cell over the slide.  Both take the dense branch and a resident slide and are refused with
     `--random_sampler`, `--ondisk`, `--tta` and `--proba`.
+    `--clusters K [--cluster_seed S] [--cluster_init kmeans++|maximin] [--save_clusters PATH]` runs k-means over the embeddings of
+    the same pass (no annotation needed; the same refusals) and writes `{stem}_clusters.jpg`, the cluster of
+    most covering tiles per cell in a K-colour palette over the slide, and `{stem}_clusters.json` (K, sizes, inertia, iterations,
+    converged); `--load_clusters PATH` applies a saved codebook instead of fitting.  `--regions_json` / `--export_anno` then
+    describe the cluster map's regions, named `cluster_0` ...; the class map and its JPEGs are those of a run without the flags.
     `model`: an injected module (tests)."""
     from ..distributed import finalize, init_from_env
     from ..models.patch_cls_simple import utils

@@ -322,7 +322,15 @@ int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64
  *   outside [0, K), -1 among them, are ignored), counts_dev[k] (int64[K]) their number.  The order is the contract:
  *   rows are cut into chunks of DH_EMBED_CHUNK_ROWS; a chunk's partial starts at 0 and adds its rows in ascending
  *   order; the result starts at 0 and adds the partials of ALL chunks in ascending chunk order (float32 throughout).
- *   work_dev: float32[dh_embed_class_work_size(n, D, K)] scratch (16-byte aligned); the size is -1 for bad arguments. */
+ *   work_dev: float32[dh_embed_class_work_size(n, D, K)] scratch (16-byte aligned); the size is -1 for bad arguments.
+ * dh_embed_assign: per row i the nearest of the K rows of centres_dev (float32[K][D]):
+ *   dist_dev[i] (float32[n]) the smallest squared Euclidean distance, label_dev[i] (int32[n]) = k0 + the index of the
+ *   centre that attains it.  A distance is ONE accumulator from 0: for c ascending t = feat[i][c] - centre[k][c] (one
+ *   float32 subtract), acc = fma(t, t, acc); so a row equal to a centre gets exactly 0.  The choice is the
+ *   lexicographic minimum of (distance, index) from the start (+inf, -1): at equal distances the lower index wins, a
+ *   NaN or +inf distance never does, and a row with no finite distance gets (-1, +inf).  merge != 0: the start is
+ *   the row's existing (dist_dev[i], label_dev[i]) instead, which is kept at ties when its index is the lower (the
+ *   caller's part); this assigns against more than 64 centres in passes (k0 = 0, 64, ...).  k0 >= 0. */
 #define DH_EMBED_CHUNK_ROWS 1024
 int dh_embed_normalize(const float* in_dev, int64_t n, int32_t D, float* out_dev, void* stream);
 int dh_embed_scores(const float* feat_dev, int64_t n, int32_t D, const float* proto_dev, int32_t K, float scale,
@@ -330,6 +338,8 @@ int dh_embed_scores(const float* feat_dev, int64_t n, int32_t D, const float* pr
 int64_t dh_embed_class_work_size(int64_t n, int32_t D, int32_t K);
 int dh_embed_class_sums(const float* feat_dev, const int32_t* label_dev, int64_t n, int32_t D, int32_t K,
                         float* sums_dev, int64_t* counts_dev, float* work_dev, void* stream);
+int dh_embed_assign(const float* feat_dev, int64_t n, int32_t D, const float* centres_dev, int32_t K, int32_t k0,
+                    int32_t merge, int32_t* label_dev, float* dist_dev, void* stream);
 
 /* ---- a7: training step (float32) -------------------------------------------------------
  * Replaces, for the same network, models/patch_cls_simple/train.py:168-172:
