@@ -21,7 +21,6 @@ from . import tiles
 from ._lib import check, lib
 from .anno.utils import AnnoDescription
 from .embeddings import SlideEmbeddings, _rows, _stream, class_sums, normalize_rows
-from .tissue import fill_uncovered
 
 MAX_CLUSTERS = 64   # of dh_embed_class_sums; dh_embed_assign itself goes past it in passes (k0, merge)
 INITS = ("kmeans++", "maximin")
@@ -283,7 +282,7 @@ def cluster_map(emb: SlideEmbeddings, labels, n_clusters: int, downscale: int = 
         torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)).to(dev)
     if lb.dim() != 1 or lb.shape[0] != len(emb):
         raise ValueError(f"{tuple(lb.shape)} labels for {len(emb)} tiles")
-    kept, kept_yx = emb._kept()
+    emb.require_all_rows()
     if len(emb) == 0:
         return torch.full((emb.h // downscale, emb.w // downscale), fill_class, dtype=torch.int64, device=dev)
     if int(lb.max()) >= K:
@@ -292,8 +291,7 @@ def cluster_map(emb: SlideEmbeddings, labels, n_clusters: int, downscale: int = 
     rows = torch.nonzero(lb >= 0).reshape(-1)
     votes[rows, lb[rows]] = 1.0
     canvas, cmap = tiles.accumulate_logits(votes, emb.origins, emb.patch_size, downscale, emb.h, emb.w)
-    if kept is not None:
-        fill_uncovered(cmap, kept_yx, emb.patch_size, downscale, emb.h, emb.w, fill_class)
+    emb.fill_uncovered(cmap, downscale, fill_class)
     if len(rows) != len(emb):
         cmap[canvas.sum(dim=2) == 0] = fill_class
     return cmap

@@ -266,45 +266,38 @@ extern "C" int dh_resnet50_forward(dh_resnet50* net, const float* x, int64_t n, 
   return r50_forward_impl(net, x, nullptr, 0, 0, nullptr, (int)n, P, logits, dh::as_stream(stream));
 }
 
-// The origins are device memory: they are read back (n pairs, one synchronisation of `stream`) and checked before any launch, so that an
-// origin outside the slide is an error, not a read past the tile (the stem itself never reads outside the slide allocation either).
-extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
-                                         int32_t P, float* logits, void* stream) {
-  if (int rc = r50_check_forward(net, n, P, logits, "resnet50 forward_tiles")) return rc;
+// The fused gather + forward behind both tiles entries; `what` names the entry in messages.  `feat` (features_tiles: the pooled
+// 2048-vector of every tile, the tap one step before the logits) is stored as well when given and must be 16-byte aligned (its rows
+// are written as float4); `out` is the entry's mandatory output.  The origins are device memory: they are read back (n pairs, one synchronisation of `stream`) and checked before
+// any launch, so that an origin outside the slide is an error, not a read past the tile (the stem itself never reads outside the slide
+// allocation either).
+static int r50_forward_tiles_impl(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n, int32_t P,
+                                  float* feat, float* logits, const float* out, void* stream, const char* what) {
+  if (int rc = r50_check_forward(net, n, P, out, what)) return rc;
   if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "resnet50 forward_tiles: null slide or origins");
-  DH_REQUIRE(h >= P && w >= P, "resnet50 forward_tiles: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
+  DH_REQUIRE(slide && yx, "%s: null slide or origins", what);
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(feat) & 15) == 0, "%s: feat_dev is not 16-byte aligned", what);
+  DH_REQUIRE(h >= P && w >= P, "%s: patch %d does not fit %lldx%lld", what, P, (long long)h, (long long)w);
   hipStream_t st = dh::as_stream(stream);
   net->yx_host.resize((size_t)n * 2);
   DH_HIP(hipMemcpyAsync(net->yx_host.data(), yx, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   DH_HIP(hipStreamSynchronize(st));
   for (int64_t i = 0; i < n; ++i) {
     const int32_t y = net->yx_host[2 * i], x = net->yx_host[2 * i + 1];
-    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "resnet50 forward_tiles: origin %lld (y=%d, x=%d) puts a %d-pixel tile outside "
-               "the %lldx%lld slide", (long long)i, y, x, P, (long long)h, (long long)w);
-  }
-  return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st);
-}
-
-// forward_tiles with the pooled 2048-vector of every tile stored as well (the tap one step before the logits); logits may be NULL.
-// feat_dev must be 16-byte aligned (rows of 2048 floats are written as float4).
-extern "C" int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
-                                          int32_t P, float* feat, float* logits, void* stream) {
-  if (int rc = r50_check_forward(net, n, P, feat, "resnet50 features_tiles")) return rc;
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "resnet50 features_tiles: null slide or origins");
-  DH_REQUIRE((reinterpret_cast<uintptr_t>(feat) & 15) == 0, "resnet50 features_tiles: feat_dev is not 16-byte aligned");
-  DH_REQUIRE(h >= P && w >= P, "resnet50 features_tiles: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
-  hipStream_t st = dh::as_stream(stream);
-  net->yx_host.resize((size_t)n * 2);
-  DH_HIP(hipMemcpyAsync(net->yx_host.data(), yx, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  DH_HIP(hipStreamSynchronize(st));
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t y = net->yx_host[2 * i], x = net->yx_host[2 * i + 1];
-    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "resnet50 features_tiles: origin %lld (y=%d, x=%d) puts a %d-pixel tile "
-               "outside the %lldx%lld slide", (long long)i, y, x, P, (long long)h, (long long)w);
+    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "%s: origin %lld (y=%d, x=%d) puts a %d-pixel tile outside the %lldx%lld slide",
+               what, (long long)i, y, x, P, (long long)h, (long long)w);
   }
   return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, nullptr, feat);
+}
+
+extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                                         int32_t P, float* logits, void* stream) {
+  return r50_forward_tiles_impl(net, slide, h, w, yx, n, P, nullptr, logits, logits, stream, "resnet50 forward_tiles");
+}
+
+extern "C" int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                                          int32_t P, float* feat, float* logits, void* stream) {
+  return r50_forward_tiles_impl(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet50 features_tiles");
 }
 
 // Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (Tap above), and a conv's

@@ -1553,35 +1553,29 @@ extern "C" int dh_resnet18_forward(dh_resnet18* net, const float* x, int64_t n, 
              : forward_impl<__bf16>(net, x, nullptr, 0, 0, nullptr, n, P, logits, st);
 }
 
-extern "C" int dh_resnet18_forward_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
-                                         const int32_t* yx, int64_t n, int32_t P, float* logits,
-                                         void* stream) {
-  int rc = check_forward_args(net, n, P, logits);
+// The fused gather + forward behind both tiles entries; `what` names the entry in messages, `feat` (features_tiles: the pooled
+// 512-vector of every tile, the tap one step before the logits) is stored as well when given; `out` is the entry's mandatory output.
+static int forward_tiles_impl(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                              int32_t P, float* feat, float* logits, const float* out, void* stream, const char* what) {
+  int rc = check_forward_args(net, n, P, out);
   if (rc) return rc;
   if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "resnet18 forward_tiles: null slide or origins");
-  DH_REQUIRE(h >= P && w >= P, "resnet18 forward_tiles: patch %d does not fit %lldx%lld", P,
-             (long long)h, (long long)w);
-  hipStream_t st = dh::as_stream(stream);
-  return net->dtype == DH_DTYPE_F32
-             ? forward_impl<float>(net, nullptr, slide, h, w, yx, n, P, logits, st)
-             : forward_impl<__bf16>(net, nullptr, slide, h, w, yx, n, P, logits, st);
-}
-
-// forward_tiles with the pooled 512-vector of every tile stored as well (the tap one step before the logits); logits may be NULL
-extern "C" int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
-                                          const int32_t* yx, int64_t n, int32_t P, float* feat, float* logits,
-                                          void* stream) {
-  int rc = check_forward_args(net, n, P, feat);
-  if (rc) return rc;
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "resnet18 features_tiles: null slide or origins");
-  DH_REQUIRE(h >= P && w >= P, "resnet18 features_tiles: patch %d does not fit %lldx%lld", P,
-             (long long)h, (long long)w);
+  DH_REQUIRE(slide && yx, "%s: null slide or origins", what);
+  DH_REQUIRE(h >= P && w >= P, "%s: patch %d does not fit %lldx%lld", what, P, (long long)h, (long long)w);
   hipStream_t st = dh::as_stream(stream);
   return net->dtype == DH_DTYPE_F32
              ? forward_impl<float>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat)
              : forward_impl<__bf16>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat);
+}
+
+extern "C" int dh_resnet18_forward_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
+                                         const int32_t* yx, int64_t n, int32_t P, float* logits, void* stream) {
+  return forward_tiles_impl(net, slide, h, w, yx, n, P, nullptr, logits, logits, stream, "resnet18 forward_tiles");
+}
+
+extern "C" int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
+                                          const int32_t* yx, int64_t n, int32_t P, float* feat, float* logits, void* stream) {
+  return forward_tiles_impl(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet18 features_tiles");
 }
 
 // ---------------------------------------------------------------------------

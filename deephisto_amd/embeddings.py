@@ -1,7 +1,6 @@
 """Tile embeddings of a whole slide and a prototype (nearest-class-mean) scorer on top of them.
 
-`extract_embeddings(sampler, model, ...)` runs the plan of `predict.predict_full_patched` (the dense sampler's unique tiles, the
-tissue stage then the quality stage, `shard_range`, `launch_size`, lanes over `streams`) through the models' features entry
+`extract_embeddings(sampler, model, ...)` runs the tile plan of `predict.predict_full_patched` (`plan.py`) through the models' features entry
 (`dh_resnet18_features_tiles` / `dh_resnet50_features_tiles`: the fused gather + forward with every tile's pooled feature vector,
 the input of `fc`, stored as well) and returns a `SlideEmbeddings`: float32[n_kept, 512 | 2048] on the device, one exchange of
 the rows under torch.distributed.  `PrototypeClassifier` turns embeddings plus a handful of labelled tiles (`tile_labels`) into a
@@ -19,10 +18,9 @@ import torch
 from . import tiles
 from ._lib import check, lib
 from .patch_samplers.full_samplers import FullImageDenseSampler
-from .predict import (_finish, _normalised_first, _side_stream, accumulation_list, exchange_logits, launch_size,
-                      shard_range)
-from .quality import QualityFilter, check_fill_classes, score_quality
-from .tissue import TissueFilter, fill_uncovered, score_tiles
+from .plan import Lanes, TileGrid, exchange_rows, finish, launch_tiles, normalised_first, plan_tiles, require_dense_resident
+from .quality import QualityFilter
+from .tissue import TissueFilter, fill_uncovered
 
 CHUNK_ROWS = 1024   # DH_EMBED_CHUNK_ROWS: the chunking of class_sums' summation order
 
@@ -90,18 +88,6 @@ def class_sums(features: torch.Tensor, labels: torch.Tensor, n_classes: int) -> 
 _META = ("patch_size", "stride", "h", "w", "layer", "arch", "compute_dtype", "n_unique", "n_padded")
 
 
-class _Grid:
-    """What `predict._finish` reads of a sampler: the padded origin list and its geometry."""
-
-    def __init__(self, origins, n_tiles, patch_size, h, w):
-        self.origins, self.n_tiles, self.patch_size, self.h, self.w = origins, n_tiles, patch_size, h, w
-
-
-class _Fill:
-    def __init__(self, fill_class):
-        self.fill_class = fill_class
-
-
 class SlideEmbeddings:
     """The per-tile embeddings of one slide.
 
@@ -157,115 +143,67 @@ class SlideEmbeddings:
             logits = torch.from_numpy(z["logits"]).to(device) if "logits" in z.files else None
             return cls(torch.from_numpy(z["features"]).to(device), z["origins"], z["tile_index"], logits, **meta)
 
-    def _grid(self) -> _Grid:
-        """The sampler's padded origin list, rebuilt: the unique grid, then copies of the corner tile."""
-        o, n_u = tiles.tile_grid(self.h, self.w, self.patch_size, self.stride, 1)
-        if n_u != self.n_unique:
-            raise ValueError("the stored geometry does not reproduce the tile grid")
-        pad = np.repeat(o[n_u - 1:n_u], self.n_padded - n_u, axis=0)
-        return _Grid(np.concatenate([o[:n_u], pad]) if len(pad) else o[:n_u], n_u, self.patch_size, self.h, self.w)
-
-    def _kept(self):
-        """(kept, kept_yx_dev) as `predict._finish` takes them: None, None when every unique tile ran."""
+    def require_all_rows(self) -> None:
         if self.row_range is not None:
             raise ValueError("these embeddings hold one rank's rows only (gather=False): a map needs all of them")
-        if len(self) == self.n_unique:
-            return None, None
-        return self.tile_index, torch.from_numpy(self.origins).to(self.features.device)
+
+    def fill_uncovered(self, cmap: torch.Tensor, downscale: int, fill_class: int) -> torch.Tensor:
+        """In place: the cells of int64[h // d, w // d] `cmap` no tile of these embeddings covers become `fill_class`."""
+        self.require_all_rows()
+        if len(self) != self.n_unique:
+            fill_uncovered(cmap, torch.from_numpy(self.origins).to(cmap.device), self.patch_size, downscale, self.h, self.w, fill_class)
+        return cmap
 
     def class_map(self, downscale: int = 16, dedupe_padding: bool = False, fill_class: int = -1) -> torch.Tensor:
         """int64[h // d, w // d]: the class map `predict_full_patched` gives for this run, bit for bit, finished from the
-        stored logits by its own tail (`predict._finish`); cells no kept tile covers get `fill_class`."""
+        stored logits by its own tail (`plan.finish`); cells no kept tile covers get `fill_class`."""
         if self.logits is None:
             raise ValueError("class_map needs the logits: extract_embeddings(..., return_logits=True)")
-        kept, kept_yx = self._kept()
-        return _finish(self._grid(), self.logits, kept, kept_yx, downscale, dedupe_padding,
-                       None if kept is None else _Fill(fill_class), False, False)
+        self.require_all_rows()
+        grid = TileGrid.from_geometry(self.h, self.w, self.patch_size, self.stride, self.n_unique, self.n_padded)
+        if len(self) == self.n_unique:   # every unique tile ran: the unfiltered tail
+            return finish(grid, self.logits, None, None, downscale, dedupe_padding, None, False, False)
+        kept_yx_dev = torch.from_numpy(self.origins).to(self.features.device)
+        return finish(grid, self.logits, self.tile_index, kept_yx_dev, downscale, dedupe_padding, fill_class, False, False)
 
 
-@_normalised_first
+@normalised_first
 def extract_embeddings(sampler: FullImageDenseSampler, model, micro_batch: int | None = None, group=None, streams: int = 2,
                        tissue: TissueFilter | None = None, tissue_info: dict | None = None,
                        quality: QualityFilter | None = None, quality_info: dict | None = None,
                        return_logits: bool = False, gather: bool = True, *, tta=None) -> SlideEmbeddings:
-    """The pooled feature vector of every tile `predict_full_patched` would classify, from the same plan: the dense sampler's
-    unique tiles, the tissue stage then the quality stage (`tissue=`, `quality=` and their info dicts as there), the rank's
-    `shard_range`, launches of `launch_size` alternating over `streams` lanes, each through the model's features entry.
+    """The pooled feature vector of every tile `predict_full_patched` would classify, from the same plan (`plan.plan_tiles`;
+    `tissue=`, `quality=` and their info dicts as there), each launch through the model's features entry.
     `gather=True`: one `exchange_logits` of the feature rows (and a second for the logits with `return_logits`), after which
     every rank holds all rows in tile order; `gather=False`: each rank keeps its own rows (`row_range`).
-    Keyword-only `stain=` / `stain_info=`: see `predict._normalised_first`, which wraps this function.
+    Keyword-only `stain=` / `stain_info=`: see `plan.normalised_first`, which wraps this function.
     Refused with a ValueError: a streamed (ONDISK_MULTIPROC) sampler, any sampler but the dense one, and `tta=`."""
-    import torch.distributed as dist
-
     if tta is not None:
         raise ValueError("extract_embeddings has no test-time augmentation (an average of embeddings over views is out of scope)")
-    if not isinstance(sampler, FullImageDenseSampler):
-        raise ValueError("extract_embeddings works on the dense sampler's grid only (not on the random sampler's branch)")
-    if not sampler.resident:
-        raise ValueError("extract_embeddings needs an HBM-resident slide (ONDISK_MULTIPROC streams it)")
+    require_dense_resident(sampler, "extract_embeddings")
     if not hasattr(model, "features_entry"):
         raise ValueError("extract_embeddings needs a ResNet18HIP or ResNet50HIP model")
-    if quality is not None:
-        check_fill_classes(tissue, quality)
-    slide = sampler.data_device
-    dev, P = slide.device, sampler.patch_size
-    origins, n_unique = sampler.origins, sampler.n_tiles
-    kept = kept_yx_dev = None
-    if tissue is not None:
-        kept_idx_dev, kept_yx_dev, info = score_tiles(slide, torch.from_numpy(origins[:n_unique]).to(dev), P, tissue,
-                                                      origins[:n_unique])
-        kept = kept_idx_dev.cpu().numpy().astype(np.int64)
-        if tissue_info is not None:
-            tissue_info.update(info, kept=kept)
-    if quality is not None:
-        t = -1 if tissue is None else info["threshold"]
-        scored = torch.from_numpy(origins[:n_unique]).to(dev) if kept is None else kept_yx_dev
-        q_idx_dev, kept_yx_dev, qinfo = score_quality(slide, scored, P, t, quality,
-                                                      origins[:n_unique] if kept is None else origins[:n_unique][kept])
-        q = q_idx_dev.cpu().numpy().astype(np.int64)
-        kept = q if kept is None else kept[q]
-        if quality_info is not None:
-            quality_info.update(qinfo, kept=kept)
-    n_work = n_unique if kept is None else len(kept)
-    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
-    world = dist.get_world_size(group) if distributed else 1
-    rank = dist.get_rank(group) if distributed else 0
-    lo, hi = shard_range(n_work, world, rank)
-    mb = launch_size(hi - lo, micro_batch or model.default_micro_batch())
-    o_dev = torch.from_numpy(origins[lo:hi]).to(dev) if kept is None else kept_yx_dev[lo:hi]
-    per_rank = -(-n_work // world)
-    D, n_cls = model.feature_width, model.n_classes
-    feat = torch.zeros((per_rank, D), dtype=torch.float32, device=dev)
-    logits = torch.zeros((per_rank, n_cls), dtype=torch.float32, device=dev) if return_logits else None
-    handles = model.eval().lane_handles(max(1, streams))
-    main = torch.cuda.current_stream(dev)
-    lanes = [main] + [_side_stream(dev, i) for i in range(1, len(handles))]
-    for st in lanes[1:]:
-        st.wait_stream(main)
-    fwd, fwd_name = model.features_entry()
-    for k, s in enumerate(range(0, hi - lo, mb)):
-        lane, e = k % len(handles), min(s + mb, hi - lo)
-        check(fwd(handles[lane], slide.data_ptr(), sampler.h, sampler.w, o_dev.data_ptr() + 8 * s, e - s, P,
-                  feat.data_ptr() + 4 * D * s, logits.data_ptr() + 4 * n_cls * s if return_logits else None,
-                  C.c_void_p(lanes[lane].cuda_stream)), fwd_name)
-    for st in lanes[1:]:
-        main.wait_stream(st)
-    tile_index = np.arange(n_unique, dtype=np.int64) if kept is None else kept
-    yx = origins[:n_unique][tile_index]
+    plan = plan_tiles(sampler, model, micro_batch, group, tissue, tissue_info, quality, quality_info)
+    slide, P, o_dev, grid = sampler.data_device, sampler.patch_size, plan.o_dev, plan.grid
+    n, D = plan.hi - plan.lo, model.feature_width
+    feat = torch.zeros((plan.per_rank, D), dtype=torch.float32, device=slide.device)
+    logits = torch.zeros((plan.per_rank, model.n_classes), dtype=torch.float32, device=slide.device) if return_logits else None
+    entry = model.features_entry()
+    Lanes(model, streams, slide.device).run(n, plan.mb, lambda handle, stream, s, e: launch_tiles(
+        entry, handle, slide, sampler.h, sampler.w, o_dev, s, e, P, logits, stream, feat=feat))
+    tile_index = np.arange(grid.n_unique, dtype=np.int64) if plan.kept is None else plan.kept
+    yx = grid.origins[:grid.n_unique][tile_index]
     row_range = None
     if gather:
-        if distributed and n_work:
-            feat = exchange_logits(feat, n_work, group)
-            logits = exchange_logits(logits, n_work, group) if return_logits else None
-        else:
-            feat, logits = feat[:n_work], logits[:n_work] if return_logits else None
+        feat = exchange_rows(plan, feat, group)
+        logits = exchange_rows(plan, logits, group) if return_logits else None
     else:
-        feat, logits = feat[:hi - lo], logits[:hi - lo] if return_logits else None
-        tile_index, yx = tile_index[lo:hi], yx[lo:hi]
-        row_range = (lo, hi) if world > 1 else None
+        feat, logits = feat[:n], logits[:n] if return_logits else None
+        tile_index, yx = tile_index[plan.lo:plan.hi], yx[plan.lo:plan.hi]
+        row_range = (plan.lo, plan.hi) if plan.world > 1 else None
     return SlideEmbeddings(feat, yx, tile_index, logits, patch_size=P, stride=sampler.stride, h=sampler.h, w=sampler.w,
                            layer=sampler.layer, arch="resnet50" if D == 2048 else "resnet18",
-                           compute_dtype=model.compute_dtype, n_unique=n_unique, n_padded=len(origins), row_range=row_range)
+                           compute_dtype=model.compute_dtype, n_unique=grid.n_unique, n_padded=len(grid.origins), row_range=row_range)
 
 
 def tile_labels(emb: SlideEmbeddings, truth_map, downscale: int) -> np.ndarray:
@@ -323,13 +261,11 @@ class PrototypeClassifier:
         """int64[h // d, w // d] class map: the score rows accumulated over the tiles' footprints in tile order, like logits
         (`tiles.accumulate_logits`), then the first maximum per cell; cells no tile of `emb` covers get `fill_class`."""
         sc = self.scores(emb.features)
-        kept, kept_yx = emb._kept()
+        emb.require_all_rows()
         if len(emb) == 0:
             return torch.full((emb.h // downscale, emb.w // downscale), fill_class, dtype=torch.int64, device=sc.device)
         _, cmap = tiles.accumulate_logits(sc, emb.origins, emb.patch_size, downscale, emb.h, emb.w)
-        if kept is not None:
-            fill_uncovered(cmap, kept_yx, emb.patch_size, downscale, emb.h, emb.w, fill_class)
-        return cmap
+        return emb.fill_uncovered(cmap, downscale, fill_class)
 
     def similarity(self, emb: SlideEmbeddings, query_rows, downscale: int = 16) -> torch.Tensor:
         """float32[h // d, w // d] in [0, 1], ready for `tiles.heatmap_blend`: per cell, the mean over the tiles covering it of

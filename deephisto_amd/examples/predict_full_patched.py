@@ -204,21 +204,29 @@ def _anno_from_args(ap, args):
     return records
 
 
+def _dense_resident_only(ap, args, who: str) -> None:
+    """`who` (a flag, or a feature by name) runs over the dense sampler's grid of a resident slide: --random_sampler and --ondisk
+    are argparse errors."""
+    if args.random_sampler:
+        ap.error(f"{who} works on the dense sampler's grid; it cannot be combined with --random_sampler")
+    if args.ondisk:
+        ap.error(f"{who} needs the slide resident in HBM; it cannot be combined with --ondisk")
+
+
+def _fill_class(ap, flag: str, spelled: str) -> int:
+    """The class id of a --tissue_fill / --quality_fill value: a class label, or -1 for no class."""
+    labels = {a.label: a.id for a in AnnoDescription.with_known_colors(KNOWN_COLORS).anno_classes}
+    if spelled != "-1" and spelled not in labels:
+        ap.error(f"{flag} must be one of {', '.join(labels)} or -1, not {spelled!r}")
+    return labels.get(spelled, -1)
+
+
 def _tissue_from_args(ap, args) -> TissueFilter | None:
     """The TissueFilter of the --tissue flags, or None for `--tissue off`; a bad combination is an argparse error."""
     if args.tissue == "off":
         return None
-    if args.random_sampler:
-        ap.error("--tissue works on the dense sampler's grid; it cannot be combined with --random_sampler")
-    if args.ondisk:
-        ap.error("--tissue needs the slide resident in HBM; it cannot be combined with --ondisk")
-    labels = {a.label: a.id for a in AnnoDescription.with_known_colors(KNOWN_COLORS).anno_classes}
-    if args.tissue_fill in labels:
-        fill = labels[args.tissue_fill]
-    elif args.tissue_fill == "-1":
-        fill = -1
-    else:
-        ap.error(f"--tissue_fill must be one of {', '.join(labels)} or -1, not {args.tissue_fill!r}")
+    _dense_resident_only(ap, args, "--tissue")
+    fill = _fill_class(ap, "--tissue_fill", args.tissue_fill)
     try:
         threshold = "otsu" if args.tissue == "otsu" else int(args.tissue)
     except ValueError:
@@ -236,18 +244,9 @@ def _quality_from_args(ap, args) -> QualityFilter | None:
         if args.quality_json:
             ap.error("--quality_json needs --min_sharpness, --max_ink or --quality_fill")
         return None
-    if args.random_sampler:
-        ap.error("the quality filter works on the dense sampler's grid; it cannot be combined with --random_sampler")
-    if args.ondisk:
-        ap.error("the quality filter needs the slide resident in HBM; it cannot be combined with --ondisk")
-    labels = {a.label: a.id for a in AnnoDescription.with_known_colors(KNOWN_COLORS).anno_classes}
+    _dense_resident_only(ap, args, "the quality filter")
     spelled = args.quality_fill if args.quality_fill is not None else "-1"
-    if spelled in labels:
-        fill = labels[spelled]
-    elif spelled == "-1":
-        fill = -1
-    else:
-        ap.error(f"--quality_fill must be one of {', '.join(labels)} or -1, not {spelled!r}")
+    fill = _fill_class(ap, "--quality_fill", spelled)
     try:
         filt = QualityFilter(0 if args.min_sharpness is None else args.min_sharpness,
                              1.0 if args.max_ink is None else args.max_ink, fill_class=fill)
@@ -321,10 +320,7 @@ def _embeddings_from_args(ap, args) -> None:
                         ("--clusters", args.clusters), ("--load_clusters", args.load_clusters)):
         if not value:
             continue
-        if args.random_sampler:
-            ap.error(f"{flag} works on the dense sampler's grid; it cannot be combined with --random_sampler")
-        if args.ondisk:
-            ap.error(f"{flag} needs the slide resident in HBM; it cannot be combined with --ondisk")
+        _dense_resident_only(ap, args, flag)
         if args.tta != "off":
             ap.error(f"{flag} stores one forward pass per tile; it cannot be combined with --tta")
         if args.proba:

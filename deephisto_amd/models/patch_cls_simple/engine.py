@@ -361,10 +361,10 @@ class ResNetHIP(nn.Module):
         """Tiles per launch of the whole-slide paths: the most one inference launch takes."""
         return self.MAX_TILES
 
-    def forward_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int) -> torch.Tensor:
-        """Fused gather + /255 + eval forward straight from the uint8 slide in HBM: one launch, float32[n, n_classes] raw logits."""
+    def _launch_tiles(self, who: str, entry, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, *out):
+        """The argument checks and the one launch of forward_tiles / features_tiles; `out`: the entry's output pointers."""
         if self.training:
-            raise NotImplementedError("forward_tiles is an inference entry point; call .eval()")
+            raise NotImplementedError(f"{who} is an inference entry point; call .eval()")
         if not (slide.is_cuda and origins_dev.is_cuda):
             raise RuntimeError("slide and origins must live in GPU memory")
         if slide.dtype != torch.uint8 or slide.dim() != 3 or not slide.is_contiguous():
@@ -373,31 +373,22 @@ class ResNetHIP(nn.Module):
             raise ValueError("origins must be contiguous int32[n, 2]")
         h = self.lane_handles(1)[0]
         n = int(origins_dev.shape[0])
-        out = torch.empty((n, self.n_classes), dtype=torch.float32, device=slide.device)
-        fwd, name = self.tiles_entry()
+        tensors = [None if width is None else torch.empty((n, width), dtype=torch.float32, device=slide.device) for width in out]
+        fwd, name = entry()
         check(fwd(h, slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n, int(patch),
-                  out.data_ptr(), _stream(slide.device)), name)
-        return out
+                  *(None if t is None else t.data_ptr() for t in tensors), _stream(slide.device)), name)
+        return tensors
+
+    def forward_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int) -> torch.Tensor:
+        """Fused gather + /255 + eval forward straight from the uint8 slide in HBM: one launch, float32[n, n_classes] raw logits."""
+        return self._launch_tiles("forward_tiles", self.tiles_entry, slide, origins_dev, patch, self.n_classes)[0]
 
     def features_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, return_logits: bool = False):
         """forward_tiles one step earlier: float32[n, feature_width], the global average pool of every tile's last activation (what
         `fc` reads), in one launch; with `return_logits` also the float32[n, n_classes] logits of forward_tiles, bit for bit
         (without it the fc is skipped)."""
-        if self.training:
-            raise NotImplementedError("features_tiles is an inference entry point; call .eval()")
-        if not (slide.is_cuda and origins_dev.is_cuda):
-            raise RuntimeError("slide and origins must live in GPU memory")
-        if slide.dtype != torch.uint8 or slide.dim() != 3 or not slide.is_contiguous():
-            raise ValueError("slide must be contiguous uint8[h, w, 3]")
-        if origins_dev.dtype != torch.int32 or origins_dev.dim() != 2 or origins_dev.shape[-1] != 2 or not origins_dev.is_contiguous():
-            raise ValueError("origins must be contiguous int32[n, 2]")
-        h = self.lane_handles(1)[0]
-        n = int(origins_dev.shape[0])
-        feat = torch.empty((n, self.feature_width), dtype=torch.float32, device=slide.device)
-        logits = torch.empty((n, self.n_classes), dtype=torch.float32, device=slide.device) if return_logits else None
-        fwd, name = self.features_entry()
-        check(fwd(h, slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n, int(patch),
-                  feat.data_ptr(), logits.data_ptr() if return_logits else None, _stream(slide.device)), name)
+        feat, logits = self._launch_tiles("features_tiles", self.features_entry, slide, origins_dev, patch, self.feature_width,
+                                          self.n_classes if return_logits else None)
         return (feat, logits) if return_logits else feat
 
     def forward_infer(self, x: torch.Tensor) -> torch.Tensor:

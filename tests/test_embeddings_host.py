@@ -176,6 +176,19 @@ def test_prototype_classifier_npz_round_trip(built_lib, tmp_path):
             PrototypeClassifier(bad)
 
 
+@pytest.mark.parametrize("h,w,P,S,B,n_unique,n_padded", [(700, 900, 96, 64, 16, 154, 160), (700, 900, 96, 64, 11, 154, 154)])
+def test_grid_rebuilt_from_stored_geometry_is_the_samplers_padded_list(built_lib, h, w, P, S, B, n_unique, n_padded):
+    from deephisto_amd import tiles
+    from deephisto_amd.plan import TileGrid
+    want, n_u = tiles.tile_grid(h, w, P, S, B)
+    assert (n_u, len(want)) == (n_unique, n_padded)
+    grid = TileGrid.from_geometry(h, w, P, S, n_unique, n_padded)
+    assert (grid.n_unique, grid.patch_size, grid.h, grid.w) == (n_unique, P, h, w)
+    assert grid.origins.dtype == np.int32 and np.array_equal(grid.origins, want)
+    with pytest.raises(ValueError, match="does not reproduce the tile grid"):
+        TileGrid.from_geometry(h, w, P, S, n_unique - 1, n_padded)
+
+
 # ---- refusals ---------------------------------------------------------------------------------------------------------
 def test_extract_embeddings_refuses_what_is_out_of_scope(built_lib):
     from deephisto_amd.embeddings import extract_embeddings

@@ -109,6 +109,31 @@ def test_kept_list_and_class_map_follow_predict_full_patched(setup, dev, tmp_pat
     assert _same(back.features, femb.features) and torch.equal(back.class_map(DOWN, fill_class=3), want)
 
 
+def test_both_filters_at_once_follow_predict_full_patched(setup, dev):
+    """The tissue stage and the quality stage together: both routes compose the same lists and finish the same map."""
+    from deephisto_amd.embeddings import extract_embeddings
+    from deephisto_amd.predict import predict_full_patched
+    from deephisto_amd.quality import QualityFilter, sharpness_summary
+    from deephisto_amd.tissue import TissueFilter
+    m, smp = setup
+    tissue, first = TissueFilter("otsu", fill_class=3), {}
+    extract_embeddings(smp, m, tissue=tissue, quality=QualityFilter(fill_class=3), quality_info=first)
+    q = sharpness_summary(first["stats"])
+    min_sharpness = int((q["q1"] + q["q3"]) / 2)
+    assert q["q1"] < min_sharpness < q["q3"], q
+    quality = QualityFilter(min_sharpness=min_sharpness, fill_class=3)
+    tinfo, qinfo, etinfo, eqinfo = {}, {}, {}, {}
+    emb = extract_embeddings(smp, m, tissue=tissue, tissue_info=etinfo, quality=quality, quality_info=eqinfo, return_logits=True)
+    for dedupe in (False, True):
+        want = predict_full_patched(smp, m, 5, downscale=DOWN, dedupe_padding=dedupe, tissue=tissue, tissue_info=tinfo,
+                                    quality=quality, quality_info=qinfo)
+        assert np.array_equal(eqinfo["kept"], qinfo["kept"]) and np.array_equal(etinfo["kept"], tinfo["kept"])
+        assert 0 < len(qinfo["kept"]) < len(tinfo["kept"]) < smp.n_tiles
+        assert qinfo["n_kept"] == len(qinfo["kept"]) and tinfo["n_kept"] == len(tinfo["kept"])
+        assert torch.equal(emb.class_map(DOWN, dedupe_padding=dedupe, fill_class=3), want), f"dedupe_padding={dedupe}"
+    assert np.array_equal(emb.tile_index, qinfo["kept"])
+
+
 def test_prototype_map_on_real_features(setup, dev):
     """Labels: the two-region synthetic annotation of ANNO_SEED.  predict_map must equal the float64 NumPy pipeline on every cell whose
     float64 top-two accumulated scores differ by more than the scores' bound ((D + 2) u sum |f| |p|) summed over the cell's tiles; the

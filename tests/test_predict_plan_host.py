@@ -80,6 +80,27 @@ def test_launch_size(monkeypatch):
     assert launch_size(1000, 4096) == 4096
 
 
+@pytest.mark.parametrize("world,n_unique,micro_batch", list(itertools.product((1, 2, 3), (0, 1, 11, 12, 13), (4, 4096))))
+def test_plan_shards_tile_the_work_in_order(world, n_unique, micro_batch):
+    """plan_shard with explicit world and rank, no filter, on the CPU: the ranks' [lo, hi) tile [0, n_work) in order, every rank
+    sizes the same block for the exchange, and the launch size is launch_size of the rank's own share."""
+    from deephisto_amd.plan import TileGrid, plan_shard
+    from deephisto_amd.predict import launch_size
+    origins = _origins(n_unique, 3 if n_unique else 0)
+    grid = TileGrid(origins, n_unique, 112, 2000, 2000)
+    end = 0
+    for rank in range(world):
+        p = plan_shard(grid, world, rank, micro_batch, "cpu")
+        assert (p.world, p.rank, p.n_work, p.kept, p.kept_yx_dev, p.fill_class) == (world, rank, n_unique, None, None, None)
+        assert p.lo == end and p.lo <= p.hi
+        end = p.hi
+        assert p.per_rank == -(-n_unique // world) and p.hi - p.lo <= p.per_rank
+        assert p.mb == launch_size(p.hi - p.lo, micro_batch)
+        assert p.o_dev.dtype.is_floating_point is False and p.o_dev.device.type == "cpu"
+        np.testing.assert_array_equal(p.o_dev.numpy(), origins[p.lo:p.hi])
+    assert end == n_unique
+
+
 # every project name importable from deephisto_amd.examples.predict_full_patched before the engine and the visualiser moved out
 # (taken by hand from that file; `_finish_masked`, which `_finish` replaced, and the stdlib modules it imported are left out)
 SURFACE = (
