@@ -1,6 +1,7 @@
 // resnet50_infer.inc -- bf16 INFERENCE engine of the ResNet-50 patch classifier (dh_resnet50_*), the counterpart of dh_resnet18's
 // bf16 path for the network get_model(..., arch="resnet50") trains (torchvision resnet50 v1.5 + fc[n_cls, 2048]).
-// Included at the end of resnet_kernels.hip, after gemm1x1_infer.inc.
+// Included at the end of resnet_kernels.hip, after gemm1x1_infer.inc.  The handle's common state, the parameter entry, finalize's checks
+// and the tiles / tap / operands entries are infer_core.inc's, shared with dh_resnet18; the network itself is net_desc.inc's.
 //
 // Eval-mode BN is folded at finalize (host, double): W' = W * s, b' = beta - mean * s with s = gamma / sqrt(var + 1e-5).  Every
 // convolution is then ONE kernel pass that writes its final bf16 activation:
@@ -23,58 +24,12 @@ constexpr int R50_MAX_P = 256;
 constexpr int64_t R50_MAX_TILES = ((int64_t)1 << 31) / ((int64_t)256 * (R50_MAX_P / 4) * (R50_MAX_P / 4) * 2);
 static_assert(R50_MAX_TILES == DH_RESNET50_MAX_TILES, "include/deephisto_hip.h states the launch limit");
 
-struct dh_resnet50 {
-  struct Blk { int c1 = -1, c2 = -1, c3 = -1, ds = -1, stride = 1; };
-  int n_classes = 0;
-  std::map<std::string, std::vector<float>> params;   // host copies by state_dict name
-  std::vector<ConvLayer> convs;                       // index 0 = stem; w_dev = folded bf16 operand, shift_dev = folded bias
-  std::vector<Blk> blocks;
-  float* ones = nullptr;                              // scale = 1 for the stem / 3x3 epilogues (shared by every layer)
-  float* fc_w = nullptr;
-  float* fc_b = nullptr;
-  bool finalized = false;
-  void* ws = nullptr;                                 // activation buffers, sized for the largest launch shape so far
-  size_t ws_bytes = 0;
-  std::vector<int32_t> yx_host;                       // origin check of forward_tiles
+struct dh_resnet50 : InferNet {   // convs: w_dev = folded bf16 operand, shift_dev = folded bias, scale_dev = ones
+  float* ones = nullptr;          // scale = 1 for the stem / 3x3 epilogues (shared by every layer)
+  std::vector<int32_t> yx_host;   // origin check of forward_tiles
 };
 
 namespace {
-
-void r50_topology(dh_resnet50* net) {
-  net->convs.clear(); net->blocks.clear();
-  auto add = [&](const std::string& n, const std::string& bn, int cin, int cout, int ks, int stride) {
-    net->convs.push_back({n, bn, cin, cout, ks, stride});
-    return (int)net->convs.size() - 1;
-  };
-  add("conv1", "bn1", 3, 64, 7, 2);
-  const int width[4] = {64, 128, 256, 512}, nblk[4] = {3, 4, 6, 3};
-  int cin = 64;
-  for (int s = 0; s < 4; ++s)
-    for (int k = 0; k < nblk[s]; ++k) {
-      const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(k);
-      const int stride = (k == 0 && s > 0) ? 2 : 1, w = width[s], cout = 4 * w;
-      dh_resnet50::Blk b;
-      b.stride = stride;
-      b.c1 = add(pre + ".conv1", pre + ".bn1", cin, w, 1, 1);
-      b.c2 = add(pre + ".conv2", pre + ".bn2", w, w, 3, stride);   // torchvision v1.5: the stage stride on the 3x3 conv
-      b.c3 = add(pre + ".conv3", pre + ".bn3", w, cout, 1, 1);
-      if (stride != 1 || cin != cout) b.ds = add(pre + ".downsample.0", pre + ".downsample.1", cin, cout, 1, stride);
-      net->blocks.push_back(b);
-      cin = cout;
-    }
-}
-
-int64_t r50_expected_elems(const dh_resnet50* net, const std::string& name) {
-  if (name == "fc.weight") return (int64_t)net->n_classes * 2048;
-  if (name == "fc.bias") return net->n_classes;
-  for (const auto& c : net->convs) {
-    if (name == c.name + ".weight") return (int64_t)c.cout * c.cin * c.ks * c.ks;
-    for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"})
-      if (name == c.bn + s) return c.cout;
-    if (name == c.bn + ".num_batches_tracked") return 1;
-  }
-  return -1;
-}
 
 // Tile shape per GEMM shape.  128 x 128 (NMT = 4: a third less operand ingest through L2) where the channel count allows it and K <= 1024;
 // 128 x 64 at K = 2048 (measured on the training engine, profiles/r04_exp_gemm_wide.txt: the wide tile is 14-22 % faster at K <= 1024,
@@ -119,25 +74,20 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
   const size_t px = (size_t)B * H2 * H2 * 2;   // bytes per channel of a stage-1 map
   const size_t big = al(256 * px), t1 = al(128 * px), t2 = al(64 * px);
   const size_t need = 2 * big + t1 + t2;
-  if (need > net->ws_bytes) {
-    if (net->ws) DH_HIP(hipFree(net->ws));
-    net->ws = nullptr; net->ws_bytes = 0;
-    DH_HIP(hipMalloc(&net->ws, need));
-    net->ws_bytes = need;
-  }
+  int rc;
+  if ((rc = infer_workspace(net, need))) return rc;
   char* base = static_cast<char*>(net->ws);
   bf16_t* X = reinterpret_cast<bf16_t*>(base);
   bf16_t* D = reinterpret_cast<bf16_t*>(base + big);
   bf16_t* T1 = reinterpret_cast<bf16_t*>(base + 2 * big);
   bf16_t* T2 = reinterpret_cast<bf16_t*>(base + 2 * big + t1);
-  int rc;
   DH_REQUIRE(stem_seam_bytes(B, P) <= t1, "resnet50 forward: seam scratch larger than the bottleneck buffer");
   if ((rc = launch_stem_pool(net->convs[0], x, slide, slide_h, slide_w, yx, B, P, X, T1, st))) return rc;   // T1: free until conv1
   for (const char* nm : {"conv1", "maxpool"})   // the fused stem stores only the pooled map
     if ((rc = tap_after<__bf16>(tap, nm, X, 64, H2, H2, 32, st))) return rc;
   int H = H2;
-  for (const dh_resnet50::Blk& b : net->blocks) {
-    const ConvLayer &c1 = net->convs[b.c1], &c2 = net->convs[b.c2], &c3 = net->convs[b.c3];
+  for (const BlockDesc& b : net->desc->blocks) {
+    const ConvLayer &c1 = net->convs[b.conv[0]], &c2 = net->convs[b.conv[1]], &c3 = net->convs[b.conv[2]];
     const int Ho = (H - 1) / b.stride + 1;
     if ((rc = r50_gemm(c1, X, nullptr, T1, B, H, H, true, st))) return rc;
     if ((rc = tap_after<__bf16>(tap, c1.name, T1, c1.cout, H, H, 32, st))) return rc;
@@ -158,14 +108,14 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
     H = Ho;
   }
   if (feat)   // dh_resnet50_features_tiles: the same head, the pooled vector stored as well
-    hipLaunchKernelGGL(r50_head_kernel<true>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits, feat);
+    hipLaunchKernelGGL(r50_head_kernel<true>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
   else
-    hipLaunchKernelGGL(r50_head_kernel<false>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w, net->fc_b, net->n_classes, logits, nullptr);
+    hipLaunchKernelGGL(r50_head_kernel<false>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
-int r50_check_forward(dh_resnet50* net, int64_t n, int32_t P, const void* logits, const char* what) {
+int r50_check_forward(const InferNet* net, int64_t n, int32_t P, const void* logits, const char* what) {
   DH_REQUIRE(net != nullptr, "%s: null handle", what);
   DH_REQUIRE(net->finalized, "%s: call dh_resnet50_finalize after setting parameters", what);
   DH_REQUIRE(P >= 64 && P <= R50_MAX_P && P % 32 == 0, "%s: patch %d unsupported (64 <= P <= %d, P %% 32 == 0)", what, P, R50_MAX_P);
@@ -175,6 +125,33 @@ int r50_check_forward(dh_resnet50* net, int64_t n, int32_t P, const void* logits
   return DH_OK;
 }
 
+// feat rows are written as float4: 16-byte aligned; 1x1 operands are gemm1x1_infer.inc's plain bf16 [cout][cin]
+const InferEngine R50_ENGINE = {"resnet50", r50_check_forward, 16, true};
+
+// The origins are device memory: they are read back (n pairs, one synchronisation of `st`) and checked before any launch, so that an
+// origin outside the slide is an error, not a read past the tile (the stem itself never reads outside the slide allocation either).
+int r50_check_origins(dh_resnet50* net, int64_t h, int64_t w, const int32_t* yx, int64_t n, int32_t P, hipStream_t st, const char* what) {
+  net->yx_host.resize((size_t)n * 2);
+  DH_HIP(hipMemcpyAsync(net->yx_host.data(), yx, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  DH_HIP(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t y = net->yx_host[2 * i], x = net->yx_host[2 * i + 1];
+    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "%s: origin %lld (y=%d, x=%d) puts a %d-pixel tile outside the %lldx%lld slide",
+               what, (long long)i, y, x, P, (long long)h, (long long)w);
+  }
+  return DH_OK;
+}
+
+// both tiles entries: the origin check, then the forward
+int r50_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n, int32_t P, float* feat,
+              float* logits, const float* out, void* stream, const char* what) {
+  hipStream_t st = dh::as_stream(stream);
+  return infer_tiles(R50_ENGINE, net, slide, h, w, yx, n, P, feat, out, what, [&](Tap* tap) {
+    if (int rc = r50_check_origins(net, h, w, yx, n, P, st, what)) return rc;
+    return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, tap, feat);
+  });
+}
+
 }  // namespace
 
 extern "C" int dh_resnet50_create(dh_resnet50** out, int32_t n_classes) {
@@ -182,65 +159,41 @@ extern "C" int dh_resnet50_create(dh_resnet50** out, int32_t n_classes) {
   DH_REQUIRE(n_classes > 0 && n_classes <= 1024, "resnet50 create: n_classes=%d", n_classes);
   if (int erc = dh::env_check()) return erc;
   auto* net = new dh_resnet50();
-  net->n_classes = n_classes;
-  r50_topology(net);
+  infer_init(net, "resnet50", n_classes);
   *out = net;
   return DH_OK;
 }
 
 extern "C" void dh_resnet50_destroy(dh_resnet50* net) {
   if (!net) return;
-  for (auto& c : net->convs) {
-    if (c.w_dev) (void)hipFree(c.w_dev);
-    if (c.shift_dev) (void)hipFree(c.shift_dev);   // scale_dev is net->ones
-  }
+  for (auto& c : net->convs) c.scale_dev = nullptr;   // every conv's scale is net->ones
   if (net->ones) (void)hipFree(net->ones);
-  if (net->fc_w) (void)hipFree(net->fc_w);
-  if (net->fc_b) (void)hipFree(net->fc_b);
-  if (net->ws) (void)hipFree(net->ws);
+  infer_free(net);
   delete net;
 }
 
 extern "C" int dh_resnet50_set_param(dh_resnet50* net, const char* name, const float* data, int64_t n_elem) {
-  DH_REQUIRE(net && name && data, "resnet50 set_param: null argument");
-  const int64_t want = r50_expected_elems(net, name);
-  DH_REQUIRE(want >= 0, "resnet50 set_param: unknown parameter '%s'", name);
-  DH_REQUIRE(want == n_elem, "resnet50 set_param: '%s' has %lld elements, expected %lld", name, (long long)n_elem, (long long)want);
-  net->params[name].assign(data, data + n_elem);
-  net->finalized = false;
-  return DH_OK;
+  return infer_set_param(R50_ENGINE, net, name, data, n_elem);
 }
 
 extern "C" int dh_resnet50_finalize(dh_resnet50* net, void* stream) {
-  DH_REQUIRE(net != nullptr, "resnet50 finalize: null handle");
   (void)stream;   // uploads are synchronous (hipMemcpy), like dh_resnet18_finalize
-  net->finalized = false;
-  auto get = [&](const std::string& k) -> const std::vector<float>* {
-    auto it = net->params.find(k);
-    return it == net->params.end() ? nullptr : &it->second;
-  };
-  for (const auto& c : net->convs) {
-    DH_REQUIRE(get(c.name + ".weight") && get(c.bn + ".weight") && get(c.bn + ".bias") && get(c.bn + ".running_mean") &&
-               get(c.bn + ".running_var"), "resnet50 finalize: parameters of '%s' / '%s' are not all set", c.name.c_str(), c.bn.c_str());
-  }
-  const auto *fw = get("fc.weight"), *fb = get("fc.bias");
-  DH_REQUIRE(fw && fb, "resnet50 finalize: fc.weight / fc.bias are not set");
-  int rc;
+  int rc = infer_finalize_begin(R50_ENGINE, net);
+  if (rc) return rc;
   if (!net->ones) {
-    const std::vector<float> one(2048, 1.0f);
+    const std::vector<float> one(net->desc->feat, 1.0f);
     if ((rc = upload(one, reinterpret_cast<void**>(&net->ones)))) return rc;
   }
+  std::vector<double> scale, shift;
   for (auto& c : net->convs) {
-    const auto &w = *get(c.name + ".weight"), &g = *get(c.bn + ".weight"), &be = *get(c.bn + ".bias"), &mu = *get(c.bn + ".running_mean"),
-               &var = *get(c.bn + ".running_var");
-    // eval-mode BN (eps = 1e-5, torch default) folded into the weights and a bias
+    const std::vector<float>& w = *infer_param(net, c.name + ".weight");
+    // eval-mode BN folded into the weights and a bias
+    infer_bn_affine(net, c, scale, shift);
     const int64_t per = (int64_t)c.cin * c.ks * c.ks;
-    std::vector<float> wf(w.size()), bias(c.cout);
-    for (int k = 0; k < c.cout; ++k) {
-      const double s = (double)g[k] / sqrt((double)var[k] + 1e-5);
-      bias[k] = (float)((double)be[k] - (double)mu[k] * s);
-      for (int64_t i = 0; i < per; ++i) wf[k * per + i] = (float)((double)w[k * per + i] * s);
-    }
+    std::vector<float> wf(w.size());
+    const std::vector<float> bias(shift.begin(), shift.end());
+    for (int k = 0; k < c.cout; ++k)
+      for (int64_t i = 0; i < per; ++i) wf[k * per + i] = (float)((double)w[k * per + i] * scale[k]);
     if (c.ks == 1) {   // W'[cout][cin], bf16 (gemm1x1_infer.inc's W operand)
       std::vector<uint16_t> wb(wf.size());
       for (size_t i = 0; i < wf.size(); ++i) wb[i] = host_bf16(wf[i]);
@@ -254,9 +207,7 @@ extern "C" int dh_resnet50_finalize(dh_resnet50* net, void* stream) {
     if (rc || (rc = upload(bias, reinterpret_cast<void**>(&c.shift_dev)))) return rc;
     c.scale_dev = net->ones;
   }
-  if ((rc = upload(*fw, reinterpret_cast<void**>(&net->fc_w))) || (rc = upload(*fb, reinterpret_cast<void**>(&net->fc_b)))) return rc;
-  net->finalized = true;
-  return DH_OK;
+  return infer_finalize_end(net);
 }
 
 extern "C" int dh_resnet50_forward(dh_resnet50* net, const float* x, int64_t n, int32_t P, float* logits, void* stream) {
@@ -266,76 +217,28 @@ extern "C" int dh_resnet50_forward(dh_resnet50* net, const float* x, int64_t n, 
   return r50_forward_impl(net, x, nullptr, 0, 0, nullptr, (int)n, P, logits, dh::as_stream(stream));
 }
 
-// The fused gather + forward behind both tiles entries; `what` names the entry in messages.  `feat` (features_tiles: the pooled
-// 2048-vector of every tile, the tap one step before the logits) is stored as well when given and must be 16-byte aligned (its rows
-// are written as float4); `out` is the entry's mandatory output.  The origins are device memory: they are read back (n pairs, one synchronisation of `stream`) and checked before
-// any launch, so that an origin outside the slide is an error, not a read past the tile (the stem itself never reads outside the slide
-// allocation either).
-static int r50_forward_tiles_impl(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n, int32_t P,
-                                  float* feat, float* logits, const float* out, void* stream, const char* what) {
-  if (int rc = r50_check_forward(net, n, P, out, what)) return rc;
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "%s: null slide or origins", what);
-  DH_REQUIRE((reinterpret_cast<uintptr_t>(feat) & 15) == 0, "%s: feat_dev is not 16-byte aligned", what);
-  DH_REQUIRE(h >= P && w >= P, "%s: patch %d does not fit %lldx%lld", what, P, (long long)h, (long long)w);
-  hipStream_t st = dh::as_stream(stream);
-  net->yx_host.resize((size_t)n * 2);
-  DH_HIP(hipMemcpyAsync(net->yx_host.data(), yx, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  DH_HIP(hipStreamSynchronize(st));
-  for (int64_t i = 0; i < n; ++i) {
-    const int32_t y = net->yx_host[2 * i], x = net->yx_host[2 * i + 1];
-    DH_REQUIRE(y >= 0 && x >= 0 && y <= h - P && x <= w - P, "%s: origin %lld (y=%d, x=%d) puts a %d-pixel tile outside the %lldx%lld slide",
-               what, (long long)i, y, x, P, (long long)h, (long long)w);
-  }
-  return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, nullptr, feat);
-}
-
 extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
                                          int32_t P, float* logits, void* stream) {
-  return r50_forward_tiles_impl(net, slide, h, w, yx, n, P, nullptr, logits, logits, stream, "resnet50 forward_tiles");
+  return r50_tiles(net, slide, h, w, yx, n, P, nullptr, logits, logits, stream, "resnet50 forward_tiles");
 }
 
 extern "C" int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
                                           int32_t P, float* feat, float* logits, void* stream) {
-  return r50_forward_tiles_impl(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet50 features_tiles");
+  return r50_tiles(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet50 features_tiles");
 }
 
-// Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (Tap above), and a conv's
-// operands as the engine holds them after finalize: the folded, bf16-rounded weight, scale (1) and the folded bias.
+// Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (no origin check), and a
+// conv's operands as the engine holds them after finalize: the folded, bf16-rounded weight, scale (1) and the folded bias.
 extern "C" int dh_debug_resnet50_forward_tap(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n,
                                              int32_t P, const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev,
                                              int64_t out_elems, float* logits_dev, void* stream) {
-  if (int rc = r50_check_forward(net, n, P, logits_dev, "resnet50 forward tap")) return rc;
-  DH_REQUIRE(n > 0 && slide && yx_dev && conv_name, "resnet50 forward tap: null argument or empty launch");
-  DH_REQUIRE(h >= P && w >= P, "resnet50 forward tap: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
-  DH_REQUIRE(tap_name_known(net, conv_name), "resnet50 forward tap: unknown conv '%s'", conv_name);
   hipStream_t st = dh::as_stream(stream);
-  if (int rc = tap_check(sel_dev, k, n, out_dev, logits_dev, st)) return rc;
-  Tap tap;
-  tap.name = conv_name; tap.sel = sel_dev; tap.k = k; tap.out = out_dev; tap.out_elems = out_elems;
-  if (int rc = r50_forward_impl(net, nullptr, slide, h, w, yx_dev, (int)n, P, logits_dev, st, &tap)) return rc;
-  DH_REQUIRE(tap.hit, "resnet50 forward tap: '%s' is not stored by this engine", conv_name);
-  return DH_OK;
+  return infer_tap(R50_ENGINE, net, slide, h, w, yx_dev, n, P, conv_name, sel_dev, k, out_dev, out_elems, logits_dev, st, [&](Tap* tap) {
+    return r50_forward_impl(net, nullptr, slide, h, w, yx_dev, (int)n, P, logits_dev, st, tap);
+  });
 }
 
 extern "C" int dh_debug_resnet50_operands(dh_resnet50* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
                                           float* shift_host, int64_t c_elems) {
-  DH_REQUIRE(net && net->finalized && conv_name, "resnet50 operands: needs a finalized network");
-  for (const auto& c : net->convs) {
-    if (c.name != conv_name) continue;
-    if (c.ks != 1) return read_operands(c, 2, true, w_host, w_elems, scale_host, shift_host, c_elems);
-    DH_REQUIRE(w_host && scale_host && shift_host && w_elems == (int64_t)c.cout * c.cin && c_elems == c.cout,
-               "resnet50 operands %s: bad buffers", c.name.c_str());
-    std::vector<uint16_t> wb((size_t)w_elems);   // gemm1x1_infer.inc's W operand: plain bf16 [cout][cin]
-    DH_HIP(hipMemcpy(wb.data(), c.w_dev, wb.size() * 2, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < w_elems; ++i) {
-      const uint32_t u = (uint32_t)wb[i] << 16;
-      memcpy(&w_host[i], &u, 4);
-    }
-    DH_HIP(hipMemcpy(scale_host, c.scale_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
-    DH_HIP(hipMemcpy(shift_host, c.shift_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
-    return DH_OK;
-  }
-  dh::set_error("resnet50 operands: unknown conv '%s'", conv_name);
-  return DH_EINVAL;
+  return infer_operands(R50_ENGINE, net, 2, conv_name, w_host, w_elems, scale_host, shift_host, c_elems);
 }

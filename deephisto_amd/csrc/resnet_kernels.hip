@@ -521,72 +521,17 @@ __global__ __launch_bounds__(256) void avgpool_fc_kernel(const T* __restrict__ i
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct ConvLayer {
-  std::string name;  // state_dict prefix of the conv ("layer1.0.conv1"); BN is its sibling
-  std::string bn;
-  int cin, cout, ks, stride;
-  void* w_dev = nullptr;        // packed weights
-  void* w2_dev = nullptr;       // bf16 inference, stride-2 3x3 convs with cout % 128 == 0 and their downsample convs: the wide (HALF) packing
-  float* scale_dev = nullptr;   // [cout]
-  float* shift_dev = nullptr;
-};
+}  // namespace
+
+#include "net_desc.inc"
+
+namespace {
 
 inline uint16_t host_bf16(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
   if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x7FFFFFu)) return (uint16_t)((u >> 16) | 0x40);
   return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-}  // namespace
-
-struct dh_train;
-struct dh_resnet18 {
-  dh_train* train = nullptr;  // training state (train.inc), owned
-  int n_classes = 0;
-  int dtype = DH_DTYPE_F32;
-  std::map<std::string, std::vector<float>> params;  // host copies by state_dict name
-  std::vector<ConvLayer> convs;                      // index 0 = stem
-  float* fc_w_dev = nullptr;
-  float* fc_b_dev = nullptr;
-  bool finalized = false;
-  // activation workspace
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
-  int esz() const { return dtype == DH_DTYPE_F32 ? 4 : 2; }
-};
-
-namespace {
-
-void build_topology(dh_resnet18* net) {
-  net->convs.clear();
-  net->convs.push_back({"conv1", "bn1", 3, 64, 7, 2});
-  const int ch[4] = {64, 128, 256, 512};
-  int cin = 64;
-  for (int s = 0; s < 4; ++s) {
-    for (int blk = 0; blk < 2; ++blk) {
-      const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(blk);
-      const int stride = (blk == 0 && s > 0) ? 2 : 1;
-      const int bcin = blk == 0 ? cin : ch[s];
-      net->convs.push_back({pre + ".conv1", pre + ".bn1", bcin, ch[s], 3, stride});
-      net->convs.push_back({pre + ".conv2", pre + ".bn2", ch[s], ch[s], 3, 1});
-      if (blk == 0 && s > 0)
-        net->convs.push_back({pre + ".downsample.0", pre + ".downsample.1", bcin, ch[s], 1, 2});
-    }
-    cin = ch[s];
-  }
-}
-
-int64_t expected_elems(const dh_resnet18* net, const std::string& name) {
-  if (name == "fc.weight") return (int64_t)net->n_classes * 512;
-  if (name == "fc.bias") return net->n_classes;
-  for (const auto& c : net->convs) {
-    if (name == c.name + ".weight") return (int64_t)c.cout * c.cin * c.ks * c.ks;
-    for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"})
-      if (name == c.bn + s) return c.cout;
-    if (name == c.bn + ".num_batches_tracked") return 1;
-  }
-  return -1;
 }
 
 // Pack [cout][cin][ks][ks] f32 into fragment order:
@@ -1257,54 +1202,18 @@ int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide
   return DH_OK;
 }
 
-// Test hook of the inference forwards (dh_debug_resnet18_forward_tap, dh_debug_resnet50_forward_tap): right after the launch that stores
-// conv `name`'s output, that buffer's images sel[0..k) as float32 NCHW [k][C][H][W], stream-ordered before any later launch can overwrite
-// it.  A forward without a tap (nullptr) issues exactly its own launches.
-struct Tap {
-  std::string name;
-  const int32_t* sel = nullptr;   // device, checked against the launch's n by the hook
-  int k = 0;
-  float* out = nullptr;
-  int64_t out_elems = 0;
-  bool hit = false;
+}  // namespace
+
+#include "infer_core.inc"
+
+struct dh_train;
+struct dh_resnet18 : InferNet {
+  dh_train* train = nullptr;  // training state (train.inc), owned
+  int dtype = DH_DTYPE_F32;
+  int esz() const { return dtype == DH_DTYPE_F32 ? 4 : 2; }
 };
 
-// in: [image][C/cp][H][W][cp] -- cp = 32: channel-blocked, 16: 16-channel planes, C: NHWC
-template <typename T>
-__global__ void tap_gather_kernel(const T* __restrict__ in, const int32_t* __restrict__ sel, int C, int cp, int64_t hw, int64_t total,
-                                  float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t px = i % hw;
-    const int c = (int)((i / hw) % C);
-    const int64_t b = sel[i / hw / C];
-    out[i] = (float)in[((b * (C / cp) + c / cp) * hw + px) * cp + c % cp];
-  }
-}
-
-template <typename T>
-int tap_after(Tap* tap, const std::string& name, const void* buf, int C, int H, int W, int cp, hipStream_t st) {
-  if (!tap || name != tap->name) return DH_OK;
-  const int64_t total = (int64_t)tap->k * C * H * W;
-  DH_REQUIRE(total == tap->out_elems, "forward tap %s: the output holds %lld elements, [%d][%d][%d][%d] needs %lld", name.c_str(),
-             (long long)tap->out_elems, tap->k, C, H, W, (long long)total);
-  hipLaunchKernelGGL((tap_gather_kernel<T>), dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, st,
-                     static_cast<const T*>(buf), tap->sel, C, cp, (int64_t)H * W, total, tap->out);
-  DH_LAUNCH_CHECK();
-  tap->hit = true;
-  return DH_OK;
-}
-
-// Host checks of a tap request before any launch: k in [1, n], every sel in [0, n) (read back: one synchronisation of `st`)
-int tap_check(const int32_t* sel_dev, int32_t k, int64_t n, float* out_dev, const float* logits_dev, hipStream_t st) {
-  DH_REQUIRE(sel_dev && out_dev && logits_dev, "forward tap: null argument");
-  DH_REQUIRE(k > 0 && k <= n, "forward tap: k = %d selected images out of range [1, %lld]", k, (long long)n);
-  std::vector<int32_t> sel(k);
-  DH_HIP(hipMemcpyAsync(sel.data(), sel_dev, (size_t)k * 4, hipMemcpyDeviceToHost, st));
-  DH_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < k; ++i)
-    DH_REQUIRE(sel[i] >= 0 && sel[i] < n, "forward tap: sel[%d] = %d outside the launch of %lld tiles", i, sel[i], (long long)n);
-  return DH_OK;
-}
+namespace {
 
 template <typename T>
 int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
@@ -1322,12 +1231,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
              sizeof(T) == 2 ? "bf16" : "float32");
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t need = al(stem_bytes) + 3 * al(act_bytes);
-  if (need > net->ws_bytes) {
-    if (net->ws) DH_HIP(hipFree(net->ws));
-    net->ws = nullptr; net->ws_bytes = 0;
-    DH_HIP(hipMalloc(&net->ws, need));
-    net->ws_bytes = need;
-  }
+  if (int rc = infer_workspace(net, need)) return rc;
   char* base = static_cast<char*>(net->ws);
   void* S = base;
   void* bufA = base + al(stem_bytes);
@@ -1376,68 +1280,74 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
   // ([image][C/32][H][W][32], written that way by the fused stem), f32 activations NHWC.
   constexpr bool BLK = sizeof(T) == 2;
   int H = H2, W = H2;
-  size_t ci = 1;
   bool x16 = false;   // X holds the block input in 16-channel planes (written that way for the wide stride-2 kernel)
   void* X = bufA;     // block input / output; bufB: the block's intermediate; `other`: the third buffer
-  for (int s = 0; s < 4; ++s) {
-    for (int blk = 0; blk < 2; ++blk) {
-      const bool has_ds = (blk == 0 && s > 0);
-      const ConvLayer& c1 = net->convs[ci];
-      const ConvLayer& c2 = net->convs[ci + 1];
-      void* other = X == bufA ? bufC : bufA;
-      int Ho, Wo, h2, w2;
-      int rc;
-      const void* resid = X;
-      if (has_ds) {
-        // conv1 (3x3/2 + BN + ReLU) and the 1x1/2 downsample (+ BN) of the block in ONE launch
-        Ho = (H + 2 - 3) / 2 + 1; Wo = (W + 2 - 3) / 2 + 1;
-        rc = launch_conv3x3<T, 2>(c1, X, nullptr, bufB, B, H, W, true, st, Ho, Wo, &net->convs[ci + 2], other, BLK, 0, 0, x16, false);
-        if (rc) return rc;
-        if ((rc = tap_after<T>(tap, net->convs[ci + 2].name, other, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
-        resid = other;
-      } else {
-        DH_REQUIRE(!x16, "resnet18 forward: only a downsample block reads 16-channel planes");
-        rc = run_conv<T>(c1, X, nullptr, bufB, B, H, W, true, st, &Ho, &Wo, BLK);
-        if (rc) return rc;
-      }
-      if ((rc = tap_after<T>(tap, c1.name, bufB, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
-      // the block that follows starts with a stride-2 conv on the wide kernel: this block's output goes out in 16-channel planes
-      x16 = false;
-      if (blk == 1 && s < 3) {
-        const ConvLayer& n1 = net->convs[ci + 2];
-        const ConvLayer& nds = net->convs[ci + 4];
-        x16 = BLK && s2_wide_eligible(n1, nds, esz, (Wo + 2 - 3) / 2 + 1);
-      }
-      // conv2 + residual.  Same layout: in place over the residual (every lane reads the elements it then writes).  16-channel planes out,
-      // 32-channel planes in: the two layouts put different pixels at the same address -- the output goes to the third buffer
-      void* O = X;
-      if (has_ds) O = X;                 // the block input is dead once conv1 and the downsample have run (stream order)
-      else if (x16) O = other;
-      rc = run_conv<T>(c2, bufB, resid, O, B, Ho, Wo, true, st, &h2, &w2, BLK, x16);
+  const std::vector<BlockDesc>& blocks = net->desc->blocks;
+  for (size_t bi = 0; bi < blocks.size(); ++bi) {
+    const BlockDesc& b = blocks[bi];
+    const bool has_ds = b.ds >= 0;
+    const ConvLayer& c1 = net->convs[b.conv[0]];
+    const ConvLayer& c2 = net->convs[b.conv[1]];
+    void* other = X == bufA ? bufC : bufA;
+    int Ho, Wo, h2, w2;
+    int rc;
+    const void* resid = X;
+    if (has_ds) {
+      // conv1 (3x3/2 + BN + ReLU) and the 1x1/2 downsample (+ BN) of the block in ONE launch
+      Ho = (H + 2 - 3) / 2 + 1; Wo = (W + 2 - 3) / 2 + 1;
+      rc = launch_conv3x3<T, 2>(c1, X, nullptr, bufB, B, H, W, true, st, Ho, Wo, &net->convs[b.ds], other, BLK, 0, 0, x16, false);
       if (rc) return rc;
-      if ((rc = tap_after<T>(tap, c2.name, O, c2.cout, Ho, Wo, x16 ? 16 : BLK ? 32 : c2.cout, st))) return rc;
-      X = O;
-      H = Ho; W = Wo;
-      ci += has_ds ? 3 : 2;
+      if ((rc = tap_after<T>(tap, net->convs[b.ds].name, other, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
+      resid = other;
+    } else {
+      DH_REQUIRE(!x16, "resnet18 forward: only a downsample block reads 16-channel planes");
+      rc = run_conv<T>(c1, X, nullptr, bufB, B, H, W, true, st, &Ho, &Wo, BLK);
+      if (rc) return rc;
     }
+    if ((rc = tap_after<T>(tap, c1.name, bufB, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
+    // the block that follows starts with a stride-2 conv on the wide kernel: this block's output goes out in 16-channel planes
+    x16 = false;
+    if (bi + 1 < blocks.size() && blocks[bi + 1].stride == 2) {
+      const BlockDesc& nb = blocks[bi + 1];
+      x16 = BLK && s2_wide_eligible(net->convs[nb.conv[0]], net->convs[nb.ds], esz, (Wo + 2 - 3) / 2 + 1);
+    }
+    // conv2 + residual.  Same layout: in place over the residual (every lane reads the elements it then writes).  16-channel planes out,
+    // 32-channel planes in: the two layouts put different pixels at the same address -- the output goes to the third buffer
+    void* O = X;
+    if (has_ds) O = X;                 // the block input is dead once conv1 and the downsample have run (stream order)
+    else if (x16) O = other;
+    rc = run_conv<T>(c2, bufB, resid, O, B, Ho, Wo, true, st, &h2, &w2, BLK, x16);
+    if (rc) return rc;
+    if ((rc = tap_after<T>(tap, c2.name, O, c2.cout, Ho, Wo, x16 ? 16 : BLK ? 32 : c2.cout, st))) return rc;
+    X = O;
+    H = Ho; W = Wo;
   }
   if (feat)   // dh_resnet18_features_tiles: the same head, the pooled vector stored as well
     hipLaunchKernelGGL((avgpool_fc_kernel<T, true>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
-                       512, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
+                       net->desc->feat, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
   else
     hipLaunchKernelGGL((avgpool_fc_kernel<T, false>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
-                       512, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
+                       net->desc->feat, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
 
-template <typename V>
-int upload(const std::vector<V>& v, void** dev) {
-  if (*dev) { DH_HIP(hipFree(*dev)); *dev = nullptr; }
-  DH_HIP(hipMalloc(dev, v.size() * sizeof(V)));
-  DH_HIP(hipMemcpy(*dev, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+// the forward in the handle's dtype
+int r18_forward(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w, const int32_t* yx, int64_t n,
+                int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
+  return net->dtype == DH_DTYPE_F32 ? forward_impl<float>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat)
+                                    : forward_impl<__bf16>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat);
+}
+
+int r18_check_forward(const InferNet* net, int64_t n, int32_t P, const void* logits, const char*) {
+  DH_REQUIRE(net && (logits || n == 0), "resnet18 forward: null argument");
+  DH_REQUIRE(net->finalized, "resnet18 forward: call dh_resnet18_finalize after setting parameters");
+  DH_REQUIRE(n >= 0 && n <= 4096, "resnet18 forward: batch %lld out of range [0, 4096]", (long long)n);
+  DH_REQUIRE(P >= 32 && P <= 1024, "resnet18 forward: patch %d out of range [32, 1024]", P);
   return DH_OK;
 }
+
+const InferEngine R18_ENGINE = {"resnet18", r18_check_forward, 1, false};
 
 }  // namespace
 
@@ -1447,9 +1357,8 @@ extern "C" int dh_resnet18_create(dh_resnet18** out, int32_t n_classes, int32_t 
   DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "resnet18 create: bad dtype %d", dtype);
   if (int erc = dh::env_check()) return erc;   // a mistyped DH_* switch stops here, named by dh_last_error()
   auto* net = new dh_resnet18();
-  net->n_classes = n_classes;
+  infer_init(net, "resnet18", n_classes);
   net->dtype = dtype;
-  build_topology(net);
   *out = net;
   return DH_OK;
 }
@@ -1458,124 +1367,65 @@ extern "C" int dh_resnet18_train_end(dh_resnet18* net);
 extern "C" void dh_resnet18_destroy(dh_resnet18* net) {
   if (!net) return;
   if (net->train) (void)dh_resnet18_train_end(net);
-  for (auto& c : net->convs) {
-    if (c.w_dev) (void)hipFree(c.w_dev);
-    if (c.w2_dev) (void)hipFree(c.w2_dev);
-    if (c.scale_dev) (void)hipFree(c.scale_dev);
-    if (c.shift_dev) (void)hipFree(c.shift_dev);
-  }
-  if (net->fc_w_dev) (void)hipFree(net->fc_w_dev);
-  if (net->fc_b_dev) (void)hipFree(net->fc_b_dev);
-  if (net->ws) (void)hipFree(net->ws);
+  infer_free(net);
   delete net;
 }
 
 extern "C" int dh_resnet18_set_param(dh_resnet18* net, const char* name, const float* data,
                                      int64_t n_elem) {
-  DH_REQUIRE(net && name && data, "resnet18 set_param: null argument");
-  const int64_t want = expected_elems(net, name);
-  DH_REQUIRE(want >= 0, "resnet18 set_param: unknown parameter '%s'", name);
-  DH_REQUIRE(want == n_elem, "resnet18 set_param: '%s' has %lld elements, expected %lld", name,
-             (long long)n_elem, (long long)want);
-  net->params[name].assign(data, data + n_elem);
-  net->finalized = false;
-  return DH_OK;
+  return infer_set_param(R18_ENGINE, net, name, data, n_elem);
 }
 
 extern "C" int dh_resnet18_finalize(dh_resnet18* net, void* stream) {
-  DH_REQUIRE(net != nullptr, "resnet18 finalize: null handle");
   (void)stream;
-  auto get = [&](const std::string& k) -> const std::vector<float>* {
-    auto it = net->params.find(k);
-    return it == net->params.end() ? nullptr : &it->second;
-  };
+  int rc = infer_finalize_begin(R18_ENGINE, net);   // every parameter is checked before any upload
+  if (rc) return rc;
   const int esz = net->esz();
+  std::vector<double> scale, shift;
   for (size_t i = 0; i < net->convs.size(); ++i) {
     ConvLayer& c = net->convs[i];
-    const auto* w = get(c.name + ".weight");
-    const auto *g = get(c.bn + ".weight"), *b = get(c.bn + ".bias"), *m = get(c.bn + ".running_mean"),
-               *v = get(c.bn + ".running_var");
-    DH_REQUIRE(w && g && b && m && v, "resnet18 finalize: parameters of '%s' / '%s' are not all set",
-               c.name.c_str(), c.bn.c_str());
+    const std::vector<float>& w = *infer_param(net, c.name + ".weight");
     std::vector<uint8_t> packed;
-    if (i == 0 && esz == 2) pack_stem_pool_weights(w->data(), packed);   // bf16 inference runs the fused stem only
-    else if (i == 0) pack_stem_weights(w->data(), esz, packed);
-    else pack_conv_weights(w->data(), c.cout, c.cin, c.ks, esz, packed);
-    int rc = upload(packed, &c.w_dev);
-    if (rc) return rc;
+    if (i == 0 && esz == 2) pack_stem_pool_weights(w.data(), packed);   // bf16 inference runs the fused stem only
+    else if (i == 0) pack_stem_weights(w.data(), esz, packed);
+    else pack_conv_weights(w.data(), c.cout, c.cin, c.ks, esz, packed);
+    if ((rc = upload(packed, &c.w_dev))) return rc;
     // the wide stride-2 variant's packing: a 3x3 / stride-2 conv of a downsample block and that block's 1x1 / stride-2 conv (bf16 inference)
     const bool wide3 = esz == 2 && c.ks == 3 && c.stride == 2 && c.cout % 128 == 0 && c.cin % 16 == 0;
     const bool wide1 = esz == 2 && c.ks == 1 && c.stride == 2 && c.cout % 128 == 0 && c.cin % 16 == 0;
     if (wide3 || wide1) {
       std::vector<uint8_t> packed2;
-      pack_conv_weights_wide(w->data(), c.cout, c.cin, c.ks, packed2);
+      pack_conv_weights_wide(w.data(), c.cout, c.cin, c.ks, packed2);
       if ((rc = upload(packed2, &c.w2_dev))) return rc;
     }
-    // eval-mode BN (eps = 1e-5, torch default): y = x*scale + shift
-    std::vector<float> sc(c.cout), sh(c.cout);
-    for (int k = 0; k < c.cout; ++k) {
-      const double s = (double)(*g)[k] / sqrt((double)(*v)[k] + 1e-5);
-      sc[k] = (float)s;
-      sh[k] = (float)((double)(*b)[k] - (double)(*m)[k] * s);
-    }
-    rc = upload(sc, reinterpret_cast<void**>(&c.scale_dev));
-    if (rc) return rc;
-    rc = upload(sh, reinterpret_cast<void**>(&c.shift_dev));
-    if (rc) return rc;
+    infer_bn_affine(net, c, scale, shift);
+    const std::vector<float> sc(scale.begin(), scale.end()), sh(shift.begin(), shift.end());
+    if ((rc = upload(sc, reinterpret_cast<void**>(&c.scale_dev))) || (rc = upload(sh, reinterpret_cast<void**>(&c.shift_dev)))) return rc;
   }
-  const auto *fw = get("fc.weight"), *fb = get("fc.bias");
-  DH_REQUIRE(fw && fb, "resnet18 finalize: fc.weight / fc.bias are not set");
-  int rc = upload(*fw, reinterpret_cast<void**>(&net->fc_w_dev));
-  if (rc) return rc;
-  rc = upload(*fb, reinterpret_cast<void**>(&net->fc_b_dev));
-  if (rc) return rc;
-  net->finalized = true;
-  return DH_OK;
-}
-
-static int check_forward_args(dh_resnet18* net, int64_t n, int32_t P, const void* logits) {
-  DH_REQUIRE(net && (logits || n == 0), "resnet18 forward: null argument");
-  DH_REQUIRE(net->finalized, "resnet18 forward: call dh_resnet18_finalize after setting parameters");
-  DH_REQUIRE(n >= 0 && n <= 4096, "resnet18 forward: batch %lld out of range [0, 4096]", (long long)n);
-  DH_REQUIRE(P >= 32 && P <= 1024, "resnet18 forward: patch %d out of range [32, 1024]", P);
-  return DH_OK;
+  return infer_finalize_end(net);
 }
 
 extern "C" int dh_resnet18_forward(dh_resnet18* net, const float* x, int64_t n, int32_t P,
                                    float* logits, void* stream) {
-  int rc = check_forward_args(net, n, P, logits);
+  int rc = r18_check_forward(net, n, P, logits, nullptr);
   if (rc) return rc;
   if (n == 0) return DH_OK;
   DH_REQUIRE(x != nullptr, "resnet18 forward: null input");
-  hipStream_t st = dh::as_stream(stream);
-  return net->dtype == DH_DTYPE_F32
-             ? forward_impl<float>(net, x, nullptr, 0, 0, nullptr, n, P, logits, st)
-             : forward_impl<__bf16>(net, x, nullptr, 0, 0, nullptr, n, P, logits, st);
-}
-
-// The fused gather + forward behind both tiles entries; `what` names the entry in messages, `feat` (features_tiles: the pooled
-// 512-vector of every tile, the tap one step before the logits) is stored as well when given; `out` is the entry's mandatory output.
-static int forward_tiles_impl(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
-                              int32_t P, float* feat, float* logits, const float* out, void* stream, const char* what) {
-  int rc = check_forward_args(net, n, P, out);
-  if (rc) return rc;
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(slide && yx, "%s: null slide or origins", what);
-  DH_REQUIRE(h >= P && w >= P, "%s: patch %d does not fit %lldx%lld", what, P, (long long)h, (long long)w);
-  hipStream_t st = dh::as_stream(stream);
-  return net->dtype == DH_DTYPE_F32
-             ? forward_impl<float>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat)
-             : forward_impl<__bf16>(net, nullptr, slide, h, w, yx, n, P, logits, st, nullptr, feat);
+  return r18_forward(net, x, nullptr, 0, 0, nullptr, n, P, logits, dh::as_stream(stream));
 }
 
 extern "C" int dh_resnet18_forward_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
                                          const int32_t* yx, int64_t n, int32_t P, float* logits, void* stream) {
-  return forward_tiles_impl(net, slide, h, w, yx, n, P, nullptr, logits, logits, stream, "resnet18 forward_tiles");
+  return infer_tiles(R18_ENGINE, net, slide, h, w, yx, n, P, nullptr, logits, "resnet18 forward_tiles", [&](Tap* tap) {
+    return r18_forward(net, nullptr, slide, h, w, yx, n, P, logits, dh::as_stream(stream), tap);
+  });
 }
 
 extern "C" int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w,
                                           const int32_t* yx, int64_t n, int32_t P, float* feat, float* logits, void* stream) {
-  return forward_tiles_impl(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet18 features_tiles");
+  return infer_tiles(R18_ENGINE, net, slide, h, w, yx, n, P, feat, feat, "resnet18 features_tiles", [&](Tap* tap) {
+    return r18_forward(net, nullptr, slide, h, w, yx, n, P, logits, dh::as_stream(stream), tap, feat);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1603,7 +1453,7 @@ extern "C" int dh_debug_conv_bn_act(const void* in_dev, const float* w_host, con
   DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "debug conv: bad dtype");
   const int esz = dtype == DH_DTYPE_F32 ? 4 : 2;
   DH_REQUIRE(cout % 64 == 0 && cin % (CHUNK_BYTES / esz) == 0, "debug conv: channel counts");
-  ConvLayer L{"debug", "debug", cin, cout, ks, stride};
+  ConvLayer L{{"debug", "debug", cin, cout, ks, stride}};
   std::vector<uint8_t> packed;
   pack_conv_weights(w_host, cout, cin, ks, esz, packed);
   int rc = upload(packed, &L.w_dev);
@@ -1669,63 +1519,18 @@ extern "C" int dh_debug_stem_pool_bf16(dh_resnet18* net, const uint8_t* slide_de
   return rc;
 }
 
-namespace {
-// the stored activations a tap may name: every conv of the topology, and "maxpool" (the pooled stem output)
-template <typename Net>
-bool tap_name_known(const Net* net, const char* name) {
-  if (!strcmp(name, "maxpool")) return true;
-  for (const auto& c : net->convs)
-    if (c.name == name) return true;
-  return false;
-}
-
-// a conv's operands as the engine holds them: the packed weight read back from the device and unpacked, scale and shift (or 1 and the
-// folded bias) read back; synchronous
-int read_operands(const ConvLayer& c, int esz, bool fused_stem, float* w_host, int64_t w_elems, float* scale_host, float* shift_host,
-                  int64_t c_elems) {
-  DH_REQUIRE(w_host && scale_host && shift_host, "operands: null argument");
-  DH_REQUIRE(w_elems == (int64_t)c.cout * c.cin * c.ks * c.ks && c_elems == c.cout, "operands %s: buffers of %lld / %lld elements, "
-             "expected %lld / %d", c.name.c_str(), (long long)w_elems, (long long)c_elems, (long long)c.cout * c.cin * c.ks * c.ks, c.cout);
-  size_t bytes;
-  if (c.ks == 7) bytes = fused_stem ? (size_t)SP_WBYTES : (size_t)7 * 11 * 2 * 256;
-  else bytes = (size_t)(c.cout / 64) * (c.cin / (CHUNK_BYTES / esz)) * c.ks * c.ks * SLAB_TAP;
-  std::vector<uint8_t> packed(bytes);
-  DH_HIP(hipMemcpy(packed.data(), c.w_dev, bytes, hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < w_elems; ++i) w_host[i] = NAN;   // an element no slot carries stays NaN
-  if (c.ks == 7 && fused_stem) unpack_stem_pool_weights(packed, w_host);
-  else if (c.ks == 7) unpack_stem_weights_f32(packed, w_host);
-  else unpack_conv_weights(packed, c.cout, c.cin, c.ks, esz, w_host);
-  DH_HIP(hipMemcpy(scale_host, c.scale_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
-  DH_HIP(hipMemcpy(shift_host, c.shift_dev, (size_t)c.cout * 4, hipMemcpyDeviceToHost));
-  return DH_OK;
-}
-}  // namespace
-
 extern "C" int dh_debug_resnet18_forward_tap(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, int64_t n,
                                              int32_t P, const char* conv_name, const int32_t* sel_dev, int32_t k, float* out_dev,
                                              int64_t out_elems, float* logits_dev, void* stream) {
-  if (int rc = check_forward_args(net, n, P, logits_dev)) return rc;
-  DH_REQUIRE(n > 0 && slide && yx_dev && conv_name, "resnet18 forward tap: null argument or empty launch");
-  DH_REQUIRE(h >= P && w >= P, "resnet18 forward tap: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
-  DH_REQUIRE(tap_name_known(net, conv_name), "resnet18 forward tap: unknown conv '%s'", conv_name);
   hipStream_t st = dh::as_stream(stream);
-  if (int rc = tap_check(sel_dev, k, n, out_dev, logits_dev, st)) return rc;
-  Tap tap;
-  tap.name = conv_name; tap.sel = sel_dev; tap.k = k; tap.out = out_dev; tap.out_elems = out_elems;
-  const int rc = net->dtype == DH_DTYPE_F32 ? forward_impl<float>(net, nullptr, slide, h, w, yx_dev, n, P, logits_dev, st, &tap)
-                                            : forward_impl<__bf16>(net, nullptr, slide, h, w, yx_dev, n, P, logits_dev, st, &tap);
-  if (rc) return rc;
-  DH_REQUIRE(tap.hit, "resnet18 forward tap: '%s' is not stored by this engine", conv_name);
-  return DH_OK;
+  return infer_tap(R18_ENGINE, net, slide, h, w, yx_dev, n, P, conv_name, sel_dev, k, out_dev, out_elems, logits_dev, st, [&](Tap* tap) {
+    return r18_forward(net, nullptr, slide, h, w, yx_dev, n, P, logits_dev, st, tap);
+  });
 }
 
 extern "C" int dh_debug_resnet18_operands(dh_resnet18* net, const char* conv_name, float* w_host, int64_t w_elems, float* scale_host,
                                           float* shift_host, int64_t c_elems) {
-  DH_REQUIRE(net && net->finalized && conv_name, "resnet18 operands: needs a finalized network");
-  for (const auto& c : net->convs)
-    if (c.name == conv_name) return read_operands(c, net->esz(), net->esz() == 2, w_host, w_elems, scale_host, shift_host, c_elems);
-  dh::set_error("resnet18 operands: unknown conv '%s'", conv_name);
-  return DH_EINVAL;
+  return infer_operands(R18_ENGINE, net, net ? net->esz() : 0, conv_name, w_host, w_elems, scale_host, shift_host, c_elems);
 }
 
 // ---------------------------------------------------------------------------

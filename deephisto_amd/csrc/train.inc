@@ -1247,7 +1247,7 @@ int tr_conv(UnitAffine u, int cin, int cout, int ks, int stride, const float* wp
     const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
     return gemm1x1_f32(in, wp, res, out, (int64_t)B * Ho * Wo, cout, cin, stride, Ho, Wo, Hi, Wi, st);
   }
-  ConvLayer L{"train", "train", cin, cout, ks, stride};
+  ConvLayer L{{"train", "train", cin, cout, ks, stride}};
   L.w_dev = const_cast<float*>(wp);
   L.scale_dev = const_cast<float*>(u.ones);
   L.shift_dev = const_cast<float*>(u.zeros);
@@ -1258,7 +1258,7 @@ int tr_conv(UnitAffine u, int cin, int cout, int ks, int stride, const float* wp
 // dX = data gradient of a 3x3 / stride-2 conv (cz channels of dZ -> cx channels of dX) from the packed dgrad operator `wp`
 int tr_dgrad_s2(UnitAffine u, int cz, int cx, const float* wp, const float* dz, const float* res, float* dx, int B, int Ho, int Wo,
                 int Hi, int Wi, hipStream_t st) {
-  ConvLayer L{"train", "train", cz, cx, 3, 1};
+  ConvLayer L{{"train", "train", cz, cx, 3, 1}};
   L.w_dev = const_cast<float*>(wp);
   L.scale_dev = const_cast<float*>(u.ones);
   L.shift_dev = const_cast<float*>(u.zeros);
@@ -1403,23 +1403,17 @@ int tr_wgrad(float* wgrad_slabs, float* dw_out, const ConvLayer& c, const TrainC
   return DH_OK;
 }
 
-// first train_begin: the block table from the handle's convolution list (conv1, conv2 and, where the next entry is a 1x1, its downsample),
-// the arena layout in forward order, and the completion items of the backward pass: fc, the blocks last to first, the stem -- each
+// first train_begin: the block table from the network description (net_desc.inc), the arena layout in forward order, and the completion items of the backward pass: fc, the blocks last to first, the stem -- each
 // runs from its first tensor down to where the previous item started
 void tr_layout(dh_resnet18* net) {
   dh_train* t = net->train;
-  const int nconv = (int)net->convs.size();
-  for (int i = 1; i + 1 < nconv;) {
-    const int ds = i + 2 < nconv && net->convs[i + 2].ks == 1 ? i + 2 : -1;
-    t->blocks.push_back({i, i + 1, ds, 0, 0});
-    i += ds < 0 ? 2 : 3;
-  }
+  for (const BlockDesc& b : net->desc->blocks) t->blocks.push_back({b.conv[0], b.conv[1], b.ds, 0, 0});
   for (const auto& c : net->convs) {
     store_add(*t, c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
     store_add(*t, c.bn + ".weight", c.cout); store_add(*t, c.bn + ".bias", c.cout);
     store_radd(*t, c.bn + ".running_mean", c.cout); store_radd(*t, c.bn + ".running_var", c.cout);
   }
-  store_add(*t, "fc.weight", (int64_t)net->n_classes * 512); store_add(*t, "fc.bias", net->n_classes);
+  store_add(*t, "fc.weight", (int64_t)net->n_classes * net->desc->feat); store_add(*t, "fc.bias", net->n_classes);
   int64_t end = t->n_params;
   auto item_from = [&](int64_t start) { t->items.push_back({start, end - start}); end = start; };
   item_from(t->slot["fc.weight"].first);
@@ -1829,7 +1823,7 @@ extern "C" int dh_debug_wgrad_f32(const float* dz_dev, const float* x_dev, float
   float* slabs;
   int rc = sc.get(&slabs, (int64_t)WGRAD3_WGS * 9 * 64 * 64);
   if (rc) return rc;
-  ConvLayer c{"dbg", "dbg", cin, cout, ks, stride};
+  ConvLayer c{{"dbg", "dbg", cin, cout, ks, stride}};
   TrainConv tc;
   tc.Hi = Hi; tc.Wi = Wi; tc.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; tc.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
   if ((rc = tr_wgrad(slabs, dw_dev, c, tc, x_dev, dz_dev, B, st, mode == 1))) return rc;

@@ -21,9 +21,7 @@
 // stream's hand-off are train_core.inc's, shared with the float32 engine.
 #include <type_traits>
 
-struct T2Conv {
-  std::string name, bn;
-  int cin = 0, cout = 0, ks = 0, stride = 1;
+struct T2Conv : ConvDesc {   // the description (net_desc.inc) plus this engine's buffers
   int Hi = 0, Wi = 0, Ho = 0, Wo = 0;
   void* wp_f = nullptr;   // bf16 forward operand: 3x3 fragment order | 1x1 W[cout][cin] | 7x7 stem layout
   void* wp_d = nullptr;   // bf16 dgrad operand: 3x3 flipped + transposed fragment order | 1x1 Wt[cin][cout]
@@ -33,13 +31,11 @@ struct T2Conv {
   bf16_t* dZ = nullptr;   // side-stream weight gradients only: this conv's own dZ buffer (read by the side stream long after it was written)
   BnBufs bnb{};
 };
-struct T2Block { int conv[3] = {-1, -1, -1}; int nconv = 0; int ds = -1; };
 
 struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order: every completion item is one convolution (or fc)
-  std::string arch;
-  int n_classes = 0, feat = 0;
+  int n_classes = 0, feat = 0;   // feat, blocks and the describing part of convs: copies of the architecture's NetDesc (net_desc.inc)
   std::vector<T2Conv> convs;     // index 0 = stem
-  std::vector<T2Block> blocks;
+  std::vector<BlockDesc> blocks;
   float *ones = nullptr, *zeros = nullptr, *partial = nullptr;
   int B = 0, P = 0;
   bf16_t* X1 = nullptr;          // pooled stem output = input of the first block
@@ -83,48 +79,6 @@ int g_abl_consumer_ks = 0;   // kernel size of the convolution that consumes the
 #define DH_ABL_SKIP_STATS(c) false
 #endif
 
-void t2_topology(dh_train2* t) {
-  t->convs.clear(); t->blocks.clear();
-  auto add = [&](const std::string& n, const std::string& bn, int cin, int cout, int ks, int stride) {
-    T2Conv c; c.name = n; c.bn = bn; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
-    t->convs.push_back(c);
-    return (int)t->convs.size() - 1;
-  };
-  add("conv1", "bn1", 3, 64, 7, 2);
-  if (t->arch == "resnet18") {
-    const int ch[4] = {64, 128, 256, 512};
-    int cin = 64;
-    for (int s = 0; s < 4; ++s)
-      for (int blk = 0; blk < 2; ++blk) {
-        const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(blk);
-        const int stride = (blk == 0 && s > 0) ? 2 : 1, bcin = blk == 0 ? cin : ch[s];
-        T2Block b; b.nconv = 2;
-        b.conv[0] = add(pre + ".conv1", pre + ".bn1", bcin, ch[s], 3, stride);
-        b.conv[1] = add(pre + ".conv2", pre + ".bn2", ch[s], ch[s], 3, 1);
-        if (stride != 1 || bcin != ch[s]) b.ds = add(pre + ".downsample.0", pre + ".downsample.1", bcin, ch[s], 1, stride);
-        t->blocks.push_back(b);
-        if (blk == 1) cin = ch[s];
-      }
-    t->feat = 512;
-  } else {   // resnet50: Bottleneck x [3, 4, 6, 3], expansion 4, the stage stride on the 3x3 conv (torchvision v1.5)
-    const int width[4] = {64, 128, 256, 512}, nblk[4] = {3, 4, 6, 3};
-    int cin = 64;
-    for (int s = 0; s < 4; ++s)
-      for (int blk = 0; blk < nblk[s]; ++blk) {
-        const std::string pre = "layer" + std::to_string(s + 1) + "." + std::to_string(blk);
-        const int stride = (blk == 0 && s > 0) ? 2 : 1, w = width[s], cout = 4 * w;
-        T2Block b; b.nconv = 3;
-        b.conv[0] = add(pre + ".conv1", pre + ".bn1", cin, w, 1, 1);
-        b.conv[1] = add(pre + ".conv2", pre + ".bn2", w, w, 3, stride);
-        b.conv[2] = add(pre + ".conv3", pre + ".bn3", w, cout, 1, 1);
-        if (stride != 1 || cin != cout) b.ds = add(pre + ".downsample.0", pre + ".downsample.1", cin, cout, 1, stride);
-        t->blocks.push_back(b);
-        cin = cout;
-      }
-    t->feat = 2048;
-  }
-}
-
 // arenas in backward-completion order: fc, then blocks last to first (inside a block: last conv ... first conv, downsample), stem;
 // each of them is one completion item
 void t2_layout(dh_train2* t) {
@@ -140,7 +94,7 @@ void t2_layout(dh_train2* t) {
   store_add(*t, "fc.weight", (int64_t)t->n_classes * t->feat); store_add(*t, "fc.bias", t->n_classes);
   item_done();
   for (int b = (int)t->blocks.size() - 1; b >= 0; --b) {
-    const T2Block& blk = t->blocks[b];
+    const BlockDesc& blk = t->blocks[b];
     for (int i = blk.nconv - 1; i >= 0; --i) add_conv(blk.conv[i]);
     if (blk.ds >= 0) add_conv(blk.ds);
   }
@@ -244,7 +198,7 @@ int t2_red_blocks(int64_t rows, int C) {
 int t2_conv3(dh_train2* t, int cin, int cout, int stride, const void* wp, const bf16_t* in, const bf16_t* res, bf16_t* out, int B, int Hi,
              int Wi, hipStream_t st) {
   if (g_t2_abl & 256) return DH_OK;
-  ConvLayer L{"t2", "t2", cin, cout, 3, stride};
+  ConvLayer L{{"t2", "t2", cin, cout, 3, stride}};
   L.w_dev = const_cast<void*>(wp); L.scale_dev = t->ones; L.shift_dev = t->zeros;
   const int Ho = (Hi + 2 - 3) / stride + 1, Wo = (Wi + 2 - 3) / stride + 1;
   DH_REQUIRE((int64_t)B * Hi * Wi * cin * 2 < ((int64_t)1 << 32), "conv3x3: input larger than 4 GiB, reduce the batch");
@@ -327,7 +281,7 @@ int t2_conv_dgrad(dh_train2* t, const T2Conv& c, const bf16_t* dz, const bf16_t*
     // the stride-1 conv over a zero-upsampled copy, no 4x-sized tensor written and read).  As four launches this was SLOWER than the
     // upsampled path at bf16 rate (ResNet-18 3.04 -> 3.11 ms per step: each launch fills a fraction of the chip); merged it wins
     // (2.665 -> 2.640 ms, ResNet-50 7.45 -> 7.43; the upsampled path left the engine in round 5).
-    ConvLayer L{"t2", "t2", c.cout, c.cin, 3, 1};
+    ConvLayer L{{"t2", "t2", c.cout, c.cin, 3, 1}};
     L.w_dev = c.wp_d; L.scale_dev = t->ones; L.shift_dev = t->zeros;
     return launch_dgrad_s2<__bf16>(L, dz, res, dx, B, c.Ho, c.Wo, c.Hi, c.Wi, st);
   }
@@ -630,7 +584,7 @@ int t2_shape(dh_train2* t, int B, int P) {
   };
   if ((rc = setup(0, P))) return done(rc);
   int H = H2;
-  for (const T2Block& b : t->blocks) {
+  for (const BlockDesc& b : t->blocks) {
     int h = H;
     for (int i = 0; i < b.nconv; ++i) {
       if ((rc = setup(b.conv[i], h, i + 1 == b.nconv))) return done(rc);
@@ -660,12 +614,13 @@ int t2_shape(dh_train2* t, int B, int P) {
 
 extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_classes) {
   DH_REQUIRE(out && arch, "train2 create: null argument");
-  DH_REQUIRE(std::string(arch) == "resnet18" || std::string(arch) == "resnet50", "train2 create: unknown architecture '%s'", arch);
+  const NetDesc* desc = net_desc(arch);
+  DH_REQUIRE(desc != nullptr, "train2 create: unknown architecture '%s'", arch);
   DH_REQUIRE(n_classes > 0 && n_classes <= 1024, "train2 create: n_classes=%d", n_classes);
   if (int erc = dh::env_check()) return erc;   // a mistyped DH_* switch stops here, named by dh_last_error()
   auto* t = new dh_train2();
-  t->arch = arch; t->n_classes = n_classes;
-  t2_topology(t);
+  t->n_classes = n_classes; t->feat = desc->feat; t->blocks = desc->blocks;
+  for (const ConvDesc& d : desc->convs) t->convs.push_back(T2Conv{d});
   t2_layout(t);
   int rc;
   auto fail = [&](int r) { store_free_all(*t); delete t; return r; };
@@ -775,7 +730,7 @@ extern "C" int dh_train2_forward(dh_train2* t, const float* x, int64_t n, int32_
     if ((rc = t2_bn_fwd(t, c, nullptr, true, tr, st, false, t->X1, t->pool_idx))) return rc;   // + ReLU + maxpool in the same pass
   }
   const bf16_t* X = t->X1;
-  for (const T2Block& b : t->blocks) {
+  for (const BlockDesc& b : t->blocks) {
     const bf16_t* in = X;
     for (int i = 0; i < b.nconv; ++i) {
       T2Conv& c = t->convs[b.conv[i]];
@@ -877,12 +832,12 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   // BN backward then reads neither the block output nor writes the masked copy: the incoming tensor IS the identity gradient.
   auto premasked = [&](int bi) {
     if (bi + 1 >= (int)t->blocks.size()) return false;
-    const T2Block& nx = t->blocks[bi + 1];
+    const BlockDesc& nx = t->blocks[bi + 1];
     const T2Conv& c0 = t->convs[nx.conv[0]];
     return nx.ds < 0 && c0.ks == 1 && c0.stride == 1;
   };
   for (int bi = (int)t->blocks.size() - 1; bi >= 0; --bi) {
-    const T2Block& b = t->blocks[bi];
+    const BlockDesc& b = t->blocks[bi];
     const bf16_t* Xin = bi == 0 ? t->X1 : t->convs[t->blocks[bi - 1].conv[t->blocks[bi - 1].nconv - 1]].Y;
     const bf16_t* grad = dOut;
     const bool pm = premasked(bi);

@@ -265,7 +265,8 @@ void dh_resnet18_destroy(dh_resnet18* net);
 int dh_resnet18_set_param(dh_resnet18* net, const char* name, const float* data_host,
                           int64_t n_elem);
 /* Call after all parameters are set (or changed): folds BN running stats into
- * per-channel scale/shift and packs conv weights into MFMA fragment order. */
+ * per-channel scale/shift and packs conv weights into MFMA fragment order.
+ * Checks all parameters before it uploads any. */
 int dh_resnet18_finalize(dh_resnet18* net, void* stream);
 /* x_dev: float32[n][3][P][P] NCHW in [0,1] (what batch_predictor feeds the model);
  * logits_dev: float32[n][n_classes].  P must be a multiple of 32. */
