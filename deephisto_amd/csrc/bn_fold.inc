@@ -235,10 +235,25 @@ __global__ __launch_bounds__(256) void bn2_cs_reduce_kernel(const bf16_t* __rest
   __syncthreads();
   if (threadIdx.x < 2 * CS_CH) {   // the 32 row lanes of a channel, added in index order
     const int k = threadIdx.x >> 6, ch = threadIdx.x & 63;
-    float t = red[k][0][ch];
+    if (MODE == 0) {
+      // The statistics' lanes are added in DOUBLE and rounded once: the consumer forms var = E z^2 - mean^2, which multiplies the relative
+      // error of sum z^2 by 1 + (mean / std)^2.  A lane holds at most 16 rows and its float32 sum of bf16 squares is exact or nearly so;
+      // the 31 float32 additions of the lanes were not: at 512 rows a group they left sum z^2 of a channel whose mean is 8 standard
+      // deviations 1.2e-7 off, 3.7e-6 in invstd (tests/test_gpu_bn_bf16_parity.py, 16384 x 128).  The backward sums have no such
+      // amplification and keep their float32 order.  What remains is the ONE rounding of each partial row to float32 (<= 2^-25 of the
+      // row): on such a channel up to 64 * 2^-25 = 1.9e-6 of var when a map has one or two row groups (64 - 128 rows); with 32 rows the
+      // roundings average out (2.6e-7 of invstd measured at 16384 x 128).  So the 1e-6 of the tests holds for the data and shapes
+      // tested, not by construction: a structural bound needs partial rows that lose nothing (a hi / lo float pair).
+      double t = (double)red[k][0][ch];
 #pragma unroll
-    for (int q = 1; q < 32; ++q) t += red[k][q][ch];
-    partial[((int64_t)g.rg * 2 + k) * C + g.c0 + ch] = t;
+      for (int q = 1; q < 32; ++q) t += (double)red[k][q][ch];
+      partial[((int64_t)g.rg * 2 + k) * C + g.c0 + ch] = (float)t;
+    } else {
+      float t = red[k][0][ch];
+#pragma unroll
+      for (int q = 1; q < 32; ++q) t += red[k][q][ch];
+      partial[((int64_t)g.rg * 2 + k) * C + g.c0 + ch] = t;
+    }
   }
 }
 

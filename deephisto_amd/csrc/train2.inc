@@ -1127,6 +1127,69 @@ extern "C" int dh_debug_bn2_bf16(const uint16_t* z_dev, const uint16_t* res_dev,
   return dbg_finish(st, "debug bn2");
 }
 
+// dh_debug_bn2_bf16 with the engine's remaining routes through t2_bn_fwd / t2_bn_bwd selectable (tests/test_gpu_bn_bf16_parity.py):
+//   fold     : t->fold (1: small maps finalize inside the apply passes, bn_fold.inc; 0: partial sums -> finalize launch -> elementwise pass);
+//   bits     : (may be null) the ReLU pattern of y, [rows][C / 8] bytes (st8_bits), as a block's top BN leaves it;
+//   z2, gamma2, beta2 (all or none): the join of a downsample block -- the branch BN of z2 runs with apply = false (statistics and
+//              coefficients only; mean2 / invstd2 return them) and this BN applies it inside its own pass (bn2_apply_join_kernel).
+extern "C" int dh_debug_bn2_paths_bf16(const uint16_t* z_dev, const uint16_t* res_dev, const float* gamma_dev, const float* beta_dev, int32_t relu,
+                                       int32_t fold, uint16_t* y_dev, uint8_t* bits_dev, float* mean_dev, float* invstd_dev,
+                                       const uint16_t* z2_dev, const float* gamma2_dev, const float* beta2_dev, float* mean2_dev,
+                                       float* invstd2_dev, const uint16_t* dy_dev, int32_t relu_mode, uint16_t* dz_dev, uint16_t* g_out_dev,
+                                       float* dgamma_dev, float* dbeta_dev, int64_t rows, int32_t C, void* stream) {
+  DH_REQUIRE(z_dev && gamma_dev && beta_dev, "debug bn2 paths: null input (z_dev, gamma_dev or beta_dev)");
+  DH_REQUIRE(y_dev && mean_dev && invstd_dev, "debug bn2 paths: null output (y_dev, mean_dev or invstd_dev)");
+  DH_REQUIRE(rows > 0 && rows < ((int64_t)1 << 31), "debug bn2 paths: rows=%lld", (long long)rows);
+  DH_REQUIRE(C >= 64 && C <= 2048 && C % 64 == 0 && (256 % (C / 8) == 0 || (C / 8) % 256 == 0), "debug bn2 paths: C=%d (64 ... 2048, C / 8 divides 256)", C);
+  DH_REQUIRE(fold == 0 || fold == 1, "debug bn2 paths: fold=%d (0 or 1)", fold);
+  DH_REQUIRE(relu == 0 || relu == 1, "debug bn2 paths: relu=%d (0 or 1)", relu);
+  const bool join = z2_dev || gamma2_dev || beta2_dev || mean2_dev || invstd2_dev;
+  DH_REQUIRE(!join || (z2_dev && gamma2_dev && beta2_dev && mean2_dev && invstd2_dev),
+             "debug bn2 paths: the join needs z2_dev, gamma2_dev, beta2_dev, mean2_dev and invstd2_dev together");
+  DH_REQUIRE(!join || (relu == 1 && !res_dev), "debug bn2 paths: the join is a ReLU'd BN without res_dev (relu=%d)", relu);
+  DH_REQUIRE(!dy_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn2 paths: backward (dy_dev given) needs dz_dev, dgamma_dev and dbeta_dev");
+  DH_REQUIRE(!dy_dev || (relu_mode >= 0 && relu_mode <= 2), "debug bn2 paths: relu_mode=%d (0, 1 or 2)", relu_mode);
+  DH_REQUIRE(!g_out_dev || (dy_dev && relu_mode == 1), "debug bn2 paths: g_out_dev goes with dy_dev and relu_mode 1");
+  hipStream_t st = dh::as_stream(stream);
+  DbgScratch sc;
+  dh_train2 t;
+  t.B = 1;
+  t.fold = fold != 0;
+  T2Conv c, d;
+  c.name = "dbg"; c.bn = "dbgbn"; c.cout = C; c.Ho = 1; c.Wo = (int)rows; c.ks = 3;
+  d.name = "dbgds"; d.bn = "dbgds"; d.cout = C; d.Ho = 1; d.Wo = (int)rows; d.ks = 1;
+  int rc;
+  float* buf;
+  if ((rc = sc.get(&buf, (int64_t)20 * C))) return rc;
+  DH_HIP(hipMemsetAsync(buf, 0, 20 * C * sizeof(float), st));
+  // parameter / gradient / running-statistic "arenas" of the two layers: [gamma, beta, gamma2, beta2]
+  t.Pm = buf; t.G = buf + 4 * C; t.R = buf + 8 * C;
+  t.slot["dbgbn.weight"] = {0, C}; t.slot["dbgbn.bias"] = {C, C};
+  t.slot["dbgds.weight"] = {2 * C, C}; t.slot["dbgds.bias"] = {3 * C, C};
+  t.rslot["dbgbn.running_mean"] = {0, C}; t.rslot["dbgbn.running_var"] = {C, C};
+  t.rslot["dbgds.running_mean"] = {2 * C, C}; t.rslot["dbgds.running_var"] = {3 * C, C};
+  DH_HIP(hipMemcpyAsync(t.Pm, gamma_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  DH_HIP(hipMemcpyAsync(t.Pm + C, beta_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  c.bnb.mean = mean_dev; c.bnb.invstd = invstd_dev; c.bnb.scale = buf + 12 * C; c.bnb.shift = buf + 13 * C;
+  c.bnb.k0 = buf + 14 * C; c.bnb.k1 = buf + 15 * C; c.bnb.k2 = buf + 16 * C;
+  if ((rc = sc.get(&t.partial, T2_PARTIAL_FLOATS))) return rc;
+  c.Z = const_cast<bf16_t*>(z_dev); c.Y = y_dev;
+  if (join) {
+    DH_HIP(hipMemcpyAsync(t.Pm + 2 * C, gamma2_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DH_HIP(hipMemcpyAsync(t.Pm + 3 * C, beta2_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    d.bnb.mean = mean2_dev; d.bnb.invstd = invstd2_dev; d.bnb.scale = buf + 17 * C; d.bnb.shift = buf + 18 * C;
+    d.Z = const_cast<bf16_t*>(z2_dev);
+    if ((rc = t2_bn_fwd(&t, d, nullptr, false, true, st, false, nullptr, nullptr, false))) return rc;
+  }
+  if ((rc = t2_bn_fwd(&t, c, res_dev, relu != 0, true, st, false, nullptr, nullptr, true, join ? &d : nullptr, 0, bits_dev))) return rc;
+  if (dy_dev) {
+    if ((rc = t2_bn_bwd(&t, c, dy_dev, relu_mode == 1 ? y_dev : nullptr, relu_mode, dz_dev, g_out_dev, st))) return rc;
+    DH_HIP(hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DH_HIP(hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  return dbg_finish(st, "debug bn2 paths");
+}
+
 // The stem's fused tail on caller data, through the engine's launch code (t2_bn_fwd with a pooled target, t2_bn_pool_bwd):
 //   forward  : pooled [B][Hp][Wp][C] = maxpool3x3/2(relu(bn(z))) with batch statistics, first-maximum positions (uint8), mean / invstd;
 //   backward : (dpool given) dz [B][Hi][Wi][C], dgamma, dbeta.
@@ -1200,6 +1263,22 @@ extern "C" int dh_debug_maxpool2_bf16(const uint16_t* x_dev, uint16_t* y_dev, co
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((int64_t)B * Hi * Wi * C / 8)), dim3(256), 0, st, idx, dy_dev, dx_dev, B, Hi, Wi, C, Ho, Wo);
   DH_LAUNCH_CHECK();
   return dbg_finish(st, "debug maxpool2");
+}
+// ... the same pair with the recorded first-maximum positions returned: idx_dev [B][Ho][Wo][C] bytes, dyy * 3 + dxx of the 3x3 window
+extern "C" int dh_debug_maxpool2_idx_bf16(const uint16_t* x_dev, uint16_t* y_dev, uint8_t* idx_dev, const uint16_t* dy_dev, uint16_t* dx_dev,
+                                          int32_t B, int32_t Hi, int32_t Wi, int32_t C, void* stream) {
+  DH_REQUIRE(x_dev, "debug maxpool2 idx: null input (x_dev)");
+  DH_REQUIRE(y_dev && idx_dev, "debug maxpool2 idx: null output (y_dev or idx_dev)");
+  DH_REQUIRE(!dy_dev || dx_dev, "debug maxpool2 idx: backward (dy_dev given) needs dx_dev");
+  DH_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "debug maxpool2 idx: B=%d Hi=%d Wi=%d", B, Hi, Wi);
+  DH_REQUIRE(C > 0 && C % 8 == 0, "debug maxpool2 idx: C=%d (a positive multiple of 8)", C);
+  hipStream_t st = dh::as_stream(stream);
+  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
+  hipLaunchKernelGGL(maxpool2_fwd_idx_kernel, dim3(grid_for((int64_t)B * Ho * Wo * C / 8)), dim3(256), 0, st, x_dev, y_dev, idx_dev, B, Hi, Wi, C, Ho, Wo);
+  if (dy_dev)
+    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((int64_t)B * Hi * Wi * C / 8)), dim3(256), 0, st, idx_dev, dy_dev, dx_dev, B, Hi, Wi, C, Ho, Wo);
+  DH_LAUNCH_CHECK();
+  return dbg_finish(st, "debug maxpool2 idx");
 }
 extern "C" int dh_debug_upsample2_add_bf16(const uint16_t* t_dev, uint16_t* dx_dev, int32_t B, int32_t Ho, int32_t Wo, int32_t Hi, int32_t Wi,
                                            int32_t C, void* stream) {

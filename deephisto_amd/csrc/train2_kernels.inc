@@ -392,17 +392,6 @@ __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const bf16_t* __rest
   }
 }
 
-// a += b (elementwise, bf16): joins the two gradient branches of a block input
-__global__ __launch_bounds__(256) void add2_kernel(bf16_t* __restrict__ a, const bf16_t* __restrict__ b, int64_t n8) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    F8 x = ld8(a + i * 8);
-    const F8 y = ld8(b + i * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x.v[e] += y.v[e];
-    st8(a + i * 8, x);
-  }
-}
-
 // dx[b][2i][2j][:] += t[b][i][j][:]
 __global__ __launch_bounds__(256) void upsample2_add_bf16_kernel(const bf16_t* __restrict__ t, bf16_t* __restrict__ dx, int B, int Ho,
                                                                  int Wo, int Hi, int Wi, int C) {

@@ -54,6 +54,16 @@ int dh_debug_gemm1x1_bwdsums_bf16(const uint16_t* a_dev, const uint16_t* w_dev, 
 int dh_debug_bn2_bf16(const uint16_t* z_dev, const uint16_t* res_dev, const float* gamma_dev, const float* beta_dev, int32_t relu,
                       uint16_t* y_dev, float* mean_dev, float* invstd_dev, const uint16_t* dy_dev, int32_t relu_mode, uint16_t* dz_dev,
                       uint16_t* g_out_dev, float* dgamma_dev, float* dbeta_dev, int64_t rows, int32_t C, void* stream);
+/* dh_debug_bn2_paths_bf16: dh_debug_bn2_bf16 with the engine's other routes through the same launch code selectable.  fold: 1 = small
+ * maps (rows <= DH_T2_FOLD_ROWS) finalize inside the apply passes, 0 = partial sums -> finalize launch -> elementwise pass everywhere.
+ * bits_dev (may be null): the ReLU pattern of y, [rows][C / 8] bytes, bit e set where value e of the 8 is non-zero.  z2_dev, gamma2_dev,
+ * beta2_dev, mean2_dev, invstd2_dev (all or none): the join of a downsample block, y = relu(bn(z) + bf16(bn2(z2))), the branch BN's
+ * statistics returned in mean2 / invstd2 (needs relu = 1 and no res_dev).  Every refusal names its argument (dh_last_error). */
+int dh_debug_bn2_paths_bf16(const uint16_t* z_dev, const uint16_t* res_dev, const float* gamma_dev, const float* beta_dev, int32_t relu,
+                            int32_t fold, uint16_t* y_dev, uint8_t* bits_dev, float* mean_dev, float* invstd_dev, const uint16_t* z2_dev,
+                            const float* gamma2_dev, const float* beta2_dev, float* mean2_dev, float* invstd2_dev, const uint16_t* dy_dev,
+                            int32_t relu_mode, uint16_t* dz_dev, uint16_t* g_out_dev, float* dgamma_dev, float* dbeta_dev, int64_t rows,
+                            int32_t C, void* stream);
 /* the stem's fused tail (bf16 engine): pooled = maxpool3x3/2(relu(bn(z))) straight from z with batch statistics (+ positions, mean, invstd);
  * with dpool_dev: dz, dgamma, dbeta with the maxpool's gradient gathered inside the BN backward passes. */
 int dh_debug_bn2_pool_bf16(const uint16_t* z_dev, const float* gamma_dev, const float* beta_dev, uint16_t* pooled_dev, uint8_t* idx_dev,
@@ -63,6 +73,9 @@ int dh_debug_bn2_pool_bf16(const uint16_t* z_dev, const float* gamma_dev, const 
  * the strided add of the downsample branch's gradient, and the average-pool + fc backward. */
 int dh_debug_maxpool2_bf16(const uint16_t* x_dev, uint16_t* y_dev, const uint16_t* dy_dev, uint16_t* dx_dev, int32_t B, int32_t Hi,
                            int32_t Wi, int32_t C, void* stream);
+/* ... the same max-pool pair, with the recorded first-maximum positions returned: idx_dev [B][Ho][Wo][C] bytes, dyy * 3 + dxx. */
+int dh_debug_maxpool2_idx_bf16(const uint16_t* x_dev, uint16_t* y_dev, uint8_t* idx_dev, const uint16_t* dy_dev, uint16_t* dx_dev, int32_t B,
+                               int32_t Hi, int32_t Wi, int32_t C, void* stream);
 int dh_debug_upsample2_add_bf16(const uint16_t* t_dev, uint16_t* dx_dev, int32_t B, int32_t Ho, int32_t Wo, int32_t Hi, int32_t Wi,
                                 int32_t C, void* stream);
 int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float* w_dev, uint16_t* dx_dev, int32_t B, int32_t HW, int32_t C,

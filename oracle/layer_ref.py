@@ -25,9 +25,11 @@ MIN_EXP = -125                          # frexp exponent of the smallest normal 
 
 
 def quantum(v: np.ndarray, fmt: str) -> np.ndarray:
-    """ulp of float64 values v in format `fmt` (bf16 / f32): 2^(e - p) for v = m 2^e, 0.5 <= |m| < 1; subnormal spacing below."""
-    _, e = np.frexp(np.asarray(v, np.float64))
-    return np.ldexp(1.0, np.maximum(e, MIN_EXP) - MANT[fmt])
+    """ulp of float64 values v in format `fmt` (bf16 / f32): 2^(e - p) for v = m 2^e, 0.5 <= |m| < 1; subnormal spacing below, and at
+    0 (frexp gives 0 the exponent 0, which would make the unit of an exact zero -- every ReLU-clamped element -- that of 0.5)."""
+    v = np.asarray(v, np.float64)
+    _, e = np.frexp(v)
+    return np.ldexp(1.0, np.maximum(np.where(v == 0, MIN_EXP, e), MIN_EXP) - MANT[fmt])
 
 
 def round_to(v: np.ndarray, fmt: str) -> np.ndarray:
