@@ -5,6 +5,9 @@
 //   dh_embed_class_sums   per-class sums of labelled rows in a fixed chunked order + int64 counts
 //   dh_embed_assign       per row, the nearest of K centres and its squared distance: the scores tile for
 //                         K > 16, one row per lane against centres broadcast from LDS for K <= 16
+//   dh_embed_scatter      the scatter matrix of the rows about a mean: one triangle of 64 x 64 tiles, chunk
+//                         partials in a fixed order, the other triangle a mirrored store
+//   dh_embed_project      scale * (feat - mean) . comp^T: the scores tile with the subtract at staging
 // No atomics, and every reduction has one fixed order that the launch geometry cannot change: a row's result is the same bits
 // whatever n, the row's place and the grid are (the house rule of the canvas kernels).
 //
@@ -341,6 +344,232 @@ __global__ __launch_bounds__(256) void embed_class_final_kernel(const float* __r
   }
 }
 
+// ---- dh_embed_project ------------------------------------------------------------------------------------
+// The tile of embed_scores_kernel with the mean taken off a feature stage as it is parked in LDS (one float32 subtract per element),
+// a scale per component and an output row of ld floats of which only the first K are written.
+__global__ __launch_bounds__(256) void embed_project_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                            const float* __restrict__ mean, const float* __restrict__ comp, int K,
+                                                            const float* __restrict__ scale, float* __restrict__ out, int ld) {
+  __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
+  __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
+  const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
+  const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  ScStage g = sc_fetch(feat, comp, n, D, K, row0, 0, tid);
+  float4 m = *reinterpret_cast<const float4*>(mean + kt * 4);   // the mean of this thread's four columns of the stage
+  float* const st_f = &s_f[rt * SC_LD + kt * 4];
+  float* const st_p = &s_p[rt * SC_LD + kt * 4];
+  for (int c0 = 0; c0 < D; c0 += SC_CK) {
+    __syncthreads();   // the previous stage's readers are done
+    *reinterpret_cast<float4*>(st_f) = make_float4(g.f0.x - m.x, g.f0.y - m.y, g.f0.z - m.z, g.f0.w - m.w);
+    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = make_float4(g.f1.x - m.x, g.f1.y - m.y, g.f1.z - m.z, g.f1.w - m.w);
+    *reinterpret_cast<float4*>(st_p) = g.p0;
+    *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
+    *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
+    *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
+    __syncthreads();
+    if (c0 + SC_CK < D) {
+      g = sc_fetch(feat, comp, n, D, K, row0, c0 + SC_CK, tid);
+      m = *reinterpret_cast<const float4*>(mean + c0 + SC_CK + kt * 4);
+    }
+    if (kt < K) {
+#pragma unroll 4
+      for (int c = 0; c < SC_CK; c += 4) {
+        float4 f[2], p[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(rt + 16 * i) * SC_LD + c]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const float4*>(&s_p[(kt + 16 * j) * SC_LD + c]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float t = acc[i][j];
+            t = __builtin_fmaf(f[i].x, p[j].x, t);
+            t = __builtin_fmaf(f[i].y, p[j].y, t);
+            t = __builtin_fmaf(f[i].z, p[j].z, t);
+            t = __builtin_fmaf(f[i].w, p[j].w, t);
+            acc[i][j] = t;
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = kt + 16 * j;
+    if (k >= K) continue;
+    const float s = scale ? scale[k] : 1.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int64_t row = row0 + rt + 16 * i;
+      if (row < n) out[row * ld + k] = s * acc[i][j];
+    }
+  }
+}
+
+// ---- dh_embed_scatter ------------------------------------------------------------------------------------
+// S = T^T T of the centred rows, one triangle of 64 x 64 output tiles.  Workgroup (group of chunks, tile pair (ta, tb), ta <= tb);
+// thread (ra = tid / 16, rb = tid % 16) owns S[a0 + 4 ra + i][b0 + 4 rb + j], i, j < 4: sixteen accumulators, each ONE chain of fused
+// multiply-adds over the rows of a chunk in ascending order, added to the thread's running totals at the end of every chunk
+// (tot = tot + acc, from 0, in ascending chunk order).  Rows go through LDS 32 at a time as two slabs [row][64 columns] (a diagonal
+// tile parks one and reads it twice), the mean already taken off; a row step is 2 ds_read_b128 (16 lanes share the a-slab address,
+// the 16 b-slab addresses fill one 256-byte bank row: no conflicts, no padding) for 16 FMAs.  The next stage's global loads are
+// issued before the current stage's arithmetic.  Rows past the chunk's (or the matrix's) end are loaded from the last real row
+// (in bounds) and parked as zeros, which leave a chain as it is.
+//   direct != 0: the workgroup walks ALL chunks and stores its totals into S, the off-diagonal tile a second time transposed
+//                (S[b][a] is S[a][b]'s bits: the product commutes); no scratch.
+//   direct == 0: one chunk per workgroup (chunk ch0 + blockIdx.x), its partial goes to work[blockIdx.x][pair][64][64];
+//                embed_scatter_fold_kernel adds the partials in ascending chunk order.  The host launches the pair once per batch
+//                of chunks, batch after batch, so the scratch holds one batch (see sk_batch).
+constexpr int SK_T = 64;       // the side of an output tile
+constexpr int SK_ROWS = 32;    // rows per LDS stage (CHUNK % SK_ROWS == 0)
+
+__device__ __forceinline__ void sk_pair(int pair, int T, int& ta, int& tb) {   // pairs in the order (0,0) (0,1) .. (0,T-1) (1,1) ..
+  ta = 0;
+  while (pair >= T - ta) { pair -= T - ta; ++ta; }
+  tb = ta + pair;
+}
+__device__ __forceinline__ float4 sk_centre(float4 v, float4 m, bool live) {
+  return live ? make_float4(v.x - m.x, v.y - m.y, v.z - m.z, v.w - m.w) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+__global__ __launch_bounds__(256) void embed_scatter_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                            const float* __restrict__ mean, int64_t n_chunks, int64_t ch0,
+                                                            int direct, float* __restrict__ dst) {
+  __shared__ __attribute__((aligned(16))) float s_a[SK_ROWS * SK_T];
+  __shared__ __attribute__((aligned(16))) float s_b[SK_ROWS * SK_T];
+  const int tid = threadIdx.x, ra = tid >> 4, rb = tid & 15;
+  const int T = D / SK_T;
+  int ta, tb;
+  sk_pair(blockIdx.y, T, ta, tb);
+  const bool diag = ta == tb;
+  const int a0 = ta * SK_T, b0 = tb * SK_T;
+  const float* const rd_b = diag ? s_a : s_b;
+  const int lr = tid >> 4, lc = (tid & 15) * 4;   // this thread parks rows lr and lr + 16, columns lc .. lc + 3 of each slab
+  const float4 ma = *reinterpret_cast<const float4*>(mean + a0 + lc);
+  const float4 mb = *reinterpret_cast<const float4*>(mean + b0 + lc);
+  float tot[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[i][j] = 0.f;
+  const int64_t ch_lo = direct ? 0 : ch0 + blockIdx.x, ch_hi = direct ? n_chunks : ch_lo + 1;
+  for (int64_t ch = ch_lo; ch < ch_hi; ++ch) {
+    const int64_t base = ch * CHUNK;
+    const int64_t last = std::min<int64_t>(base + CHUNK, n) - 1;   // the chunk's last row, >= base
+    const int rows = (int)(last - base + 1);
+    float acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    float4 ga0 = sc_load(feat, base + lr, last, D, a0 + lc), ga1 = sc_load(feat, base + lr + 16, last, D, a0 + lc);
+    float4 gb0 = ga0, gb1 = ga1;
+    if (!diag) { gb0 = sc_load(feat, base + lr, last, D, b0 + lc); gb1 = sc_load(feat, base + lr + 16, last, D, b0 + lc); }
+    for (int r0 = 0; r0 < rows; r0 += SK_ROWS) {
+      __syncthreads();   // the previous stage's readers are done
+      const bool live0 = base + r0 + lr <= last, live1 = base + r0 + lr + 16 <= last;
+      *reinterpret_cast<float4*>(&s_a[lr * SK_T + lc]) = sk_centre(ga0, ma, live0);
+      *reinterpret_cast<float4*>(&s_a[(lr + 16) * SK_T + lc]) = sk_centre(ga1, ma, live1);
+      if (!diag) {
+        *reinterpret_cast<float4*>(&s_b[lr * SK_T + lc]) = sk_centre(gb0, mb, live0);
+        *reinterpret_cast<float4*>(&s_b[(lr + 16) * SK_T + lc]) = sk_centre(gb1, mb, live1);
+      }
+      __syncthreads();
+      if (r0 + SK_ROWS < rows) {
+        const int64_t nx = base + r0 + SK_ROWS + lr;
+        ga0 = sc_load(feat, nx, last, D, a0 + lc);
+        ga1 = sc_load(feat, nx + 16, last, D, a0 + lc);
+        if (!diag) { gb0 = sc_load(feat, nx, last, D, b0 + lc); gb1 = sc_load(feat, nx + 16, last, D, b0 + lc); }
+      }
+#pragma unroll 8
+      for (int r = 0; r < SK_ROWS; ++r) {
+        const float4 va = *reinterpret_cast<const float4*>(&s_a[r * SK_T + 4 * ra]);
+        const float4 vb = *reinterpret_cast<const float4*>(&rd_b[r * SK_T + 4 * rb]);
+        const float a[4] = {va.x, va.y, va.z, va.w}, b[4] = {vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_fmaf(a[i], b[j], acc[i][j]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tot[i][j] = tot[i][j] + acc[i][j];
+  }
+  if (!direct) {   // work[chunk of the batch][pair][64][64]
+    float* w = dst + ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * (SK_T * SK_T) + (4 * ra) * SK_T + 4 * rb;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<float4*>(w + i * SK_T) = make_float4(tot[i][0], tot[i][1], tot[i][2], tot[i][3]);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    *reinterpret_cast<float4*>(dst + (int64_t)(a0 + 4 * ra + i) * D + b0 + 4 * rb) = make_float4(tot[i][0], tot[i][1], tot[i][2], tot[i][3]);
+  if (!diag) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *reinterpret_cast<float4*>(dst + (int64_t)(b0 + 4 * rb + j) * D + a0 + 4 * ra) = make_float4(tot[0][j], tot[1][j], tot[2][j], tot[3][j]);
+  }
+}
+
+// The second pass of direct == 0: thread (pair, ra, rb) adds its 4 x 4 block of the partials of a batch's chunks in ascending chunk
+// order (eight loads in flight, added in order) to what S holds from the batches before it (its own triangle's element; 0 for the
+// first batch) and stores it into S as the kernel above does.
+__global__ __launch_bounds__(256) void embed_scatter_fold_kernel(const float* __restrict__ work, int64_t n_chunks, int D, int first,
+                                                                 float* __restrict__ S) {
+  const int tid = threadIdx.x, ra = tid >> 4, rb = tid & 15;
+  const int n_pairs = gridDim.x;
+  int ta, tb;
+  sk_pair(blockIdx.x, D / SK_T, ta, tb);
+  const int a0 = ta * SK_T, b0 = tb * SK_T;
+  const int64_t step = (int64_t)n_pairs * (SK_T * SK_T);
+  float4 tot[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float* w = work + (int64_t)blockIdx.x * (SK_T * SK_T) + (4 * ra + i) * SK_T + 4 * rb;
+    float* const s_row = S + (int64_t)(a0 + 4 * ra + i) * D + b0 + 4 * rb;
+    float4 t = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(s_row);
+    int64_t ch = 0;
+    for (; ch + 8 <= n_chunks; ch += 8) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(w + (ch + u) * step);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { t.x = t.x + v[u].x; t.y = t.y + v[u].y; t.z = t.z + v[u].z; t.w = t.w + v[u].w; }
+    }
+    for (; ch < n_chunks; ++ch) {
+      const float4 v = *reinterpret_cast<const float4*>(w + ch * step);
+      t.x = t.x + v.x; t.y = t.y + v.y; t.z = t.z + v.z; t.w = t.w + v.w;
+    }
+    tot[i] = t;
+    *reinterpret_cast<float4*>(s_row) = t;
+  }
+  if (ta != tb) {
+    float* m = S + (int64_t)(b0 + 4 * rb) * D + a0 + 4 * ra;
+    *reinterpret_cast<float4*>(m) = make_float4(tot[0].x, tot[1].x, tot[2].x, tot[3].x);
+    *reinterpret_cast<float4*>(m + D) = make_float4(tot[0].y, tot[1].y, tot[2].y, tot[3].y);
+    *reinterpret_cast<float4*>(m + 2 * (int64_t)D) = make_float4(tot[0].z, tot[1].z, tot[2].z, tot[3].z);
+    *reinterpret_cast<float4*>(m + 3 * (int64_t)D) = make_float4(tot[0].w, tot[1].w, tot[2].w, tot[3].w);
+  }
+}
+
+// Which decomposition dh_embed_scatter takes: the chunks of one batch are spread over the grid, their partials held in scratch of
+// at most SK_WORK_FLOATS floats and at most half the feature matrix; a matrix too small for a batch of two chunks is walked by one
+// workgroup per tile pair, without scratch (sk_batch == 0).
+constexpr int64_t SK_WORK_FLOATS = (int64_t)1 << 26;
+int64_t sk_pairs(int D) { return (int64_t)(D / SK_T) * (D / SK_T + 1) / 2; }
+int64_t sk_batch(int64_t n, int D) {
+  const int64_t n_chunks = (n + CHUNK - 1) / CHUNK;
+  const int64_t b = std::min(n_chunks, std::min(SK_WORK_FLOATS, n * D / 2) / (sk_pairs(D) * SK_T * SK_T));
+  return b < 2 ? 0 : b;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int check_dims(const char* what, int64_t n, int32_t D, int32_t K) {
@@ -420,6 +649,62 @@ extern "C" int dh_embed_class_sums(const float* feat, const int32_t* label, int6
   }
   hipLaunchKernelGGL(embed_class_final_kernel, dim3((K * D + 255) / 256), dim3(256), 0, st, work, chunk_count, n_chunks, D, K, sums,
                      counts);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int64_t dh_embed_scatter_work_size(int64_t n, int32_t D) {
+  if (check_dims("dh_embed_scatter_work_size", n, D, 1)) return -1;
+  return sk_batch(n, D) * sk_pairs(D) * (SK_T * SK_T);   // partials float32[chunks of a batch][pairs][64][64]
+}
+
+extern "C" int dh_embed_scatter(const float* feat, int64_t n, int32_t D, const float* mean, float* scatter, float* work,
+                                void* stream) {
+  if (int rc = check_dims("dh_embed_scatter", n, D, 1)) return rc;
+  const int64_t n_chunks = (n + CHUNK - 1) / CHUNK;
+  DH_REQUIRE(n_chunks <= 0x7fffffff, "dh_embed_scatter: n = %lld exceeds one launch", (long long)n);
+  hipStream_t st = dh::as_stream(stream);
+  if (n == 0) {   // needs no pointer; a matrix that is given becomes all zero
+    if (!scatter) return DH_OK;
+    DH_REQUIRE(aligned16(scatter), "dh_embed_scatter: scatter_dev not 16-byte aligned");
+    DH_HIP(hipMemsetAsync(scatter, 0, sizeof(float) * (size_t)D * D, st));
+    return DH_OK;
+  }
+  const int64_t batch = sk_batch(n, D);
+  const bool direct = batch == 0;
+  DH_REQUIRE(feat && mean && scatter, "dh_embed_scatter: null feat_dev, mean_dev or scatter_dev");
+  DH_REQUIRE(direct || work, "dh_embed_scatter: null work_dev (dh_embed_scatter_work_size(n, D) floats)");
+  DH_REQUIRE(aligned16(feat) && aligned16(mean) && aligned16(scatter) && (direct || aligned16(work)),
+             "dh_embed_scatter: feat_dev / mean_dev / scatter_dev / work_dev not 16-byte aligned");
+  const int n_pairs = (int)sk_pairs(D);   // <= 2080
+  if (direct) {
+    hipLaunchKernelGGL(embed_scatter_kernel, dim3(1, n_pairs), dim3(256), 0, st, feat, n, D, mean, n_chunks, (int64_t)0, 1, scatter);
+    DH_LAUNCH_CHECK();
+    return DH_OK;
+  }
+  for (int64_t ch0 = 0; ch0 < n_chunks; ch0 += batch) {
+    const int64_t count = std::min(batch, n_chunks - ch0);
+    hipLaunchKernelGGL(embed_scatter_kernel, dim3((unsigned)count, n_pairs), dim3(256), 0, st, feat, n, D, mean, n_chunks, ch0, 0, work);
+    DH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(embed_scatter_fold_kernel, dim3(n_pairs), dim3(256), 0, st, work, count, D, ch0 == 0 ? 1 : 0, scatter);
+    DH_LAUNCH_CHECK();
+  }
+  return DH_OK;
+}
+
+extern "C" int dh_embed_project(const float* feat, int64_t n, int32_t D, const float* mean, const float* comp, int32_t K,
+                                const float* scale, float* out, int32_t ld, void* stream) {
+  if (int rc = check_dims("dh_embed_project", n, D, K)) return rc;
+  DH_REQUIRE(ld >= K && ld <= 4096 && ld % 4 == 0, "dh_embed_project: ld = %d unsupported (K = %d <= ld <= 4096, ld %% 4 == 0)", ld, K);
+  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_project: n = %lld exceeds one launch", (long long)n);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(feat && mean && comp && out, "dh_embed_project: null feat_dev, mean_dev, comp_dev or out_dev");
+  DH_REQUIRE(aligned16(feat) && aligned16(mean) && aligned16(comp) && aligned16(out),
+             "dh_embed_project: feat_dev / mean_dev / comp_dev / out_dev not 16-byte aligned");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(scale) & 3) == 0, "dh_embed_project: scale_dev not 4-byte aligned");
+  const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
+  hipLaunchKernelGGL(embed_project_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, mean, comp, K, scale, out,
+                     ld);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

@@ -13,7 +13,8 @@ ones and traces them into polygons; the CLI does so with `--regions_json`, `--mi
 `extract_embeddings(sampler, model, ...)` (deephisto_amd.embeddings) hands out the per-tile feature vectors of
 the same plan, and `PrototypeClassifier` scores them against class prototypes; the CLI does so with `--save_embeddings PATH` and
 `--prototypes PATH`.  Without an annotation, `--clusters K` groups them by k-means (deephisto_amd.clustering)
-and paints the cluster map.
+and paints the cluster map; `--pca N` fits a principal-component basis on them (deephisto_amd.pca) and
+paints the first three components as RGB.
 `main` calls `predict_full_patched` and `predict_random_patched` through this module's globals (tests replace them here).
 """
 from __future__ import annotations
@@ -32,6 +33,7 @@ from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embedding
 from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
+from ..pca import PCA  # noqa: F401  (exported here)
 from ..predict import (_SIDE_STREAMS, _forward_streamed, _side_stream, exchange_logits, predict_full_patched,  # noqa: F401  (exported here)
                        predict_random_patched, shard_range)
 from ..psimage_compat import Patch, open_slide
@@ -315,9 +317,10 @@ def _proba_from_args(ap, args) -> None:
 
 
 def _embeddings_from_args(ap, args) -> None:
-    """Checks --save_embeddings / --prototypes; a bad combination is an argparse error."""
+    """Checks --save_embeddings / --prototypes / --clusters / --pca; a bad combination is an argparse error."""
     for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes),
-                        ("--clusters", args.clusters), ("--load_clusters", args.load_clusters)):
+                        ("--clusters", args.clusters), ("--load_clusters", args.load_clusters),
+                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca)):
         if not value:
             continue
         _dense_resident_only(ap, args, flag)
@@ -338,6 +341,15 @@ def _embeddings_from_args(ap, args) -> None:
         ap.error("--save_clusters, --cluster_seed and --cluster_init need --clusters")
     if (args.clusters is not None or args.load_clusters) and args.min_region is not None:
         ap.error("--min_region cleans the class map; with --clusters the region flags describe the cluster map as it is")
+    if args.pca is not None and not 1 <= args.pca <= 64:
+        ap.error(f"--pca must be in 1 .. 64, not {args.pca}")
+    if args.load_pca:
+        if args.save_pca or args.pca is not None:
+            ap.error("--load_pca applies a saved basis: --pca and --save_pca belong to a fit")
+        if not Path(args.load_pca).is_file():
+            ap.error(f"--load_pca {args.load_pca}: no such file")
+    elif args.save_pca and args.pca is None:
+        ap.error("--save_pca needs --pca")
 
 
 def _regions_from_args(ap, args) -> None:
@@ -421,6 +433,12 @@ def _build_parser():
     ap.add_argument("--save_clusters", default=None, metavar="PATH", help="with --clusters: the fitted codebook as one .npz (rank 0)")
     ap.add_argument("--load_clusters", default=None, metavar="PATH",
                     help="apply the codebook of an earlier --save_clusters to this slide instead of fitting (K comes from the file)")
+    ap.add_argument("--pca", type=int, default=None, metavar="N",
+                    help="principal components of the tile embeddings of this pass (1 .. 64, no annotation needed): writes "
+                         "{stem}_pca.jpg, the first three components as red, green and blue, and {stem}_pca.json (rank 0)")
+    ap.add_argument("--save_pca", default=None, metavar="PATH", help="with --pca: the fitted basis as one .npz (rank 0)")
+    ap.add_argument("--load_pca", default=None, metavar="PATH",
+                    help="apply the basis of an earlier --save_pca to this slide instead of fitting (N comes from the file)")
     return ap
 
 
@@ -480,7 +498,8 @@ def _run(args, model, device, rank, world):
         info: dict = {}
         qinfo: dict = {}
         args.embeddings = None
-        if args.save_embeddings or args.prototypes or args.clusters is not None or args.load_clusters:
+        if args.save_embeddings or args.prototypes or args.clusters is not None or args.load_clusters or args.pca is not None \
+                or args.load_pca:
             # the same plan through the features entry; the map is finished from that pass's logits by predict_full_patched's tail
             filt = args.quality_filter if args.quality_filter is not None else args.tissue_filter
             emb = args.embeddings = extract_embeddings(smp, model, tissue=args.tissue_filter, tissue_info=info,
@@ -597,6 +616,42 @@ def _clusters_rank0(args, src, stem, out_dir, device):
     return cmap, dsc
 
 
+def _pca_rank0(args, stem, out_dir, device) -> None:
+    """--pca / --load_pca: fit a principal-component basis on this slide's embeddings (or apply a saved one), write
+    `{stem}_pca.json` and, with visualisations, `{stem}_pca.jpg`: the first min(3, N) components as red, green and blue."""
+    import json
+    import time
+
+    emb = args.embeddings
+    if args.load_pca:
+        pca = PCA.load(args.load_pca, device=device)
+        if pca.components_.shape[1] != emb.width:
+            raise ValueError(f"--load_pca {args.load_pca}: a basis of {pca.components_.shape[1]} columns does not fit this run "
+                             f"({emb.width})")
+    else:
+        pca = PCA(args.pca).fit(emb)
+        if args.save_pca:
+            Path(args.save_pca).parent.mkdir(parents=True, exist_ok=True)
+            pca.save(args.save_pca)
+    N = pca.n_components
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    pca.transform(emb)
+    torch.cuda.synchronize(device)
+    project_ms = 1e3 * (time.perf_counter() - t0)
+    ratio = pca.explained_variance_ratio_
+    print(f"pca: {N} components over {len(emb)} tiles, explained variance {float(ratio.sum()):.4f} "
+          f"(first {float(ratio[0]):.4f}), " + (f"basis {args.load_pca}" if args.load_pca else f"fitted on {pca.n_samples_} rows"),
+          flush=True)
+    out_dir.mkdir(exist_ok=True, parents=True)
+    doc = dict(n_components=N, n_tiles=len(emb), n_samples=pca.n_samples_, explained_variance=pca.explained_variance_.tolist(),
+               explained_variance_ratio=ratio.tolist(), scatter_ms=pca.timings_.get("scatter_ms"), eigen_ms=pca.timings_.get("eigen_ms"),
+               project_ms=project_ms, fitted_here=not args.load_pca)
+    (out_dir / f"{stem}_pca.json").write_text(json.dumps(doc, indent=1) + "\n")
+    if not args.no_visualizations:
+        _save_jpeg(pca.colour_map(emb, args.downscale_vis, components=tuple(range(min(3, N)))), out_dir / f"{stem}_pca.jpg")
+
+
 def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
     """What rank 0, where the map is whole, prints and writes after the prediction: the score, the JPEGs, the probability
     files, then the regions with the cleaned map's score and JPEGs."""
@@ -618,6 +673,8 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
         save_proba(args.save_proba, proba)
     if args.prototypes:
         _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device)
+    if args.pca is not None or args.load_pca:
+        _pca_rank0(args, stem, out_dir, device)
     if args.clusters is not None or args.load_clusters:
         pred, anno_dsc = _clusters_rank0(args, src, stem, out_dir, device)   # the region flags below describe the cluster map
     if not (args.regions_json or args.min_region is not None or args.export_anno):
@@ -690,6 +747,10 @@ def main(argv=None, model=None):
     most covering tiles per cell in a K-colour palette over the slide, and `{stem}_clusters.json` (K, sizes, inertia, iterations,
     converged); `--load_clusters PATH` applies a saved codebook instead of fitting.  `--regions_json` / `--export_anno` then
     describe the cluster map's regions, named `cluster_0` ...; the class map and its JPEGs are those of a run without the flags.
+    `--pca N [--save_pca PATH]` fits the first N principal components of the embeddings of the same pass (DESIGN.md section 4.19;
+    the same refusals) and writes `{stem}_pca.jpg`, the first three components of every cell's tiles as red, green and blue, and
+    `{stem}_pca.json` (N, tiles, explained variance and ratios, milliseconds of scatter, eigen-solve and projection);
+    `--load_pca PATH` applies a saved basis instead of fitting.
     `model`: an injected module (tests)."""
     from ..distributed import finalize, init_from_env
     from ..models.patch_cls_simple import utils

@@ -331,7 +331,19 @@ int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64
  *   lexicographic minimum of (distance, index) from the start (+inf, -1): at equal distances the lower index wins, a
  *   NaN or +inf distance never does, and a row with no finite distance gets (-1, +inf).  merge != 0: the start is
  *   the row's existing (dist_dev[i], label_dev[i]) instead, which is kept at ties when its index is the lower (the
- *   caller's part); this assigns against more than 64 centres in passes (k0 = 0, 64, ...).  k0 >= 0. */
+ *   caller's part); this assigns against more than 64 centres in passes (k0 = 0, 64, ...).  k0 >= 0.
+ * dh_embed_scatter: scatter_dev (float32[D][D], both triangles written) = the scatter matrix of the
+ *   rows about mean_dev (float32[D]): S[a][b] = sum_i t_i[a] * t_i[b] with t_i[c] = feat[i][c] - mean[c] (one float32
+ *   subtract).  The order is the contract: rows are cut into chunks of DH_EMBED_CHUNK_ROWS; a chunk's partial is ONE
+ *   accumulator from 0, for its rows in ascending order acc = fma(t[a], t[b], acc); the result starts at 0 and adds the
+ *   partials of ALL chunks in ascending chunk order (float32 throughout).  Hence S[a][b] and S[b][a] are the same bits,
+ *   the result does not depend on the grid, and n = 0 writes all zeros (into scatter_dev when it is given; no pointer
+ *   is needed then).  work_dev: float32[dh_embed_scatter_work_size(n, D)] scratch (16-byte aligned; may be NULL when
+ *   the size is 0); the size is -1 for bad arguments.
+ * dh_embed_project: out[i][j] = scale[j] * acc for j < K with ONE accumulator from 0: for c
+ *   ascending acc = fma(feat[i][c] - mean[c], comp[j][c], acc) (one float32 subtract).  comp_dev float32[K][D],
+ *   scale_dev float32[K] or NULL (every scale 1), out_dev float32[n][ld] with K <= ld <= 4096 and ld % 4 == 0;
+ *   columns K .. ld - 1 of out_dev are not touched.  A row's result depends on that row alone. */
 #define DH_EMBED_CHUNK_ROWS 1024
 int dh_embed_normalize(const float* in_dev, int64_t n, int32_t D, float* out_dev, void* stream);
 int dh_embed_scores(const float* feat_dev, int64_t n, int32_t D, const float* proto_dev, int32_t K, float scale,
@@ -341,6 +353,11 @@ int dh_embed_class_sums(const float* feat_dev, const int32_t* label_dev, int64_t
                         float* sums_dev, int64_t* counts_dev, float* work_dev, void* stream);
 int dh_embed_assign(const float* feat_dev, int64_t n, int32_t D, const float* centres_dev, int32_t K, int32_t k0,
                     int32_t merge, int32_t* label_dev, float* dist_dev, void* stream);
+int64_t dh_embed_scatter_work_size(int64_t n, int32_t D);
+int dh_embed_scatter(const float* feat_dev, int64_t n, int32_t D, const float* mean_dev, float* scatter_dev,
+                     float* work_dev, void* stream);
+int dh_embed_project(const float* feat_dev, int64_t n, int32_t D, const float* mean_dev, const float* comp_dev,
+                     int32_t K, const float* scale_dev, float* out_dev, int32_t ld, void* stream);
 
 /* ---- a7: training step (float32) -------------------------------------------------------
  * Replaces, for the same network, models/patch_cls_simple/train.py:168-172:
