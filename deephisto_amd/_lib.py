@@ -67,6 +67,10 @@ SIGNATURES = {
     "dh_resnet50_forward_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p]),
     "dh_resnet18_features_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
     "dh_resnet50_features_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "dh_resnet18_cam_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "dh_resnet50_cam_tiles": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "dh_accumulate_cam": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _p, _p, _p]),
+    "dh_accumulate_cam_mean": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i64, _i64, _p, _p, _p, _p, _i32, _p]),
     "dh_embed_normalize": (C.c_int, [_p, _i64, _i32, _p, _p]),
     "dh_embed_scores": (C.c_int, [_p, _i64, _i32, _p, _i32, C.c_float, _p, _p]),
     "dh_embed_class_work_size": (_i64, [_i64, _i32, _i32]),

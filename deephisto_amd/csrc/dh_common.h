@@ -30,6 +30,15 @@ struct BinPlan { int32_t G, bins_x; int64_t nbins, total; const int32_t *d_start
 struct BinGeom { int32_t G, bins_x, dh, dw, n_cls, P, d; };
 int bin_plan(const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int64_t h, int64_t w, hipStream_t st, BinPlan* out);
 
+// Row of a class activation map (float32 [n][S * S][n_cls], S = P / 32) that tile t at origin (y, x) contributes to canvas cell
+// (cy, cx), a cell the tile covers: position i = ceil(((cy + 1) d - y) / 32) - 1 along y and j likewise along x, the one position
+// whose 32-pixel sub-tile owns the cell.  (cy + 1) d <= h, so 32-bit arithmetic holds up to CAM_MAX_SIDE.
+constexpr int64_t CAM_MAX_SIDE = INT32_MAX - 64;
+__host__ __device__ inline int64_t cam_row(int64_t t, int S, int d, int cy, int cx, int y, int x) {
+  const int i = ((cy + 1) * d - y + 31) / 32 - 1, j = ((cx + 1) * d - x + 31) / 32 - 1;
+  return (t * S + i) * S + j;
+}
+
 }  // namespace dh
 
 #define DH_REQUIRE(cond, ...)            \

@@ -1,6 +1,7 @@
 // Whole-slide probability maps for MI355X (gfx950, wave64):
 //   dh_softmax_rows     per-tile softmax of the logits (expf, sums in class order)
 //   dh_accumulate_mean  ordered per-cell sums of the tile probabilities + int32 hit counts, with the finish fused in on request
+//   dh_accumulate_cam_mean  the same over S x S rows per tile, each on its own 32 x 32-pixel block
 //   dh_finish_mean      proba = sum / count, first-maximum class, confidence; fill for cells nothing covers
 //   dh_heatmap_blend    a scalar field times a colour blended over the slide in float64
 // HBM-bound like the class-map kernels of tile_kernels.hip, whose bin plan (one workgroup per G x G bin, one writer per cell,
@@ -48,13 +49,17 @@ __device__ __forceinline__ int first_max(Ptr p, int n_cls, float* best_out) {
 // order.  FINISH: the pass ends with proba = sum / count through LDS and the class-0 thread of each cell takes the first
 // maximum -- the sums never travel to HBM and back for the finish.  Bins without tiles still run then (their cells get the
 // fill, or the finish of what the state held).
-template <bool FINISH>
+// CAM (dh_accumulate_cam_mean): `probs` holds S x S rows per tile and a covered cell takes the row dh::cam_row names, as in
+// accumulate_bins_kernel<true>.
+template <bool FINISH, bool CAM = false>
 __global__ __launch_bounds__(256) void accumulate_mean_kernel(
     const float* __restrict__ probs, const int32_t* __restrict__ yx, const int32_t* __restrict__ bin_start,
     const int32_t* __restrict__ bin_tiles, BinGeom g, float* __restrict__ sum, int32_t* __restrict__ count,
     int64_t* __restrict__ map, float* __restrict__ conf, int fill_class) {
   __shared__ int32_t s_t[256], s_y0[256], s_y1[256], s_x0[256], s_x1[256];
   __shared__ float s_p[256];
+  __shared__ int32_t s_y[CAM ? 256 : 1], s_x[CAM ? 256 : 1];
+  const int S = g.P >> 5;
   const int bin = blockIdx.x;
   const int beg = bin_start[bin], end = bin_start[bin + 1];
   if (!FINISH && beg == end) return;  // uniform for the block
@@ -77,13 +82,16 @@ __global__ __launch_bounds__(256) void accumulate_mean_kernel(
         s_t[threadIdx.x] = t;
         s_y0[threadIdx.x] = y / g.d; s_y1[threadIdx.x] = (y + g.P) / g.d;
         s_x0[threadIdx.x] = x / g.d; s_x1[threadIdx.x] = (x + g.P) / g.d;
+        if constexpr (CAM) { s_y[threadIdx.x] = y; s_x[threadIdx.x] = x; }
       }
       __syncthreads();
       const int m = min(256, end - l0);
       if (live)
         for (int k = 0; k < m; ++k)
           if (cy >= s_y0[k] && cy < s_y1[k] && cx >= s_x0[k] && cx < s_x1[k]) {
-            acc = acc + probs[(int64_t)s_t[k] * g.n_cls + cls];
+            int64_t row = s_t[k];
+            if constexpr (CAM) row = dh::cam_row(row, S, g.d, cy, cx, s_y[k], s_x[k]);
+            acc = acc + probs[row * g.n_cls + cls];
             ++cnt;
           }
     }
@@ -167,9 +175,11 @@ extern "C" int dh_finish_mean(const float* sum, const int32_t* count, int64_t n_
   return DH_OK;
 }
 
-extern "C" int dh_accumulate_mean(const float* probs, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls,
-                                  int64_t h, int64_t w, float* sum, int32_t* count, int64_t* map, float* conf,
-                                  int32_t fill_class, void* stream) {
+namespace {
+// both ordered mean accumulations: one row per tile (dh_accumulate_mean), or S x S rows per tile (CAM: dh_accumulate_cam_mean)
+template <bool CAM>
+int accumulate_mean(const float* probs, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls, int64_t h, int64_t w,
+                    float* sum, int32_t* count, int64_t* map, float* conf, int32_t fill_class, void* stream) {
   DH_REQUIRE(n >= 0 && n <= INT32_MAX / 8, "accumulate mean: n=%lld outside [0, %d]", (long long)n, INT32_MAX / 8);
   DH_REQUIRE(n_cls > 0 && n_cls <= MAX_CLS, "accumulate mean: n_cls=%d outside [1, %d]", n_cls, MAX_CLS);
   DH_REQUIRE(P > 0 && d > 0, "accumulate mean: patch=%d and downscale=%d must be > 0", P, d);
@@ -188,13 +198,29 @@ extern "C" int dh_accumulate_mean(const float* probs, const int32_t* yx_host, in
     return map ? dh_finish_mean(sum, count, dh_ * dw_, n_cls, fill_class, sum, map, conf, stream) : DH_OK;
   const BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
   if (map)
-    hipLaunchKernelGGL(accumulate_mean_kernel<true>, dim3((unsigned)plan.nbins), dim3(256), 0, st, probs, plan.d_yx, plan.d_start,
+    hipLaunchKernelGGL((accumulate_mean_kernel<true, CAM>), dim3((unsigned)plan.nbins), dim3(256), 0, st, probs, plan.d_yx, plan.d_start,
                        plan.d_tiles, g, sum, count, map, conf, fill_class);
   else
-    hipLaunchKernelGGL(accumulate_mean_kernel<false>, dim3((unsigned)plan.nbins), dim3(256), 0, st, probs, plan.d_yx, plan.d_start,
+    hipLaunchKernelGGL((accumulate_mean_kernel<false, CAM>), dim3((unsigned)plan.nbins), dim3(256), 0, st, probs, plan.d_yx, plan.d_start,
                        plan.d_tiles, g, sum, count, map, conf, fill_class);
   DH_LAUNCH_CHECK();
   return DH_OK;
+}
+}  // namespace
+
+extern "C" int dh_accumulate_mean(const float* probs, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls,
+                                  int64_t h, int64_t w, float* sum, int32_t* count, int64_t* map, float* conf,
+                                  int32_t fill_class, void* stream) {
+  return accumulate_mean<false>(probs, yx_host, n, P, d, n_cls, h, w, sum, count, map, conf, fill_class, stream);
+}
+
+extern "C" int dh_accumulate_cam_mean(const float* probs, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls,
+                                      int64_t h, int64_t w, float* sum, int32_t* count, int64_t* map, float* conf,
+                                      int32_t fill_class, void* stream) {
+  DH_REQUIRE(P > 0 && P % 32 == 0, "accumulate cam mean: patch %d is not a positive multiple of 32", P);
+  DH_REQUIRE(h <= dh::CAM_MAX_SIDE && w <= dh::CAM_MAX_SIDE, "accumulate cam mean: h=%lld, w=%lld above %lld", (long long)h,
+             (long long)w, (long long)dh::CAM_MAX_SIDE);
+  return accumulate_mean<true>(probs, yx_host, n, P, d, n_cls, h, w, sum, count, map, conf, fill_class, stream);
 }
 
 extern "C" int dh_heatmap_blend(const uint8_t* img, const float* field, int64_t field_stride, int64_t n_cells,

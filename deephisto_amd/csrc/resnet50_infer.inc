@@ -68,7 +68,7 @@ int r50_gemm(const ConvLayer& L, const bf16_t* in, const bf16_t* res, bf16_t* ou
 }
 
 int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w, const int32_t* yx,
-                     int B, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
+                     int B, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr, float* cam = nullptr) {
   const int H2 = P / 4;   // stem 7x7/2 -> P/2, maxpool 3x3/2 -> P/4 (P % 32 == 0)
   auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t px = (size_t)B * H2 * H2 * 2;   // bytes per channel of a stage-1 map
@@ -109,9 +109,10 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
   }
   if (feat)   // dh_resnet50_features_tiles: the same head, the pooled vector stored as well
     hipLaunchKernelGGL(r50_head_kernel<true>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
-  else
+  else if (logits)   // null only in dh_resnet50_cam_tiles without logits
     hipLaunchKernelGGL(r50_head_kernel<false>, dim3(B), dim3(256), 0, st, X, H * H, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
+  if (cam) return launch_cam_head<__bf16>(net, X, B, H * H, cam, st);   // dh_resnet50_cam_tiles: fc per position of the same activation
   return DH_OK;
 }
 
@@ -142,13 +143,13 @@ int r50_check_origins(dh_resnet50* net, int64_t h, int64_t w, const int32_t* yx,
   return DH_OK;
 }
 
-// both tiles entries: the origin check, then the forward
+// the tiles entries: the origin check, then the forward
 int r50_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n, int32_t P, float* feat,
-              float* logits, const float* out, void* stream, const char* what) {
+              float* logits, const float* out, void* stream, const char* what, float* cam = nullptr) {
   hipStream_t st = dh::as_stream(stream);
   return infer_tiles(R50_ENGINE, net, slide, h, w, yx, n, P, feat, out, what, [&](Tap* tap) {
     if (int rc = r50_check_origins(net, h, w, yx, n, P, st, what)) return rc;
-    return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, tap, feat);
+    return r50_forward_impl(net, nullptr, slide, h, w, yx, (int)n, P, logits, st, tap, feat, cam);
   });
 }
 
@@ -225,6 +226,12 @@ extern "C" int dh_resnet50_forward_tiles(dh_resnet50* net, const uint8_t* slide,
 extern "C" int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
                                           int32_t P, float* feat, float* logits, void* stream) {
   return r50_tiles(net, slide, h, w, yx, n, P, feat, logits, feat, stream, "resnet50 features_tiles");
+}
+
+extern "C" int dh_resnet50_cam_tiles(dh_resnet50* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                                     int32_t P, float* cam, float* logits, void* stream) {
+  if (int rc = cam_check(R50_ENGINE, net, P, "resnet50 cam_tiles")) return rc;
+  return r50_tiles(net, slide, h, w, yx, n, P, nullptr, logits, cam, stream, "resnet50 cam_tiles", cam);
 }
 
 // Test hooks (include/deephisto_hip_debug.h): the forward of forward_tiles with one stored activation tapped (no origin check), and a

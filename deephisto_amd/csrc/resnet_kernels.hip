@@ -1205,6 +1205,7 @@ int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide
 }  // namespace
 
 #include "infer_core.inc"
+#include "cam.inc"
 
 struct dh_train;
 struct dh_resnet18 : InferNet {
@@ -1217,7 +1218,8 @@ namespace {
 
 template <typename T>
 int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w,
-                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
+                 const int32_t* yx, int64_t n64, int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr,
+                 float* cam = nullptr) {
   const int B = (int)n64;
   const int esz = (int)sizeof(T);
   const int H1 = (P + 6 - 7) / 2 + 1;       // stem out
@@ -1325,18 +1327,19 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
   if (feat)   // dh_resnet18_features_tiles: the same head, the pooled vector stored as well
     hipLaunchKernelGGL((avgpool_fc_kernel<T, true>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
                        net->desc->feat, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, feat);
-  else
+  else if (logits)   // null only in dh_resnet18_cam_tiles without logits
     hipLaunchKernelGGL((avgpool_fc_kernel<T, false>), dim3(B), dim3(256), 0, st, static_cast<const T*>(X), H * W,
                        net->desc->feat, BLK ? 1 : 0, net->fc_w_dev, net->fc_b_dev, net->n_classes, logits, nullptr);
   DH_LAUNCH_CHECK();
+  if (cam) return launch_cam_head<T>(net, X, B, H * W, cam, st);   // dh_resnet18_cam_tiles: fc per position of the same activation
   return DH_OK;
 }
 
 // the forward in the handle's dtype
 int r18_forward(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t slide_h, int64_t slide_w, const int32_t* yx, int64_t n,
-                int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr) {
-  return net->dtype == DH_DTYPE_F32 ? forward_impl<float>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat)
-                                    : forward_impl<__bf16>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat);
+                int P, float* logits, hipStream_t st, Tap* tap = nullptr, float* feat = nullptr, float* cam = nullptr) {
+  return net->dtype == DH_DTYPE_F32 ? forward_impl<float>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat, cam)
+                                    : forward_impl<__bf16>(net, x, slide, slide_h, slide_w, yx, n, P, logits, st, tap, feat, cam);
 }
 
 int r18_check_forward(const InferNet* net, int64_t n, int32_t P, const void* logits, const char*) {
@@ -1425,6 +1428,14 @@ extern "C" int dh_resnet18_features_tiles(dh_resnet18* net, const uint8_t* slide
                                           const int32_t* yx, int64_t n, int32_t P, float* feat, float* logits, void* stream) {
   return infer_tiles(R18_ENGINE, net, slide, h, w, yx, n, P, feat, feat, "resnet18 features_tiles", [&](Tap* tap) {
     return r18_forward(net, nullptr, slide, h, w, yx, n, P, logits, dh::as_stream(stream), tap, feat);
+  });
+}
+
+extern "C" int dh_resnet18_cam_tiles(dh_resnet18* net, const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx, int64_t n,
+                                     int32_t P, float* cam, float* logits, void* stream) {
+  if (int rc = cam_check(R18_ENGINE, net, P, "resnet18 cam_tiles")) return rc;
+  return infer_tiles(R18_ENGINE, net, slide, h, w, yx, n, P, nullptr, cam, "resnet18 cam_tiles", [&](Tap* tap) {
+    return r18_forward(net, nullptr, slide, h, w, yx, n, P, logits, dh::as_stream(stream), tap, nullptr, cam);
   });
 }
 

@@ -2,7 +2,7 @@
 //   a1  dh_tile_grid            host integer restatement of the dense grid order
 //   --  dh_synth_slide          closed-form benchmark slide generated in HBM
 //   a2/a4/a5 dh_tile_gather     uint8 HWC slide -> [n,P,P,3] / [n,3,P,P] f32|bf16, exactly k/255
-//   a8  dh_accumulate_logits    ordered (bit-exact) canvas accumulation, dh_argmax_map
+//   a8  dh_accumulate_logits    ordered (bit-exact) canvas accumulation, dh_argmax_map; dh_accumulate_cam: S x S rows per tile
 // All of these are HBM-bound byte/integer work: no LDS, no MFMA; the design
 // rules are full-width coalesced rows (one wave = one tile row) and 16-byte stores.
 #include <errno.h>
@@ -735,11 +735,17 @@ extern "C" int dh_tile_coords_f32(const int32_t* yx_dev, int64_t n, float* out, 
 // ---------------------------------------------------------------------------
 using dh::BinGeom;
 
+// CAM (dh_accumulate_cam): `logits` holds S x S rows per tile, S = P / 32, one per 32 x 32-pixel position,
+// and a covered cell takes the row of the one position whose 32-pixel sub-tile owns it -- position i = ceil(((cy + 1) d - y) / 32) - 1
+// along y, likewise along x: the sub-tiles' cell ranges partition the tile's.  Same plan, same bins, same order of additions.
+template <bool CAM>
 __global__ __launch_bounds__(256) void accumulate_bins_kernel(
     const float* __restrict__ logits, const int32_t* __restrict__ yx,
     const int32_t* __restrict__ bin_start, const int32_t* __restrict__ bin_tiles, BinGeom g,
     float* __restrict__ canvas) {
   __shared__ int32_t s_t[256], s_y0[256], s_y1[256], s_x0[256], s_x1[256];
+  __shared__ int32_t s_y[CAM ? 256 : 1], s_x[CAM ? 256 : 1];
+  const int S = g.P >> 5;
   const int bin = blockIdx.x;
   const int beg = bin_start[bin], end = bin_start[bin + 1];
   if (beg == end) return;  // uniform for the block
@@ -761,13 +767,17 @@ __global__ __launch_bounds__(256) void accumulate_bins_kernel(
         s_t[threadIdx.x] = t;
         s_y0[threadIdx.x] = y / g.d; s_y1[threadIdx.x] = (y + g.P) / g.d;
         s_x0[threadIdx.x] = x / g.d; s_x1[threadIdx.x] = (x + g.P) / g.d;
+        if constexpr (CAM) { s_y[threadIdx.x] = y; s_x[threadIdx.x] = x; }
       }
       __syncthreads();
       const int m = min(256, end - l0);
       if (live)
         for (int k = 0; k < m; ++k)
-          if (cy >= s_y0[k] && cy < s_y1[k] && cx >= s_x0[k] && cx < s_x1[k])
-            acc = acc + logits[(int64_t)s_t[k] * g.n_cls + cls];
+          if (cy >= s_y0[k] && cy < s_y1[k] && cx >= s_x0[k] && cx < s_x1[k]) {
+            int64_t row = s_t[k];
+            if constexpr (CAM) row = dh::cam_row(row, S, g.d, cy, cx, s_y[k], s_x[k]);
+            acc = acc + logits[row * g.n_cls + cls];
+          }
     }
     if (live) canvas[addr] = acc;
   }
@@ -879,8 +889,34 @@ extern "C" int dh_accumulate_logits(const float* logits, const int32_t* yx_host,
     if (const int rc = dh::bin_plan(yx_host, n, P, d, h, w, st, &plan)) return rc;
     if (plan.total > 0) {
       dh::BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
-      hipLaunchKernelGGL(accumulate_bins_kernel, dim3((unsigned)plan.nbins), dim3(256), 0, st, logits, plan.d_yx,
+      hipLaunchKernelGGL(accumulate_bins_kernel<false>, dim3((unsigned)plan.nbins), dim3(256), 0, st, logits, plan.d_yx,
                          plan.d_start, plan.d_tiles, g, canvas);
+      DH_LAUNCH_CHECK();
+    }
+  }
+  if (map) return dh_argmax_map(canvas, dh_ * dw_, n_cls, map, stream);
+  return DH_OK;
+}
+
+extern "C" int dh_accumulate_cam(const float* cam, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls, int64_t h,
+                                 int64_t w, float* canvas, int64_t* map, void* stream) {
+  DH_REQUIRE(cam && yx_host && canvas, "accumulate cam: null pointer");
+  DH_REQUIRE(P > 0 && P % 32 == 0, "accumulate cam: patch %d is not a positive multiple of 32", P);
+  DH_REQUIRE(d > 0 && n_cls > 0 && n >= 0, "accumulate cam: bad sizes");
+  DH_REQUIRE(h > 0 && w > 0 && h <= dh::CAM_MAX_SIDE && w <= dh::CAM_MAX_SIDE, "accumulate cam: h=%lld, w=%lld outside [1, %lld]",
+             (long long)h, (long long)w, (long long)dh::CAM_MAX_SIDE);
+  DH_REQUIRE(n <= INT32_MAX / 8, "accumulate cam: too many tiles");
+  const int64_t dh_ = h / d, dw_ = w / d;
+  hipStream_t st = dh::as_stream(stream);
+  if (dh_ == 0 || dw_ == 0) return DH_OK;
+  DH_REQUIRE(dh_ * dw_ <= (int64_t)INT32_MAX, "accumulate cam: canvas too large");
+  if (n > 0) {
+    dh::BinPlan plan;
+    if (const int rc = dh::bin_plan(yx_host, n, P, d, h, w, st, &plan)) return rc;
+    if (plan.total > 0) {
+      dh::BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
+      hipLaunchKernelGGL(accumulate_bins_kernel<true>, dim3((unsigned)plan.nbins), dim3(256), 0, st, cam, plan.d_yx, plan.d_start,
+                         plan.d_tiles, g, canvas);
       DH_LAUNCH_CHECK();
     }
   }

@@ -29,6 +29,7 @@ from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, check  # noqa: F401  (exported here)
 from ..anno.utils import AnnoDescription
 from ..clustering import INITS as CLUSTER_INITS, KMeans, cluster_description, cluster_map  # noqa: F401  (exported here)
+from ..cam import predict_fine_patched  # noqa: F401  (exported here)
 from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embeddings, tile_labels  # noqa: F401  (exported here)
 from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
@@ -352,6 +353,23 @@ def _embeddings_from_args(ap, args) -> None:
         ap.error("--save_pca needs --pca")
 
 
+def _fine_from_args(ap, args) -> None:
+    """Checks --fine; a bad combination is an argparse error."""
+    if not args.fine:
+        return
+    _dense_resident_only(ap, args, "--fine")
+    if args.tta != "off":
+        ap.error("--fine places every position of a tile's last feature map; a rotated view permutes them: it cannot be combined "
+                 "with --tta")
+    for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes),
+                        ("--clusters", args.clusters is not None), ("--load_clusters", args.load_clusters),
+                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca)):
+        if value:
+            ap.error(f"{flag} finishes the class map from one logits row per tile; it cannot be combined with --fine")
+    if args.patch_size % 32:
+        ap.error(f"--fine needs a --patch_size that is a multiple of 32, not {args.patch_size}")
+
+
 def _regions_from_args(ap, args) -> None:
     """Checks the region flags; a bad combination is an argparse error."""
     if args.clean_rounds is not None and args.min_region is None:
@@ -405,6 +423,9 @@ def _build_parser():
     ap.add_argument("--tta", choices=["off", "flips", "d4"], default="off",
                     help="test-time augmentation: classify every tile in 4 (flips) or all 8 (d4) orientations of the square and "
                          "average the logits (resident slide; 4 / 8 times the forward work)")
+    ap.add_argument("--fine", action="store_true",
+                    help="the map from the class activation maps of the last conv: values change every 32 px, same forward pass "
+                         "(dense sampler, resident slide, --patch_size a multiple of 32)")
     ap.add_argument("--proba", action="store_true", help="per-cell mean softmax probabilities; writes {stem}_confidence.jpg")
     ap.add_argument("--heat", nargs="+", default=[], metavar="LABEL",
                     help=f"with --proba: one {{stem}}_heat_LABEL.jpg per class label ({', '.join(KNOWN_COLORS)})")
@@ -455,6 +476,7 @@ def _check_args(ap, args, model=None) -> None:
     args.anno_records = _anno_from_args(ap, args)
     _proba_from_args(ap, args)
     _embeddings_from_args(ap, args)
+    _fine_from_args(ap, args)
 
 
 def _run(args, model, device, rank, world):
@@ -509,6 +531,9 @@ def _run(args, model, device, rank, world):
                 Path(args.save_embeddings).parent.mkdir(parents=True, exist_ok=True)
                 emb.save(args.save_embeddings)
                 print(f"embeddings: {len(emb)} tiles x {emb.width} floats -> {args.save_embeddings}", flush=True)
+        elif args.fine:   # the same plan through the CAM entry: S x S rows per tile, each onto its own 32-pixel block
+            out = predict_fine_patched(smp, model, n_cls, downscale=args.downscale_vis, tissue=args.tissue_filter, tissue_info=info,
+                                       quality=args.quality_filter, quality_info=qinfo, return_proba=args.proba)
         else:
             out = predict_full_patched(smp, model, n_cls, downscale=args.downscale_vis,   # sharded when world > 1
                                        tissue=args.tissue_filter, tissue_info=info, return_proba=args.proba, tta=args.tta_aug,
@@ -751,6 +776,12 @@ def main(argv=None, model=None):
     the same refusals) and writes `{stem}_pca.jpg`, the first three components of every cell's tiles as red, green and blue, and
     `{stem}_pca.json` (N, tiles, explained variance and ratios, milliseconds of scatter, eigen-solve and projection);
     `--load_pca PATH` applies a saved basis instead of fitting.
+    `--fine` builds the map from the class activation maps of the last conv (`predict_fine_patched`): every
+    tile's S x S per-position scores, S = patch_size / 32, go onto their own 32 x 32-pixel blocks, so the map's values change
+    every 32 px instead of once per tile footprint, from the same forward pass.  The canvas shape does not move: `--proba`,
+    `--heat`, `--save_proba`, `--anno`, the region flags, `--tissue`, the quality flags and `--stain` compose with it.  Dense
+    branch, resident slide, `--patch_size` a multiple of 32; refused with `--tta`, `--random_sampler`, `--ondisk` and the
+    embedding flags.
     `model`: an injected module (tests)."""
     from ..distributed import finalize, init_from_env
     from ..models.patch_cls_simple import utils

@@ -391,6 +391,28 @@ class ResNetHIP(nn.Module):
                                           self.n_classes if return_logits else None)
         return (feat, logits) if return_logits else feat
 
+    def cam_entry(self):
+        """(ctypes entry, its name) of the fused gather + forward that stores fc applied at every position of the last activation
+        (cam.predict_fine_patched's launches)."""
+        name = f"{self.ABI}_cam_tiles"
+        return getattr(lib(), name), name
+
+    def cam_tiles(self, slide: torch.Tensor, origins_dev: torch.Tensor, patch: int, return_logits: bool = False):
+        """The class activation map of every tile in one launch: float32[n, S, S, n_classes], S = patch / 32, fc applied at
+        each position of the last activation (position (i, j): the 32 x 32-pixel block of the tile at (32 i, 32 j)); a tile's
+        logits are the mean over its positions.  With `return_logits` also the float32[n, n_classes] logits of forward_tiles,
+        bit for bit (without it the pooling head is not launched).  `patch` must be a multiple of 32, n_classes <= 64."""
+        patch = int(patch)
+        if patch <= 0 or patch % 32:
+            raise ValueError(f"cam_tiles: patch {patch} is not a multiple of 32 (a position is a 32 x 32-pixel block)")
+        if self.n_classes > 64:
+            raise ValueError(f"cam_tiles: {self.n_classes} classes, class activation maps take at most 64")
+        s = patch // 32
+        cam, logits = self._launch_tiles("cam_tiles", self.cam_entry, slide, origins_dev, patch, s * s * self.n_classes,
+                                         self.n_classes if return_logits else None)
+        cam = cam.view(-1, s, s, self.n_classes)
+        return (cam, logits) if return_logits else cam
+
     def forward_infer(self, x: torch.Tensor) -> torch.Tensor:
         """float32[n, 3, P, P] in [0, 1] on the GPU -> logits through the inference handle (`<ABI>_forward`): the same function as
         forward_tiles on the gathered tiles."""

@@ -387,6 +387,78 @@ def accumulate_probabilities(logits: torch.Tensor, origins_host: np.ndarray, pat
     return state
 
 
+# ---- fine maps from class activation maps -----------------------------------------------------------
+def expand_positions(origins, patch: int) -> np.ndarray:
+    """int32[n * S * S, 2], S = patch / 32: the expanded list that defines the fine accumulation.  Tile-major, positions in order
+    p = i * S + j; position (i, j) of the tile at (y, x) is the sub-tile of side 32 at (y + 32 i, x + 32 j).  `accumulate_cam`
+    over a tile list is `accumulate_logits` over this list with patch 32 and the rows of the class activation maps."""
+    patch = int(patch)
+    if patch <= 0 or patch % 32:
+        raise ValueError(f"patch {patch} is not a multiple of 32 (a position is a 32 x 32-pixel block)")
+    yx = np.asarray(origins, dtype=np.int32).reshape(-1, 2)
+    s = patch // 32
+    off = 32 * np.stack(np.meshgrid(np.arange(s, dtype=np.int32), np.arange(s, dtype=np.int32), indexing="ij"), axis=-1).reshape(-1, 2)
+    return np.ascontiguousarray((yx[:, None, :] + off[None, :, :]).reshape(-1, 2))
+
+
+def _cam_rows(cam: torch.Tensor, origins_host, patch: int):
+    """The argument checks of the fine accumulations: float32[n, S, S, n_cls] (or [n, S * S, n_cls]) rows of n tiles."""
+    _require_cuda(cam, "cam")
+    patch = int(patch)
+    if patch <= 0 or patch % 32:
+        raise ValueError(f"patch {patch} is not a multiple of 32 (a position is a 32 x 32-pixel block)")
+    s = patch // 32
+    if cam.dtype != torch.float32 or cam.dim() not in (3, 4) or int(np.prod(cam.shape[1:-1])) != s * s:
+        raise ValueError(f"cam must be float32[n, {s}, {s}, n_cls] for patch {patch}")
+    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
+    n, n_cls = int(cam.shape[0]), int(cam.shape[-1])
+    if yx.shape[0] != n:
+        raise ValueError(f"class activation maps of {n} tiles but {yx.shape[0]} origins")
+    return cam.contiguous(), yx, n, n_cls
+
+
+def accumulate_cam(cam: torch.Tensor, origins_host: np.ndarray, patch: int, downscale: int, h: int, w: int,
+                   canvas: torch.Tensor | None = None, want_map: bool = True) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """`accumulate_logits` over `expand_positions(origins_host, patch)` with patch 32 and the rows of `cam`
+    (float32[n, S, S, n_cls], `ResNetHIP.cam_tiles`), bit for bit, from the tile list's own bin plan (dh_accumulate_cam): every
+    tile adds to each cell it covers the row of the one position whose 32-pixel block owns the cell, in tile order.
+    Returns (canvas f32[dh, dw, n_cls], map int64[dh, dw])."""
+    cam, yx, n, n_cls = _cam_rows(cam, origins_host, patch)
+    dh_, dw_ = h // downscale, w // downscale
+    if canvas is None:
+        canvas = torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=cam.device)
+    else:
+        _require_cuda(canvas, "canvas")
+        if tuple(canvas.shape) != (dh_, dw_, n_cls) or canvas.dtype != torch.float32:
+            raise ValueError("canvas must be float32[h//d, w//d, n_cls]")
+    cmap = torch.empty((dh_, dw_), dtype=torch.int64, device=cam.device) if want_map else None
+    check(lib().dh_accumulate_cam(cam.data_ptr(), yx.ctypes.data_as(C.c_void_p), n, int(patch), downscale, n_cls, h, w,
+                                  canvas.data_ptr(), cmap.data_ptr() if cmap is not None else None, _stream(cam.device)),
+          "dh_accumulate_cam")
+    return canvas, cmap
+
+
+def accumulate_cam_probabilities(cam: torch.Tensor, origins_host: np.ndarray, patch: int, downscale: int, h: int, w: int,
+                                 fill_class: int = -1) -> SlideProbabilities:
+    """`accumulate_probabilities` over the expanded list (`expand_positions`, patch 32, the rows of `cam`), bit for bit: the
+    softmax of every position's scores (dh_softmax_rows over n * S * S rows), per-cell sums and hit counts in tile order
+    (dh_accumulate_cam_mean), mean, first-maximum class and confidence.  Returns a finished SlideProbabilities."""
+    cam, yx, n, n_cls = _cam_rows(cam, origins_host, patch)
+    if not 1 <= n_cls <= 64:
+        raise ValueError(f"n_cls = {n_cls}: the probability kernels take 1 to 64 classes")
+    dh_, dw_ = h // downscale, w // downscale
+    state = SlideProbabilities(torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=cam.device),
+                               torch.zeros((dh_, dw_), dtype=torch.int32, device=cam.device))
+    probs = softmax_rows(cam.view(-1, n_cls))
+    state._outputs()
+    state.fill_class = int(fill_class)
+    check(lib().dh_accumulate_cam_mean(probs.data_ptr() if n else None, yx.ctypes.data_as(C.c_void_p) if n else None, n, int(patch),
+                                       downscale, n_cls, h, w, state.proba.data_ptr(), state.count.data_ptr(),
+                                       state.class_map.data_ptr(), state.confidence.data_ptr(), int(fill_class),
+                                       _stream(cam.device)), "dh_accumulate_cam_mean")
+    return state
+
+
 def heatmap_blend(img: torch.Tensor, field: torch.Tensor, color, alpha: float = 0.6) -> torch.Tensor:
     """`(img * alpha + (float64(field)[..., None] * color) * (1 - alpha)).astype(uint8)` in float64 (dh_heatmap_blend).
     `img` uint8[h, w, 3]; `field` float32[h, w]: one class of the probabilities (`proba[..., k]`, read in place) or the

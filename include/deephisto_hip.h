@@ -311,6 +311,31 @@ int dh_resnet50_features_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64
                                const int32_t* yx_dev, int64_t n, int32_t patch, float* feat_dev,
                                float* logits_dev, void* stream);
 
+/* ---- class activation maps of the last conv: fine whole-slide maps ----------
+ * Both engines end in global average pool + fc, so a tile's logits are the mean over the positions of its last activation of
+ * fc applied at each position.  cam_tiles is forward_tiles with those per-position terms written out:
+ *   cam_dev[t][p][k] = fc_b[k] + sum_c fc_w[k][c] * a[t][p][c],  float32[n][S * S][n_classes], S = patch / 32, p = i * S + j
+ * with i along y and j along x; position (i, j) is the 32 x 32-pixel block of the tile at (32 i, 32 j).  float32 accumulation
+ * in an order fixed by the engine and n_classes alone (not by n, the tile's index or S), no atomics.  patch % 32 == 0 and
+ * n_classes <= 64, or DH_EINVAL; every argument check of the forward_tiles sibling applies as well.  logits_dev (may be NULL:
+ * the pooling head is then not launched) receives the bits forward_tiles writes.
+ * dh_accumulate_cam / dh_accumulate_cam_mean: dh_accumulate_logits / dh_accumulate_mean over the EXPANDED list, bit for bit,
+ *   without building it: the expanded list has one entry of patch size 32 per tile and position, tile-major with positions in
+ *   order p, at origin (y + 32 i, x + 32 j), with row cam_dev[t][p] (cam_mean: probs_dev[t][p], e.g. dh_softmax_rows over
+ *   the n * S * S rows).  The sub-tiles' cell ranges partition the tile's, so a tile adds exactly one position to every cell
+ *   it covers -- i = ceil(((cy + 1) d - y) / 32) - 1, likewise j -- and the order of additions in a cell is the tile order.
+ *   yx_host, n, patch: the TILE list (int32[n][2]) and tile size, patch % 32 == 0; h, w <= 2^31 - 65; everything else as in
+ *   dh_accumulate_logits / dh_accumulate_mean, whose cached bin plan these share. */
+int dh_resnet18_cam_tiles(dh_resnet18* net, const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                          int64_t n, int32_t patch, float* cam_dev, float* logits_dev, void* stream);
+int dh_resnet50_cam_tiles(dh_resnet50* net, const uint8_t* slide_dev, int64_t h, int64_t w, const int32_t* yx_dev,
+                          int64_t n, int32_t patch, float* cam_dev, float* logits_dev, void* stream);
+int dh_accumulate_cam(const float* cam_dev, const int32_t* yx_host, int64_t n, int32_t patch, int32_t downscale,
+                      int32_t n_cls, int64_t h, int64_t w, float* canvas_dev, int64_t* map_dev, void* stream);
+int dh_accumulate_cam_mean(const float* probs_dev, const int32_t* yx_host, int64_t n, int32_t patch, int32_t downscale,
+                           int32_t n_cls, int64_t h, int64_t w, float* sum_dev, int32_t* count_dev, int64_t* map_dev,
+                           float* confidence_dev, int32_t fill_class, void* stream);
+
 /* ---- e2: embedding rows: normalise, prototype scores, per-class sums -----------
  * Row-major float32 on the device, no atomics.  A row's result depends on that row alone: not on n, not on the
  * row's place in the launch, not on the grid.  D % 64 == 0 and 64 <= D <= 4096, 1 <= K <= 64; float pointers are
