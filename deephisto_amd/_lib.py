@@ -79,6 +79,8 @@ SIGNATURES = {
     "dh_embed_scatter_work_size": (_i64, [_i64, _i32]),
     "dh_embed_scatter": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _p]),
     "dh_embed_project": (C.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p]),
+    "dh_embed_knn": (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p]),
+    "dh_embed_knn_votes": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _p, _p, _p]),
     "dh_resnet18_train_begin": (C.c_int, [_p, _i64, _i32, _p]),
     "dh_resnet18_train_end": (C.c_int, [_p]),
     "dh_resnet18_forward_train": (C.c_int, [_p, _p, _i64, _i32, _p, _p]),

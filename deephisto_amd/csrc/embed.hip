@@ -8,6 +8,9 @@
 //   dh_embed_scatter      the scatter matrix of the rows about a mean: one triangle of 64 x 64 tiles, chunk
 //                         partials in a fixed order, the other triangle a mirrored store
 //   dh_embed_project      scale * (feat - mean) . comp^T: the scores tile with the subtract at staging
+//   dh_embed_knn          per query row, the k nearest rows of a bank: 64 query rows against the bank in panels
+//                         of 64 rows on packed f32 subtracts and FMAs, a sorted list of k (distance, index) pairs per row in LDS
+//   dh_embed_knn_votes    the neighbours' labels counted per class, the winner with the nearer neighbour ahead at equal counts
 // No atomics, and every reduction has one fixed order that the launch geometry cannot change: a row's result is the same bits
 // whatever n, the row's place and the grid are (the house rule of the canvas kernels).
 //
@@ -570,6 +573,181 @@ int64_t sk_batch(int64_t n, int D) {
   return b < 2 ? 0 : b;
 }
 
+// ---- dh_embed_knn ----------------------------------------------------------------------------------------
+// The order of the selection: lexicographic on (distance, index).  It is total on the pairs that may enter (finite distances,
+// distinct indices), so the k smallest are one list however the bank is walked.  A NaN compares false and never precedes anything.
+__device__ __forceinline__ bool kn_less(float d, int j, float od, int oj) { return d < od || (d == od && j < oj); }
+
+// A workgroup owns 64 query rows and walks the bank in panels of 64 rows; thread (ra = tid / 16, rb = tid % 16) holds the 4 x 4
+// distances of query rows ra + 16 i to bank rows pb + rb + 16 j of the panel, each the chain of as_dist4 over all D columns (the
+// query rows go through LDS again for every panel; they come from L2).  The query stage sits in LDS as in the scores tile
+// ([row][68]); the bank stage sits transposed, [rb][column][j] with the slabs of rb 4 banks apart, so that one ds_read_b128 hands a
+// thread column c of its four bank rows: the pairs (j = 0, 1) and (j = 2, 3) are then adjacent registers and a column costs two
+// packed subtracts and two packed fused multiply-adds per query row, the query element read from one half of its register pair.
+// A float4 step along D is 8 ds_read_b128 for 64 element pairs (the 32 x 64 tile: 6 for 32).  The arithmetic per element pair
+// is that of as_dist4, operation for operation.
+// Per query row a list of k pairs, ascending, sits in LDS.  After a panel a thread compares each of its sixteen pairs with its
+// row's k-th pair; the few that precede it are parked in s_p (free between panels) and the 16-lane group of ra learns which by a
+// ballot.  Lane rb == i of the group then inserts them into row ra + 16 i's list, checking each against the k-th pair as it now
+// stands.  The next panel's first loads are in flight during all this.  KMAX: the list's capacity (k <= KMAX), 16 or 64.
+constexpr int KN_ROWS = 64;              // query rows of a workgroup's tile
+constexpr int KN_PLD = 4 * SC_CK + 4;    // floats of one rb's slab of the transposed bank stage
+
+typedef float kn_f2 __attribute__((ext_vector_type(2)));
+
+struct KnStage { float4 f[4], p[4]; };
+__device__ __forceinline__ KnStage kn_fetch(const float* __restrict__ query, const float* __restrict__ panel, int64_t n, int D, int rows,
+                                            int64_t row0, int c0, int tid) {
+  const int r = tid >> 4, col = c0 + (tid & 15) * 4;
+  KnStage g;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    g.f[u] = sc_load(query, row0 + r + 16 * u, n - 1, D, col);
+    g.p[u] = sc_load(panel, r + 16 * u, rows - 1, D, col);
+  }
+  return g;
+}
+
+template <int KMAX>
+__global__ __launch_bounds__(256) void embed_knn_kernel(const float* __restrict__ query, int64_t n, int D,
+                                                        const float* __restrict__ bank, int64_t m, int k, int m0, int merge,
+                                                        int32_t* __restrict__ index, float* __restrict__ dist) {
+  __shared__ __attribute__((aligned(16))) float s_f[KN_ROWS * SC_LD];
+  __shared__ __attribute__((aligned(16))) float s_p[16 * KN_PLD];
+  __shared__ float s_ld[KN_ROWS * KMAX];   // row r's k distances at k r
+  __shared__ int s_li[KN_ROWS * KMAX];     // and their indices
+  const int tid = threadIdx.x, ra = tid >> 4, rb = tid & 15;
+  const int64_t row0 = (int64_t)blockIdx.x * KN_ROWS;
+  float* const s_cand = s_p;   // [64][64] distances of a panel's survivors (16 * KN_PLD >= 64 * 64)
+  for (int e = tid; e < KN_ROWS * k; e += 256) {
+    const int r = e / k;
+    float d = __builtin_inff();
+    int j = -1;
+    if (merge && row0 + r < n) {
+      d = dist[row0 * k + e];
+      j = index[row0 * k + e];
+      if (!(d < __builtin_inff())) { d = __builtin_inff(); j = -1; }   // what could not have entered counts as padding
+    }
+    s_ld[e] = d;
+    s_li[e] = j;
+  }
+  const int stages = D / SC_CK;
+  KnStage g = {};
+  if (m > 0) g = kn_fetch(query, bank, n, D, (int)std::min<int64_t>(SC_K, m), row0, 0, tid);
+  float* const st_f = &s_f[ra * SC_LD + rb * 4];      // rows ra + 16 u, columns 4 rb ..
+  float* const st_p = &s_p[ra * KN_PLD + rb * 16];    // slab of bank rows ra + 16 j, columns 4 rb ..
+  for (int64_t pb = 0; pb < m; pb += SC_K) {
+    const int rows = (int)std::min<int64_t>(SC_K, m - pb);   // bank rows of this panel
+    kn_f2 acc[4][2];   // acc[i][h] = the distances of query row ra + 16 i to bank rows rb + 16 (2 h), rb + 16 (2 h + 1)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i][0] = acc[i][1] = kn_f2{0.f, 0.f};
+    for (int s = 0; s < stages; ++s) {
+      __syncthreads();   // the previous stage's readers, and the previous panel's inserters, are done
+#pragma unroll
+      for (int u = 0; u < 4; ++u) *reinterpret_cast<float4*>(st_f + 16 * u * SC_LD) = g.f[u];
+      *reinterpret_cast<float4*>(st_p) = make_float4(g.p[0].x, g.p[1].x, g.p[2].x, g.p[3].x);
+      *reinterpret_cast<float4*>(st_p + 4) = make_float4(g.p[0].y, g.p[1].y, g.p[2].y, g.p[3].y);
+      *reinterpret_cast<float4*>(st_p + 8) = make_float4(g.p[0].z, g.p[1].z, g.p[2].z, g.p[3].z);
+      *reinterpret_cast<float4*>(st_p + 12) = make_float4(g.p[0].w, g.p[1].w, g.p[2].w, g.p[3].w);
+      __syncthreads();
+      if (s + 1 < stages) g = kn_fetch(query, bank + pb * D, n, D, rows, row0, (s + 1) * SC_CK, tid);
+      else if (pb + SC_K < m)
+        g = kn_fetch(query, bank + (pb + SC_K) * D, n, D, (int)std::min<int64_t>(SC_K, m - pb - SC_K), row0, 0, tid);
+#pragma unroll 2
+      for (int c = 0; c < SC_CK; c += 4) {
+        float4 f[4], p[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(ra + 16 * i) * SC_LD + c]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) p[u] = *reinterpret_cast<const float4*>(&s_p[rb * KN_PLD + (c + u) * 4]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float x[4] = {f[i].x, f[i].y, f[i].z, f[i].w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {   // column c + u: t = q - b (one subtract), acc = fma(t, t, acc)
+            kn_f2 t = kn_f2{x[u], x[u]} - kn_f2{p[u].x, p[u].y};
+            acc[i][0] = __builtin_elementwise_fma(t, t, acc[i][0]);
+            t = kn_f2{x[u], x[u]} - kn_f2{p[u].z, p[u].w};
+            acc[i][1] = __builtin_elementwise_fma(t, t, acc[i][1]);
+          }
+        }
+      }
+    }
+    __syncthreads();   // s_p is read out: it takes the survivors
+    const int base = m0 + (int)pb;   // m0 + m <= 2^31 - 1
+    unsigned mine[4] = {0u, 0u, 0u, 0u};   // lane rb == i keeps row ra + 16 i's masks: bit b of mine[j] = bank row pb + b + 16 j was parked
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = ra + 16 * i;
+      const float kd = s_ld[r * k + k - 1];
+      const int kj = s_li[r * k + k - 1];
+      const float dd[4] = {acc[i][0].x, acc[i][0].y, acc[i][1].x, acc[i][1].y};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int b = rb + 16 * j;
+        const float d = dd[j];
+        const bool in = b < rows && d < __builtin_inff() && kn_less(d, base + b, kd, kj);
+        if (in) s_cand[r * SC_K + b] = d;
+        const unsigned seg = (unsigned)(__ballot(in) >> (16 * (ra & 3))) & 0xffffu;
+        if (rb == i) mine[j] = seg;
+      }
+    }
+    __syncthreads();
+    if (rb < 4) {
+      const int r = ra + 16 * rb;
+      float* const ld = &s_ld[r * k];
+      int* const li = &s_li[r * k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        unsigned bits = mine[j];
+        while (bits) {
+          const int b = __builtin_ctz(bits) + 16 * j;
+          bits &= bits - 1;
+          const float d = s_cand[r * SC_K + b];
+          const int idx = base + b;
+          if (!kn_less(d, idx, ld[k - 1], li[k - 1])) continue;
+          int p = k - 1;
+          for (; p > 0 && kn_less(d, idx, ld[p - 1], li[p - 1]); --p) { ld[p] = ld[p - 1]; li[p] = li[p - 1]; }
+          ld[p] = d;
+          li[p] = idx;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < KN_ROWS * k; e += 256) {
+    if (row0 + e / k >= n) continue;
+    dist[row0 * k + e] = s_ld[e];
+    index[row0 * k + e] = s_li[e];
+  }
+}
+
+// One thread per row.  The row's counts live in its own votes row (nobody else touches it): cleared, then one increment per
+// neighbour in stored order; the label is found by a second walk in stored order that takes a class only when it has strictly
+// more votes than the best so far, so at equal votes the class met first (the nearer neighbour's) stays.
+__global__ __launch_bounds__(256) void embed_knn_votes_kernel(const int32_t* __restrict__ index, int64_t n, int k,
+                                                              const int32_t* __restrict__ bank_label, int64_t m, int C,
+                                                              int32_t* votes, int32_t* __restrict__ label) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  int32_t* const v = votes + row * C;
+  for (int c = 0; c < C; ++c) v[c] = 0;
+  for (int p = 0; p < k; ++p) {
+    const int j = index[row * k + p];
+    if (j < 0 || j >= m) continue;
+    const int c = bank_label[j];
+    if (c >= 0 && c < C) v[c] = v[c] + 1;
+  }
+  int best = 0, lab = -1;
+  for (int p = 0; p < k; ++p) {
+    const int j = index[row * k + p];
+    if (j < 0 || j >= m) continue;
+    const int c = bank_label[j];
+    if (c >= 0 && c < C && v[c] > best) { best = v[c]; lab = c; }
+  }
+  label[row] = lab;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int check_dims(const char* what, int64_t n, int32_t D, int32_t K) {
@@ -705,6 +883,48 @@ extern "C" int dh_embed_project(const float* feat, int64_t n, int32_t D, const f
   const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
   hipLaunchKernelGGL(embed_project_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, mean, comp, K, scale, out,
                      ld);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_embed_knn(const float* query, int64_t n, const float* bank, int64_t m, int32_t D, int32_t k, int64_t m0,
+                            int32_t merge, int32_t* index, float* dist, void* stream) {
+  if (int rc = check_dims("dh_embed_knn", n, D, 1)) return rc;
+  DH_REQUIRE(k >= 1 && k <= 64, "dh_embed_knn: k = %d out of range [1, 64]", k);
+  DH_REQUIRE(m >= 0, "dh_embed_knn: m = %lld is negative", (long long)m);
+  DH_REQUIRE(m0 >= 0 && m <= 0x7fffffff && m0 <= 0x7fffffff - m, "dh_embed_knn: m0 + m = %lld + %lld exceeds 2^31 - 1 (m0 >= 0)",
+             (long long)m0, (long long)m);
+  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_knn: n = %lld exceeds one launch", (long long)n);
+  if (n == 0 || (m == 0 && merge)) return DH_OK;
+  DH_REQUIRE(query && index && dist && (m == 0 || bank), "dh_embed_knn: null query_dev, bank_dev, index_dev or dist_dev");
+  DH_REQUIRE(aligned16(query) && aligned16(bank), "dh_embed_knn: query_dev / bank_dev not 16-byte aligned");
+  DH_REQUIRE((reinterpret_cast<uintptr_t>(index) & 3) == 0 && (reinterpret_cast<uintptr_t>(dist) & 3) == 0,
+             "dh_embed_knn: index_dev / dist_dev not 4-byte aligned");
+  const int64_t grid = (n + KN_ROWS - 1) / KN_ROWS;
+  hipStream_t st = dh::as_stream(stream);
+  if (k <= 16) {   // the short list leaves LDS for a third workgroup per CU
+    hipLaunchKernelGGL(embed_knn_kernel<16>, dim3((unsigned)grid), dim3(256), 0, st, query, n, D, bank, m, k, (int)m0, merge, index, dist);
+  } else {
+    hipLaunchKernelGGL(embed_knn_kernel<64>, dim3((unsigned)grid), dim3(256), 0, st, query, n, D, bank, m, k, (int)m0, merge, index, dist);
+  }
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+extern "C" int dh_embed_knn_votes(const int32_t* index, int64_t n, int32_t k, const int32_t* bank_label, int64_t m, int32_t n_classes,
+                                  int32_t* votes, int32_t* label, void* stream) {
+  DH_REQUIRE(n >= 0 && n <= (int64_t)256 * 0x7fffffff, "dh_embed_knn_votes: n = %lld out of range", (long long)n);
+  DH_REQUIRE(k >= 1 && k <= 64, "dh_embed_knn_votes: k = %d out of range [1, 64]", k);
+  DH_REQUIRE(m >= 0 && m <= 0x7fffffff, "dh_embed_knn_votes: m = %lld out of range [0, 2^31 - 1]", (long long)m);
+  DH_REQUIRE(n_classes >= 1 && n_classes <= 64, "dh_embed_knn_votes: n_classes = %d out of range [1, 64]", n_classes);
+  if (n == 0) return DH_OK;
+  DH_REQUIRE(index && votes && label && (m == 0 || bank_label),
+             "dh_embed_knn_votes: null index_dev, bank_label_dev, votes_dev or label_dev");
+  DH_REQUIRE(((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(bank_label) | reinterpret_cast<uintptr_t>(votes) |
+               reinterpret_cast<uintptr_t>(label)) & 3) == 0,
+             "dh_embed_knn_votes: index_dev / bank_label_dev / votes_dev / label_dev not 4-byte aligned");
+  hipLaunchKernelGGL(embed_knn_votes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, dh::as_stream(stream), index, n, k,
+                     bank_label, m, n_classes, votes, label);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }

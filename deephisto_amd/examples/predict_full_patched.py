@@ -14,7 +14,8 @@ ones and traces them into polygons; the CLI does so with `--regions_json`, `--mi
 the same plan, and `PrototypeClassifier` scores them against class prototypes; the CLI does so with `--save_embeddings PATH` and
 `--prototypes PATH`.  Without an annotation, `--clusters K` groups them by k-means (deephisto_amd.clustering)
 and paints the cluster map; `--pca N` fits a principal-component basis on them (deephisto_amd.pca) and
-paints the first three components as RGB.
+paints the first three components as RGB.  `--knn K --knn_bank PATH` classifies them by their nearest labelled tiles and
+`--similar_to Y,X` retrieves the tiles most like one tile (deephisto_amd.neighbours).
 `main` calls `predict_full_patched` and `predict_random_patched` through this module's globals (tests replace them here).
 """
 from __future__ import annotations
@@ -31,6 +32,7 @@ from ..anno.utils import AnnoDescription
 from ..clustering import INITS as CLUSTER_INITS, KMeans, cluster_description, cluster_map  # noqa: F401  (exported here)
 from ..cam import predict_fine_patched  # noqa: F401  (exported here)
 from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embeddings, tile_labels  # noqa: F401  (exported here)
+from ..neighbours import KNNClassifier, cap_per_class, nearest_rows, similar_tiles  # noqa: F401  (exported here)
 from ..models.patch_cls_simple.engine import ResNetHIP
 from ..models.patch_cls_simple.model import ResNet18HIP, get_model
 from ..patch_samplers.full_samplers import DevicePatch, FullImageDenseSampler
@@ -318,10 +320,19 @@ def _proba_from_args(ap, args) -> None:
 
 
 def _embeddings_from_args(ap, args) -> None:
-    """Checks --save_embeddings / --prototypes / --clusters / --pca; a bad combination is an argparse error."""
+    """Checks --save_embeddings / --prototypes / --clusters / --pca / --knn / --similar_to; a bad combination is an argparse error."""
+    if args.knn is not None and not args.knn_bank:
+        ap.error("--knn needs --knn_bank")
+    if args.knn_bank and args.knn is None:
+        ap.error("--knn_bank needs --knn")
+    if args.knn_per_class is not None and args.knn is None:
+        ap.error("--knn_per_class needs --knn")
+    if args.similar_to is None and (args.similar_k is not None or args.similar_json):
+        ap.error("--similar_k and --similar_json need --similar_to")
     for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes),
                         ("--clusters", args.clusters), ("--load_clusters", args.load_clusters),
-                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca)):
+                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca),
+                        ("--knn", args.knn is not None), ("--similar_to", args.similar_to is not None)):
         if not value:
             continue
         _dense_resident_only(ap, args, flag)
@@ -351,6 +362,49 @@ def _embeddings_from_args(ap, args) -> None:
             ap.error(f"--load_pca {args.load_pca}: no such file")
     elif args.save_pca and args.pca is None:
         ap.error("--save_pca needs --pca")
+    _knn_from_args(ap, args)
+
+
+def _knn_from_args(ap, args) -> None:
+    """Checks --knn / --knn_bank / --knn_per_class and --similar_to / --similar_k; leaves the pixel of --similar_to as a
+    (y, x) tuple in `args.similar_yx` (None without the flag)."""
+    n_cls = len(KNOWN_COLORS)
+    if args.knn is not None:
+        if not 1 <= args.knn <= 63:
+            ap.error(f"--knn must be in 1 .. 63 (leave-one-out asks for one neighbour more), not {args.knn}")
+        if args.knn_per_class is not None and not args.anno:
+            ap.error("--knn_per_class caps a fit: it needs --anno")
+        if args.knn_per_class is not None and args.knn_per_class < 1:
+            ap.error(f"--knn_per_class must be >= 1, not {args.knn_per_class}")
+        if args.clusters is not None or args.load_clusters:
+            ap.error("--knn and --clusters each hand their own map to the region flags; run them one at a time")
+        if args.min_region is not None:
+            ap.error("--min_region cleans the class map; with --knn the region flags describe the k-NN map as it is")
+        if not args.anno:
+            if not Path(args.knn_bank).is_file():
+                ap.error(f"--knn_bank {args.knn_bank}: no such file (with --anno the bank is fitted and written there)")
+            try:
+                bank = KNNClassifier.load(args.knn_bank)
+            except (ValueError, KeyError, OSError) as e:
+                ap.error(f"--knn_bank {args.knn_bank}: not a KNNClassifier file ({e!r})")
+            arch = resolve_arch(None) if args.arch == "auto" and not args.weights else args.arch
+            width = {"resnet18": 512, "resnet50": 2048}.get(arch)   # auto with a checkpoint: known once it is read (_knn_rank0)
+            if bank.n_classes != n_cls or (width is not None and bank.bank.shape[1] != width):
+                ap.error(f"--knn_bank {args.knn_bank}: {bank.n_classes} classes x {bank.bank.shape[1]} floats do not fit this model "
+                         f"and description ({n_cls} x {width or 'the model width'})")
+    args.similar_yx = None
+    if args.similar_to is not None:
+        try:
+            y, x = (int(v) for v in args.similar_to.split(","))
+        except ValueError:
+            ap.error(f"--similar_to takes Y,X (a pixel of the slide), not {args.similar_to!r}")
+        if args.synthetic is not None and not args.pyramid and not (0 <= y < args.synthetic[0] and 0 <= x < args.synthetic[1]):
+            ap.error(f"--similar_to {y},{x} lies outside the slide ({args.synthetic[0]} x {args.synthetic[1]})")
+        if min(y, x) < 0:
+            ap.error(f"--similar_to {y},{x} lies outside the slide")
+        if args.similar_k is not None and not 1 <= args.similar_k <= 63:
+            ap.error(f"--similar_k must be in 1 .. 63, not {args.similar_k}")
+        args.similar_yx = (y, x)
 
 
 def _fine_from_args(ap, args) -> None:
@@ -363,7 +417,8 @@ def _fine_from_args(ap, args) -> None:
                  "with --tta")
     for flag, value in (("--save_embeddings", args.save_embeddings), ("--prototypes", args.prototypes),
                         ("--clusters", args.clusters is not None), ("--load_clusters", args.load_clusters),
-                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca)):
+                        ("--pca", args.pca is not None), ("--load_pca", args.load_pca),
+                        ("--knn", args.knn is not None), ("--similar_to", args.similar_to is not None)):
         if value:
             ap.error(f"{flag} finishes the class map from one logits row per tile; it cannot be combined with --fine")
     if args.patch_size % 32:
@@ -460,6 +515,20 @@ def _build_parser():
     ap.add_argument("--save_pca", default=None, metavar="PATH", help="with --pca: the fitted basis as one .npz (rank 0)")
     ap.add_argument("--load_pca", default=None, metavar="PATH",
                     help="apply the basis of an earlier --save_pca to this slide instead of fitting (N comes from the file)")
+    ap.add_argument("--knn", type=int, default=None, metavar="K",
+                    help="k-nearest-neighbour classification of the tile embeddings against a bank of labelled tiles (1 .. 63, "
+                         "needs --knn_bank): writes {stem}_knn.jpg and {stem}_knn_overlay.jpg (rank 0); --regions_json / "
+                         "--export_anno then describe that map's regions")
+    ap.add_argument("--knn_bank", default=None, metavar="PATH",
+                    help="with --knn: with --anno, fit the bank on this slide's annotated tiles, write it to PATH and print the "
+                         "leave-one-out accuracy; without, load PATH")
+    ap.add_argument("--knn_per_class", type=int, default=None, metavar="N",
+                    help="with --knn and --anno: at most N tiles of a class enter the bank (every ceil(count / N)-th, in tile order)")
+    ap.add_argument("--similar_to", default=None, metavar="Y,X",
+                    help="retrieval: the tiles of this slide most like the tile under pixel Y,X, as JSON (rank 0)")
+    ap.add_argument("--similar_k", type=int, default=None, metavar="K", help="with --similar_to: how many tiles (1 .. 63, default 16)")
+    ap.add_argument("--similar_json", default=None, metavar="PATH",
+                    help="with --similar_to: where the JSON goes (default {out_dir}/{stem}_similar.json)")
     return ap
 
 
@@ -521,7 +590,7 @@ def _run(args, model, device, rank, world):
         qinfo: dict = {}
         args.embeddings = None
         if args.save_embeddings or args.prototypes or args.clusters is not None or args.load_clusters or args.pca is not None \
-                or args.load_pca:
+                or args.load_pca or args.knn is not None or args.similar_to is not None:
             # the same plan through the features entry; the map is finished from that pass's logits by predict_full_patched's tail
             filt = args.quality_filter if args.quality_filter is not None else args.tissue_filter
             emb = args.embeddings = extract_embeddings(smp, model, tissue=args.tissue_filter, tissue_info=info,
@@ -602,6 +671,55 @@ def _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device) -> None:
         _, _, overlay = perform_and_save_visualizations(src, anno_dsc, pmap, stem=stem, save=False, device=device)
         out_dir.mkdir(exist_ok=True, parents=True)
         _save_jpeg(overlay, out_dir / f"{stem}_prototype_map.jpg")
+
+
+def _knn_rank0(args, smp, src, stem, anno_dsc, out_dir, device):
+    """--knn: with --anno, fit the bank on this slide's annotated tiles (the label of a tile is the annotation's at the cell under
+    its centre, --knn_per_class caps a class), save it and print the leave-one-out accuracy; without, load it.  Either way write
+    `{stem}_knn.jpg` and `{stem}_knn_overlay.jpg` from the k-NN class map, which is returned."""
+    emb, n_cls = args.embeddings, len(anno_dsc.anno_classes)
+    if args.anno_records is not None:
+        truth, _ = rasterize_annotation(args.anno_records, anno_dsc, args.layer, smp.h, smp.w, args.downscale_vis, device=device)
+        labels = tile_labels(emb, truth, args.downscale_vis)
+        if args.knn_per_class is not None:
+            labels = cap_per_class(labels, n_cls, args.knn_per_class)
+        knn = KNNClassifier(n_cls, k=args.knn).fit(emb, labels)
+        Path(args.knn_bank).parent.mkdir(parents=True, exist_ok=True)
+        knn.save(args.knn_bank)
+        loo = f"{knn.leave_one_out()[0]:.4f}" if len(knn.bank) else "none (an empty bank)"
+        print(f"knn: k = {knn.k}, {len(knn.bank)} labelled tiles in the bank, per class {knn.counts.tolist()}, "
+              f"leave-one-out accuracy {loo} -> {args.knn_bank}", flush=True)
+    else:
+        knn = KNNClassifier.load(args.knn_bank, device=device)
+        knn.k = args.knn
+        if knn.n_classes != n_cls or knn.bank.shape[1] != emb.width:
+            raise ValueError(f"--knn_bank {args.knn_bank}: {knn.n_classes} classes x {knn.bank.shape[1]} floats do not fit this "
+                             f"model and description ({n_cls} x {emb.width})")
+    kmap = knn.predict_map(emb, args.downscale_vis)
+    if not args.no_visualizations:
+        mask, _, overlay = perform_and_save_visualizations(src, anno_dsc, kmap, stem=stem, save=False, device=device)
+        out_dir.mkdir(exist_ok=True, parents=True)
+        _save_jpeg(mask, out_dir / f"{stem}_knn.jpg")
+        _save_jpeg(overlay, out_dir / f"{stem}_knn_overlay.jpg")
+    return kmap
+
+
+def _similar_rank0(args, stem, out_dir) -> None:
+    """--similar_to Y,X: the tiles of this slide most like the tile under that pixel, nearest first, as JSON."""
+    import json
+
+    emb = args.embeddings
+    y, x = args.similar_yx
+    if not (y < emb.h and x < emb.w):
+        raise ValueError(f"--similar_to {y},{x} lies outside the slide ({emb.h} x {emb.w})")
+    res = similar_tiles(emb, (y, x), k=args.similar_k or 16)
+    doc = dict(pixel=[y, x], query_row=res["query_row"], query_origin=res["query_origin"].tolist(), patch_size=emb.patch_size,
+               k=len(res["rows"]), rows=res["rows"].tolist(), origins=res["origins"].tolist(),
+               dist=[float(d) for d in res["dist"]])
+    path = Path(args.similar_json) if args.similar_json else out_dir / f"{stem}_similar.json"
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(doc, indent=1) + "\n")
+    print(f"similar: {len(res['rows'])} tiles like the one at {doc['query_origin']} -> {path}", flush=True)
 
 
 def _clusters_rank0(args, src, stem, out_dir, device):
@@ -700,6 +818,10 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
         _prototypes_rank0(args, smp, src, stem, anno_dsc, out_dir, device)
     if args.pca is not None or args.load_pca:
         _pca_rank0(args, stem, out_dir, device)
+    if args.similar_to is not None:
+        _similar_rank0(args, stem, out_dir)
+    if args.knn is not None:
+        pred = _knn_rank0(args, smp, src, stem, anno_dsc, out_dir, device)   # the region flags below describe the k-NN map
     if args.clusters is not None or args.load_clusters:
         pred, anno_dsc = _clusters_rank0(args, src, stem, out_dir, device)   # the region flags below describe the cluster map
     if not (args.regions_json or args.min_region is not None or args.export_anno):
@@ -776,6 +898,12 @@ def main(argv=None, model=None):
     the same refusals) and writes `{stem}_pca.jpg`, the first three components of every cell's tiles as red, green and blue, and
     `{stem}_pca.json` (N, tiles, explained variance and ratios, milliseconds of scatter, eigen-solve and projection);
     `--load_pca PATH` applies a saved basis instead of fitting.
+    `--knn K --knn_bank PATH` classifies every tile by its K nearest tiles of a labelled bank (the same
+    refusals): with `--anno` the bank is this slide's annotated tiles (`--knn_per_class N` keeps at most N of a class), written
+    to PATH with the leave-one-out accuracy printed; without `--anno` PATH is loaded.  Either way `{stem}_knn.jpg` and
+    `{stem}_knn_overlay.jpg` show the class of most neighbours per cell, and `--regions_json` / `--export_anno` describe that map.
+    `--similar_to Y,X [--similar_k K] [--similar_json PATH]` writes the K tiles of this slide most like the tile under that pixel
+    (origins and squared distances of the normalised embeddings, nearest first, the tile itself left out) as JSON.
     `--fine` builds the map from the class activation maps of the last conv (`predict_fine_patched`): every
     tile's S x S per-position scores, S = patch_size / 32, go onto their own 32 x 32-pixel blocks, so the map's values change
     every 32 px instead of once per tile footprint, from the same forward pass.  The canvas shape does not move: `--proba`,

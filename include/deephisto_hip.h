@@ -368,7 +368,23 @@ int dh_accumulate_cam_mean(const float* probs_dev, const int32_t* yx_host, int64
  * dh_embed_project: out[i][j] = scale[j] * acc for j < K with ONE accumulator from 0: for c
  *   ascending acc = fma(feat[i][c] - mean[c], comp[j][c], acc) (one float32 subtract).  comp_dev float32[K][D],
  *   scale_dev float32[K] or NULL (every scale 1), out_dev float32[n][ld] with K <= ld <= 4096 and ld % 4 == 0;
- *   columns K .. ld - 1 of out_dev are not touched.  A row's result depends on that row alone. */
+ *   columns K .. ld - 1 of out_dev are not touched.  A row's result depends on that row alone.
+ * dh_embed_knn: for every row i of query_dev (float32[n][D]) the k nearest rows of bank_dev
+ *   (float32[m][D]), exactly.  For query row i and bank row j the distance is that of dh_embed_assign: ONE accumulator from
+ *   0, for c ascending t = q[c] - b[c] (one float32 subtract), acc = fma(t, t, acc).  Row i of index_dev (int32[n][k]) and
+ *   dist_dev (float32[n][k]) holds the k smallest pairs under the lexicographic order (distance, m0 + j), stored ascending:
+ *   a total order, so the result is one well-defined list however the bank is walked.  A NaN (or +inf) distance never
+ *   enters; if fewer than k candidates are finite the tail is (-1, +inf).  merge != 0: the list already in index_dev /
+ *   dist_dev (ascending, or the (-1, +inf) padding) counts as candidates too, so a bank larger than one call, or one held
+ *   in several tensors, goes through in passes with rising m0 and the result is the bits of the single call.
+ *   1 <= k <= 64; D as above; 0 <= m, 0 <= m0, m0 + m <= 2^31 - 1; both matrices 16-byte aligned, the outputs 4-byte
+ *   aligned.  n == 0 is a no-op, m == 0 without merge fills the padding, m == 0 with merge changes nothing.  No atomics;
+ *   a query row's output does not depend on n, on the row's place or on the other rows.
+ * dh_embed_knn_votes: one vote per neighbour.  Row i walks index_dev[i][0 .. k) in stored order; an index of -1, an index
+ *   outside [0, m) or a bank_label_dev (int32[m]) entry outside [0, n_classes) casts no vote.  votes_dev[i][c]
+ *   (int32[n][n_classes]) are the counts, label_dev[i] (int32[n]) the class with the most votes; at equal votes the class
+ *   whose first member comes earliest in the neighbour list (the nearer neighbour wins); -1 when nobody voted.
+ *   1 <= k <= 64, 1 <= n_classes <= 64, 0 <= m <= 2^31 - 1. */
 #define DH_EMBED_CHUNK_ROWS 1024
 int dh_embed_normalize(const float* in_dev, int64_t n, int32_t D, float* out_dev, void* stream);
 int dh_embed_scores(const float* feat_dev, int64_t n, int32_t D, const float* proto_dev, int32_t K, float scale,
@@ -383,6 +399,10 @@ int dh_embed_scatter(const float* feat_dev, int64_t n, int32_t D, const float* m
                      float* work_dev, void* stream);
 int dh_embed_project(const float* feat_dev, int64_t n, int32_t D, const float* mean_dev, const float* comp_dev,
                      int32_t K, const float* scale_dev, float* out_dev, int32_t ld, void* stream);
+int dh_embed_knn(const float* query_dev, int64_t n, const float* bank_dev, int64_t m, int32_t D, int32_t k, int64_t m0,
+                 int32_t merge, int32_t* index_dev, float* dist_dev, void* stream);
+int dh_embed_knn_votes(const int32_t* index_dev, int64_t n, int32_t k, const int32_t* bank_label_dev, int64_t m,
+                       int32_t n_classes, int32_t* votes_dev, int32_t* label_dev, void* stream);
 
 /* ---- a7: training step (float32) -------------------------------------------------------
  * Replaces, for the same network, models/patch_cls_simple/train.py:168-172:
