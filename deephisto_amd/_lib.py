@@ -53,6 +53,9 @@ SIGNATURES = {
     "dh_label_work_size": (_i64, [_i64]),
     "dh_region_stats": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "dh_clean_small_regions": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _i32, _i64, _p, _p, C.POINTER(_i64), _p]),
+    "dh_class_mask": (C.c_int, [_p, _i64, _i64, C.c_uint64, _i32, _i32, _p, _p]),
+    "dh_distance_work_size": (_i64, [_i64, _i64]),
+    "dh_distance_transform": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p]),
     "dh_resnet18_create": (C.c_int, [C.POINTER(_p), _i32, _i32]),
     "dh_resnet18_destroy": (None, [_p]),
     "dh_resnet18_set_param": (C.c_int, [_p, C.c_char_p, _p, _i64]),

@@ -16,6 +16,9 @@ the same plan, and `PrototypeClassifier` scores them against class prototypes; t
 and paints the cluster map; `--pca N` fits a principal-component basis on them (deephisto_amd.pca) and
 paints the first three components as RGB.  `--knn K --knn_bank PATH` classifies them by their nearest labelled tiles and
 `--similar_to Y,X` retrieves the tiles most like one tile (deephisto_amd.neighbours).
+`margin_bands`, `tolerant_score` and `surface_distances` (deephisto_amd.distance) rest on the exact distance
+transform of a class mask; the CLI runs them with `--margin LABEL:PX[,PX...]`, `--score_tolerance PX`, `--surface` and writes one
+report with `--distance_json PATH`.
 `main` calls `predict_full_patched` and `predict_random_patched` through this module's globals (tests replace them here).
 """
 from __future__ import annotations
@@ -29,7 +32,9 @@ import torch
 from .. import tiles
 from .._lib import DH_LAYOUT_NCHW, check  # noqa: F401  (exported here)
 from ..anno.utils import AnnoDescription
-from ..clustering import INITS as CLUSTER_INITS, KMeans, cluster_description, cluster_map  # noqa: F401  (exported here)
+from ..clustering import INITS as CLUSTER_INITS, KMeans, cluster_description, cluster_map, cluster_palette  # noqa: F401  (exported here)
+from ..distance import (SurfaceDistance, band_composition, check_edges, class_mask, close, dilate, distance_transform, erode,  # noqa: F401  (exported here)
+                        margin_bands, open_, save_distance_report, signed_distance, surface_distances, tolerant_score)
 from ..cam import predict_fine_patched  # noqa: F401  (exported here)
 from ..embeddings import PrototypeClassifier, SlideEmbeddings, extract_embeddings, tile_labels  # noqa: F401  (exported here)
 from ..neighbours import KNNClassifier, cap_per_class, nearest_rows, similar_tiles  # noqa: F401  (exported here)
@@ -435,6 +440,44 @@ def _regions_from_args(ap, args) -> None:
         ap.error(f"--clean_rounds must be >= 1, not {args.clean_rounds}")
 
 
+def _distance_from_args(ap, args) -> None:
+    """Checks --margin / --score_tolerance / --surface / --distance_json; leaves (label, edges in px) of --margin in
+    `args.margin_spec` (None without the flag).  A bad combination is an argparse error."""
+    args.margin_spec = None
+    if args.score_tolerance is not None and not args.anno:
+        ap.error("--score_tolerance needs --anno")
+    if args.surface and not args.anno:
+        ap.error("--surface needs --anno")
+    if args.score_tolerance is not None and args.score_tolerance < 0:
+        ap.error(f"--score_tolerance must be >= 0, not {args.score_tolerance}")
+    if args.distance_json and args.margin is None and args.score_tolerance is None and not args.surface:
+        ap.error("--distance_json needs --margin, --score_tolerance or --surface")
+    steps = [f for f, on in (("--margin", args.margin is not None), ("--score_tolerance", args.score_tolerance is not None),
+                             ("--surface", args.surface)) if on]
+    if steps and (args.clusters is not None or args.load_clusters):
+        ap.error(f"{steps[0]} names the classes of the description; it cannot be combined with --clusters, whose map holds clusters")
+    if args.margin is None:
+        return
+    label, sep, spelled = args.margin.partition(":")
+    if not sep or not spelled:
+        ap.error(f"--margin takes LABEL:PX[,PX...], not {args.margin!r}")
+    if label not in KNOWN_COLORS:
+        ap.error(f"--margin label must be out of {', '.join(KNOWN_COLORS)}, not {label!r}")
+    try:
+        edges = [int(v) for v in spelled.split(",")]
+    except ValueError:
+        ap.error(f"--margin takes LABEL:PX[,PX...] with integer PX, not {args.margin!r}")
+    if len(edges) == 1:
+        if edges[0] <= 0:
+            ap.error(f"--margin {args.margin}: a single PX must be > 0 (it stands for -PX,0,PX)")
+        edges = [-edges[0], 0, edges[0]]
+    try:
+        edges = check_edges(edges)
+    except ValueError:
+        ap.error(f"--margin {args.margin}: the edges must ascend strictly (and stay below 2^31 px, at most 64 bands)")
+    args.margin_spec = (label, edges)
+
+
 def _build_parser():
     import argparse
 
@@ -529,6 +572,15 @@ def _build_parser():
     ap.add_argument("--similar_k", type=int, default=None, metavar="K", help="with --similar_to: how many tiles (1 .. 63, default 16)")
     ap.add_argument("--similar_json", default=None, metavar="PATH",
                     help="with --similar_to: where the JSON goes (default {out_dir}/{stem}_similar.json)")
+    ap.add_argument("--margin", default=None, metavar="LABEL:PX[,PX...]",
+                    help="bands of distance around class LABEL, edges in layer pixels, negative inside the class (a single PX means "
+                         "-PX,0,PX): prints the classes per band and writes {stem}_margin.jpg (rank 0)")
+    ap.add_argument("--score_tolerance", type=int, default=None, metavar="PX",
+                    help="with --anno: a second score that leaves out the cells within PX layer pixels of a label change of the annotation")
+    ap.add_argument("--surface", action="store_true",
+                    help="with --anno: Hausdorff, HD95 and average symmetric surface distance of every class the annotation holds")
+    ap.add_argument("--distance_json", default=None, metavar="PATH",
+                    help="with --margin, --score_tolerance or --surface: their results as one JSON (rank 0)")
     return ap
 
 
@@ -546,6 +598,7 @@ def _check_args(ap, args, model=None) -> None:
     _proba_from_args(ap, args)
     _embeddings_from_args(ap, args)
     _fine_from_args(ap, args)
+    _distance_from_args(ap, args)
 
 
 def _run(args, model, device, rank, world):
@@ -797,7 +850,7 @@ def _pca_rank0(args, stem, out_dir, device) -> None:
 
 def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
     """What rank 0, where the map is whole, prints and writes after the prediction: the score, the JPEGs, the probability
-    files, then the regions with the cleaned map's score and JPEGs."""
+    files, then the regions with the cleaned map's score and JPEGs, then the distance steps on the map the regions describe."""
     anno_dsc, out_dir = AnnoDescription.with_known_colors(KNOWN_COLORS), Path(args.out_dir)
     src = None if args.no_visualizations else img if isinstance(img, torch.Tensor) or not smp.resident else smp.data_device
     truth = outcome = None
@@ -824,8 +877,15 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
         pred = _knn_rank0(args, smp, src, stem, anno_dsc, out_dir, device)   # the region flags below describe the k-NN map
     if args.clusters is not None or args.load_clusters:
         pred, anno_dsc = _clusters_rank0(args, src, stem, out_dir, device)   # the region flags below describe the cluster map
-    if not (args.regions_json or args.min_region is not None or args.export_anno):
-        return
+    if args.regions_json or args.min_region is not None or args.export_anno:
+        pred = _regions_rank0(args, pred, proba, smp, src, stem, anno_dsc, out_dir, device)   # the cleaned map under --min_region
+    if args.margin_spec is not None or args.score_tolerance is not None or args.surface:
+        _distance_rank0(args, pred, truth, src, stem, anno_dsc, out_dir, device)
+
+
+def _regions_rank0(args, pred, proba, smp, src, stem, anno_dsc, out_dir, device):
+    """The region flags: table, cleanup, polygons, the cleaned map's score and JPEGs.  Returns the map they describe: the
+    cleaned one under --min_region, else `pred`."""
     res = extract_regions(pred, anno_dsc, args.layer, args.downscale_vis, min_cells=args.min_region or 0,
                           rounds=args.clean_rounds or 1, polygons=bool(args.export_anno), device=device,
                           confidence=proba.confidence if proba is not None else None)
@@ -845,6 +905,43 @@ def _report_rank0(args, pred, proba, smp, img, stem, device) -> None:
         out_dir.mkdir(exist_ok=True, parents=True)
         _save_jpeg(mask, out_dir / f"{stem}_clean_mask.jpg")
         _save_jpeg(overlay, out_dir / f"{stem}_clean_overlay.jpg")
+    return res.class_map if args.min_region is not None else pred
+
+
+def _distance_rank0(args, pred, truth, src, stem, anno_dsc, out_dir, device) -> None:
+    """--margin / --score_tolerance / --surface on `pred` (the map the region flags describe) and `truth` (the annotation's label
+    map, None without --anno): prints the figures, writes `{stem}_margin.jpg` and the report of --distance_json."""
+    labels = [""] * (max(a.id for a in anno_dsc.anno_classes) + 1)
+    for a in anno_dsc.anno_classes:
+        labels[a.id] = a.label
+    d = args.downscale_vis
+    margin = tolerant = surface = None
+    if args.margin_spec is not None:
+        label, edges = args.margin_spec
+        bands = margin_bands(pred, [labels.index(label)], edges, d, device=device)
+        counts = band_composition(pred, bands, len(labels), len(edges) - 1)
+        margin = dict(label=label, edges_px=edges, class_labels=labels, counts=counts)
+        print(f"margin of {label}, edges {edges} px; cells per band of {', '.join(labels)}, no class:", flush=True)
+        for i, row in enumerate(counts.tolist()):
+            print(f"  [{edges[i]}, {edges[i + 1]}) {row}", flush=True)
+        if not args.no_visualizations:
+            dsc = AnnoDescription.with_known_colors({f"band_{i}": c for i, c in enumerate(cluster_palette(len(edges) - 1))})
+            _, _, overlay = perform_and_save_visualizations(src, dsc, bands, stem=stem, save=False, device=device)
+            out_dir.mkdir(exist_ok=True, parents=True)
+            _save_jpeg(overlay, out_dir / f"{stem}_margin.jpg")
+    if args.score_tolerance is not None:
+        score = tolerant_score(pred, truth, labels, args.score_tolerance, d, device=device)
+        tolerant = dict(tolerance_px=args.score_tolerance, score=score)
+        print(f"score without the cells within {args.score_tolerance} px of a label change:", flush=True)
+        print(score, flush=True)
+    if args.surface:
+        held = torch.bincount(truth[truth >= 0].to(torch.int64), minlength=len(labels)).cpu().tolist()
+        surface = {labels[k]: surface_distances(pred, truth, k, d, device=device) for k in range(len(labels)) if held[k] and labels[k]}
+        for lb, s in surface.items():
+            print(f"surface {lb}: hausdorff {s.hausdorff:.1f} px, hd95 {s.hd95:.1f} px, assd {s.assd:.2f} px "
+                  f"({s.n_pred} predicted, {s.n_truth} annotated boundary cells)", flush=True)
+    if args.distance_json:
+        save_distance_report(args.distance_json, d, margin=margin, tolerant=tolerant, surface=surface)
 
 
 def main(argv=None, model=None):
@@ -910,6 +1007,13 @@ def main(argv=None, model=None):
     `--heat`, `--save_proba`, `--anno`, the region flags, `--tissue`, the quality flags and `--stain` compose with it.  Dense
     branch, resident slide, `--patch_size` a multiple of 32; refused with `--tta`, `--random_sampler`, `--ondisk` and the
     embedding flags.
+    `--margin LABEL:PX[,PX...]` cuts the map into bands of distance around class LABEL (edges in layer
+    pixels, negative inside the class, a single PX meaning `-PX,0,PX`), prints the classes per band and writes `{stem}_margin.jpg`,
+    one colour per band over the slide.  With `--anno`, `--score_tolerance PX` adds a score that leaves out the cells within PX
+    of a label change of the annotation and `--surface` the Hausdorff, HD95 and average symmetric surface distance of every class
+    the annotation holds.  `--distance_json PATH` writes all three as one report (rank 0).  They run on the map the region flags
+    describe (the cleaned one under `--min_region`) and are refused with `--clusters`; every other output is that of a run
+    without them.
     `model`: an injected module (tests)."""
     from ..distributed import finalize, init_from_env
     from ..models.patch_cls_simple import utils

@@ -248,6 +248,26 @@ int dh_clean_small_regions(const int64_t* map_dev, const int32_t* labels_dev, co
                            int64_t dh, int64_t dw, int32_t n_cls, int64_t min_cells, int32_t* votes_dev, int64_t* out_map_dev,
                            int64_t* n_changed_host, void* stream);
 
+/* ---- distance maps of a class map: class masks, exact Euclidean distance transform (no counterpart in
+ * the reference) ----
+ * dh_class_mask: mask_dev uint8[dh][dw] (0 / 1) from map_dev int64[dh][dw] with values in [-1, 63].  A cell is a member when its
+ *   class k >= 0 has bit k of class_bits set, or when it is -1 and include_unclassified is not 0.  mode 0: the members.  mode 1:
+ *   the members with at least one 4-neighbour inside the canvas that is not a member (the set's boundary; the canvas edge makes
+ *   none).  mode 2: the cells with at least one 4-neighbour inside the canvas of a different value, -1 counting as a value
+ *   (every label change; class_bits and include_unclassified are ignored).  dh, dw in [1, 32767].  The entry waits for the
+ *   stream; a value outside [-1, 63] anywhere in map_dev makes it return DH_EINVAL (mask_dev is then undefined).
+ * dh_distance_transform: d2_dev int32[dh][dw] = for every cell the minimum over the feature cells (mask != 0) of dy^2 + dx^2 in
+ *   cells, exact; nearest_dev int32[dh][dw] (or NULL) = the linear index y' * dw + x' of the feature cell that attains it, the
+ *   smallest index among equals.  Without a feature cell d2 = INT32_MAX and nearest = -1 everywhere.  dh, dw in [1, 32767]
+ *   (2 * 32767^2 < 2^31).  work_dev: int32[dh_distance_work_size(dh, dw)], scratch.  Integer arithmetic only, no atomics: the
+ *   result does not depend on the launch.  Asynchronous on the stream.
+ * dh_distance_work_size: the number of int32 elements of work_dev; 0 for a canvas outside the limits. */
+int dh_class_mask(const int64_t* map_dev, int64_t dh, int64_t dw, uint64_t class_bits, int32_t include_unclassified, int32_t mode,
+                  uint8_t* mask_dev, void* stream);
+int64_t dh_distance_work_size(int64_t dh, int64_t dw);
+int dh_distance_transform(const uint8_t* mask_dev, int64_t dh, int64_t dw, int32_t* d2_dev, int32_t* nearest_dev, int32_t* work_dev,
+                          void* stream);
+
 /* ---- a6: ResNet-18 patch classifier forward ---------------------------------
  * Replaces `model(features)` for the network built by get_model
  * (models/patch_cls_simple/model.py:5-11: torchvision resnet18 + fc[n_cls,512])
