@@ -20,7 +20,7 @@ import torch
 from . import tiles
 from ._lib import check, lib
 from .anno.utils import AnnoDescription
-from .embeddings import SlideEmbeddings, _rows, _stream, class_sums, normalize_rows
+from .embeddings import SlideEmbeddings, _count, _out_buffer, _rows, _stream, class_sums, normalize_rows
 
 MAX_CLUSTERS = 64   # of dh_embed_class_sums; dh_embed_assign itself goes past it in passes (k0, merge)
 INITS = ("kmeans++", "maximin")
@@ -41,14 +41,10 @@ def nearest_centres(features: torch.Tensor, centres: torch.Tensor, out_label: to
     n = int(x.shape[0])
     if merge and (out_label is None or out_dist is None):
         raise ValueError("merge=True starts from out_label and out_dist: both must be given")
-    if out_label is None:
-        out_label = torch.empty(n, dtype=torch.int32, device=x.device)
-    if out_dist is None:
-        out_dist = torch.empty(n, dtype=torch.float32, device=x.device)
-    for t, dt, what in ((out_label, torch.int32, "out_label must be a contiguous int32[n]"),
-                        (out_dist, torch.float32, "out_dist must be a contiguous float32[n]")):
-        if t.dtype != dt or tuple(t.shape) != (n,) or t.device != x.device or not t.is_contiguous():
-            raise ValueError(f"{what} GPU tensor on the features' device")
+    out_label = _out_buffer(out_label, torch.int32, (n,), x.device,
+                            "out_label must be a contiguous int32[n] GPU tensor on the features' device")
+    out_dist = _out_buffer(out_dist, torch.float32, (n,), x.device,
+                           "out_dist must be a contiguous float32[n] GPU tensor on the features' device")
     check(lib().dh_embed_assign(x.data_ptr(), n, int(x.shape[1]), c.data_ptr(), int(c.shape[0]), int(k0), int(bool(merge)),
                                 out_label.data_ptr(), out_dist.data_ptr(), _stream(x.device)), "dh_embed_assign")
     return out_label, out_dist
@@ -100,12 +96,6 @@ def cluster_description(n_clusters: int) -> AnnoDescription:
     return AnnoDescription.with_known_colors({f"cluster_{k}": c for k, c in enumerate(cluster_palette(n_clusters))})
 
 
-def _check_k(n_clusters) -> int:
-    if not 1 <= int(n_clusters) <= MAX_CLUSTERS:
-        raise ValueError(f"n_clusters must be in [1, {MAX_CLUSTERS}], not {n_clusters}")
-    return int(n_clusters)
-
-
 # ---- k-means ------------------------------------------------------------------------------------------------------------
 class KMeans:
     """Lloyd's k-means on the device, the same bits on every run and every rank.
@@ -128,7 +118,7 @@ class KMeans:
     rank computes the same centres and labels and nothing is exchanged; one rank's share (`gather=False`) is refused."""
 
     def __init__(self, n_clusters: int, init="kmeans++", seed: int = 0, max_iter: int = 50, normalize: bool = True):
-        self.n_clusters = _check_k(n_clusters)
+        self.n_clusters = _count(n_clusters, MAX_CLUSTERS, "n_clusters")
         self._init_centres = None
         if isinstance(init, str):
             if init not in INITS:
@@ -276,7 +266,7 @@ def cluster_map(emb: SlideEmbeddings, labels, n_clusters: int, downscale: int = 
     lowest number at equal votes.  One-hot float32 rows go over the tiles' footprints like logits (`tiles.accumulate_logits`; the
     sums are small integers, hence exact), then the first maximum.  Cells no tile of `emb` covers, and cells whose tiles all have
     label -1, get `fill_class`."""
-    K = _check_k(n_clusters)
+    K = _count(n_clusters, MAX_CLUSTERS, "n_clusters")
     dev = emb.features.device
     lb = labels.to(device=dev, dtype=torch.int64) if isinstance(labels, torch.Tensor) else \
         torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int64)).to(dev)

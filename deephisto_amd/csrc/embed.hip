@@ -1,13 +1,14 @@
 // Embedding rows for MI355X (gfx950, wave64): what a prototype (nearest-class-mean) scorer needs on top of
 // the per-tile features of dh_resnet*_features_tiles.
 //   dh_embed_normalize    row / sqrt(sum row^2): one wave per row, lane sums in column order, one butterfly over the wave
-//   dh_embed_scores       scale * feat . proto^T: a skinny f32 GEMM, 32 rows x 64 prototypes per workgroup through LDS
+//   dh_embed_scores       scale * feat . proto^T: a skinny f32 GEMM, 32 rows x 64 prototypes per workgroup through LDS (sc_tile, the
+//                         one tile under this, dh_embed_assign for K > 16 and dh_embed_project)
 //   dh_embed_class_sums   per-class sums of labelled rows in a fixed chunked order + int64 counts
-//   dh_embed_assign       per row, the nearest of K centres and its squared distance: the scores tile for
-//                         K > 16, one row per lane against centres broadcast from LDS for K <= 16
+//   dh_embed_assign       per row, the nearest of K centres and its squared distance: sc_tile on a subtract-and-FMA step
+//                         for K > 16, one row per lane against centres broadcast from LDS for K <= 16
 //   dh_embed_scatter      the scatter matrix of the rows about a mean: one triangle of 64 x 64 tiles, chunk
 //                         partials in a fixed order, the other triangle a mirrored store
-//   dh_embed_project      scale * (feat - mean) . comp^T: the scores tile with the subtract at staging
+//   dh_embed_project      scale * (feat - mean) . comp^T: sc_tile with the subtract at staging
 //   dh_embed_knn          per query row, the k nearest rows of a bank: 64 query rows against the bank in panels
 //                         of 64 rows on packed f32 subtracts and FMAs, a sorted list of k (distance, index) pairs per row in LDS
 //   dh_embed_knn_votes    the neighbours' labels counted per class, the winner with the nearer neighbour ahead at equal counts
@@ -68,36 +69,57 @@ __device__ __forceinline__ ScStage sc_fetch(const float* __restrict__ feat, cons
   return g;
 }
 
-// One workgroup per 32 rows.  Thread (rt = tid / 16, kt = tid % 16) owns rows rt and rt + 16 of the tile and prototypes kt, kt + 16,
-// kt + 32, kt + 48: eight accumulators, each ONE chain of fused multiply-adds over c = 0 .. D - 1 in ascending order.  Feature and
-// prototype columns go through LDS 64 at a time; the next stage's global loads are issued before the current stage's arithmetic.
-// Rows past n and prototypes past K are zero in LDS and never stored.
-__global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restrict__ feat, int64_t n, int D,
-                                                           const float* __restrict__ proto, int K, float scale,
-                                                           float* __restrict__ scores) {
+// The 32 x 64 tile under embed_scores_kernel, embed_assign_kernel and embed_project_kernel: one workgroup per 32 rows, 256 threads.
+//   Ownership.  Thread (rt = tid / 16, kt = tid % 16) owns rows rt and rt + 16 of the tile and prototypes kt, kt + 16, kt + 32,
+//               kt + 48: eight accumulators, returned as ScAcc.
+//   One chain.  Every accumulator starts from 0 and is ONE chain of STEP over c = 0 .. D - 1 in ascending order, four columns
+//               (a float4 of the row, a float4 of the prototype) per call: acc = STEP(f, p, acc).
+//   Padding.    Rows past n and prototypes past K are loaded from the last real one (in bounds) and zeroed; the caller never stores
+//               their accumulators.
+//   Staging.    Feature and prototype columns go through LDS 64 at a time; the next stage's global loads are issued before the
+//               current stage's arithmetic.  CENTRE: mean[c] is taken off a feature element as it is parked (one float32 subtract,
+//               before any multiply), a zeroed padding row included.
+//   LDS cost.   A float4 step along D is 6 ds_read_b128 (2 rows, 4 prototypes) for 32 element pairs.
+//   SKIP_IDLE.  A thread none of whose prototypes exists (K <= 16 leaves kt >= K idle) skips the arithmetic, never a barrier.
+__device__ __forceinline__ float sc_dot4(float4 f, float4 p, float acc) {   // the step of a dot product: four fused multiply-adds
+  acc = __builtin_fmaf(f.x, p.x, acc);
+  acc = __builtin_fmaf(f.y, p.y, acc);
+  acc = __builtin_fmaf(f.z, p.z, acc);
+  return __builtin_fmaf(f.w, p.w, acc);
+}
+__device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+
+struct ScAcc { float v[2][4]; };   // v[i][j]: the accumulator of (row rt + 16 i, prototype kt + 16 j)
+template <float (*STEP)(float4, float4, float), bool CENTRE, bool SKIP_IDLE>
+__device__ __forceinline__ ScAcc sc_tile(const float* __restrict__ feat, int64_t n, int D, const float* __restrict__ proto, int K,
+                                        const float* __restrict__ mean, int64_t row0) {
   __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
   __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
   const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
-  const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
-  float acc[2][4];
+  ScAcc acc;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+    for (int j = 0; j < 4; ++j) acc.v[i][j] = 0.f;
   ScStage g = sc_fetch(feat, proto, n, D, K, row0, 0, tid);
+  float4 m = make_float4(0.f, 0.f, 0.f, 0.f);   // the mean of this thread's four columns of the stage
+  if constexpr (CENTRE) m = *reinterpret_cast<const float4*>(mean + kt * 4);
   float* const st_f = &s_f[rt * SC_LD + kt * 4];   // where this thread parks its loads: (row tid / 16 [+ 16 j], columns 4 (tid % 16) ..)
   float* const st_p = &s_p[rt * SC_LD + kt * 4];
   for (int c0 = 0; c0 < D; c0 += SC_CK) {
     __syncthreads();   // the previous stage's readers are done
-    *reinterpret_cast<float4*>(st_f) = g.f0;
-    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = g.f1;
+    *reinterpret_cast<float4*>(st_f) = CENTRE ? sub4(g.f0, m) : g.f0;
+    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = CENTRE ? sub4(g.f1, m) : g.f1;
     *reinterpret_cast<float4*>(st_p) = g.p0;
     *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
     *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
     *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
     __syncthreads();
-    if (c0 + SC_CK < D) g = sc_fetch(feat, proto, n, D, K, row0, c0 + SC_CK, tid);
-    if (kt < K) {   // a thread none of whose prototypes exists (K <= 16 leaves kt >= K idle) has nothing to add
+    if (c0 + SC_CK < D) {
+      g = sc_fetch(feat, proto, n, D, K, row0, c0 + SC_CK, tid);
+      if constexpr (CENTRE) m = *reinterpret_cast<const float4*>(mean + c0 + SC_CK + kt * 4);
+    }
+    if (!SKIP_IDLE || kt < K) {
 #pragma unroll 4
       for (int c = 0; c < SC_CK; c += 4) {
         float4 f[2], p[4];
@@ -108,17 +130,20 @@ __global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restri
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float t = acc[i][j];
-            t = __builtin_fmaf(f[i].x, p[j].x, t);
-            t = __builtin_fmaf(f[i].y, p[j].y, t);
-            t = __builtin_fmaf(f[i].z, p[j].z, t);
-            t = __builtin_fmaf(f[i].w, p[j].w, t);
-            acc[i][j] = t;
-          }
+          for (int j = 0; j < 4; ++j) acc.v[i][j] = STEP(f[i], p[j], acc.v[i][j]);
       }
     }
   }
+  return acc;
+}
+
+// scores[row][k] = scale * (feat[row] . proto[k]): the tile on sc_dot4, idle threads skipped.
+__global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restrict__ feat, int64_t n, int D,
+                                                           const float* __restrict__ proto, int K, float scale,
+                                                           float* __restrict__ scores) {
+  const int rt = threadIdx.x >> 4, kt = threadIdx.x & 15;
+  const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
+  const ScAcc acc = sc_tile<sc_dot4, false, true>(feat, n, D, proto, K, nullptr, row0);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int64_t row = row0 + rt + 16 * i;
@@ -126,7 +151,7 @@ __global__ __launch_bounds__(256) void embed_scores_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = kt + 16 * j;
-      if (k < K) scores[row * K + k] = scale * acc[i][j];
+      if (k < K) scores[row * K + k] = scale * acc.v[i][j];
     }
   }
 }
@@ -150,47 +175,14 @@ __device__ __forceinline__ void as_take(float& bd, int& bk, float d, int k) {
   if (d < bd || (d == bd && k < bk)) { bd = d; bk = k; }
 }
 
-// K > 16: the tile of embed_scores_kernel (32 rows x 64 centres, thread (rt, kt) owns rows rt, rt + 16 and centres kt + 16 j), the inner
-// step a subtract and a fused multiply-add per element pair.  Centres past K are zero in LDS and never compared.  Epilogue: the
-// thread's minimum over its (up to) four centres, a butterfly over the 16 lanes of one rt, lane kt == 0 stores.
+// K > 16: the tile on as_dist4 (32 rows x 64 centres), no thread idle.  Centres past K are never compared.  Epilogue: the thread's
+// minimum over its (up to) four centres, a butterfly over the 16 lanes of one rt, lane kt == 0 stores.
 __global__ __launch_bounds__(256) void embed_assign_kernel(const float* __restrict__ feat, int64_t n, int D,
                                                            const float* __restrict__ centre, int K, int k0, int merge,
                                                            int32_t* __restrict__ label, float* __restrict__ dist) {
-  __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
-  __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
-  const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
+  const int rt = threadIdx.x >> 4, kt = threadIdx.x & 15;
   const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
-  float acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-  ScStage g = sc_fetch(feat, centre, n, D, K, row0, 0, tid);
-  float* const st_f = &s_f[rt * SC_LD + kt * 4];
-  float* const st_p = &s_p[rt * SC_LD + kt * 4];
-  for (int c0 = 0; c0 < D; c0 += SC_CK) {
-    __syncthreads();   // the previous stage's readers are done
-    *reinterpret_cast<float4*>(st_f) = g.f0;
-    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = g.f1;
-    *reinterpret_cast<float4*>(st_p) = g.p0;
-    *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
-    *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
-    *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
-    __syncthreads();
-    if (c0 + SC_CK < D) g = sc_fetch(feat, centre, n, D, K, row0, c0 + SC_CK, tid);
-#pragma unroll 4
-    for (int c = 0; c < SC_CK; c += 4) {
-      float4 f[2], p[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(rt + 16 * i) * SC_LD + c]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const float4*>(&s_p[(kt + 16 * j) * SC_LD + c]);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = as_dist4(f[i], p[j], acc[i][j]);
-    }
-  }
+  const ScAcc acc = sc_tile<as_dist4, false, false>(feat, n, D, centre, K, nullptr, row0);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int64_t row = row0 + rt + 16 * i;
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(256) void embed_assign_kernel(const float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = kt + 16 * j;
-      if (k < K) as_take(bd, bk, acc[i][j], k0 + k);
+      if (k < K) as_take(bd, bk, acc.v[i][j], k0 + k);
     }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) {
@@ -348,59 +340,14 @@ __global__ __launch_bounds__(256) void embed_class_final_kernel(const float* __r
 }
 
 // ---- dh_embed_project ------------------------------------------------------------------------------------
-// The tile of embed_scores_kernel with the mean taken off a feature stage as it is parked in LDS (one float32 subtract per element),
-// a scale per component and an output row of ld floats of which only the first K are written.
+// out[row][k] = scale[k] * ((feat[row] - mean) . comp[k]): the tile on sc_dot4 with the mean taken off at staging, idle threads
+// skipped; an output row is ld floats of which only the first K are written.
 __global__ __launch_bounds__(256) void embed_project_kernel(const float* __restrict__ feat, int64_t n, int D,
                                                             const float* __restrict__ mean, const float* __restrict__ comp, int K,
                                                             const float* __restrict__ scale, float* __restrict__ out, int ld) {
-  __shared__ __attribute__((aligned(16))) float s_f[SC_ROWS * SC_LD];
-  __shared__ __attribute__((aligned(16))) float s_p[SC_K * SC_LD];
-  const int tid = threadIdx.x, rt = tid >> 4, kt = tid & 15;
+  const int rt = threadIdx.x >> 4, kt = threadIdx.x & 15;
   const int64_t row0 = (int64_t)blockIdx.x * SC_ROWS;
-  float acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-  ScStage g = sc_fetch(feat, comp, n, D, K, row0, 0, tid);
-  float4 m = *reinterpret_cast<const float4*>(mean + kt * 4);   // the mean of this thread's four columns of the stage
-  float* const st_f = &s_f[rt * SC_LD + kt * 4];
-  float* const st_p = &s_p[rt * SC_LD + kt * 4];
-  for (int c0 = 0; c0 < D; c0 += SC_CK) {
-    __syncthreads();   // the previous stage's readers are done
-    *reinterpret_cast<float4*>(st_f) = make_float4(g.f0.x - m.x, g.f0.y - m.y, g.f0.z - m.z, g.f0.w - m.w);
-    *reinterpret_cast<float4*>(st_f + 16 * SC_LD) = make_float4(g.f1.x - m.x, g.f1.y - m.y, g.f1.z - m.z, g.f1.w - m.w);
-    *reinterpret_cast<float4*>(st_p) = g.p0;
-    *reinterpret_cast<float4*>(st_p + 16 * SC_LD) = g.p1;
-    *reinterpret_cast<float4*>(st_p + 32 * SC_LD) = g.p2;
-    *reinterpret_cast<float4*>(st_p + 48 * SC_LD) = g.p3;
-    __syncthreads();
-    if (c0 + SC_CK < D) {
-      g = sc_fetch(feat, comp, n, D, K, row0, c0 + SC_CK, tid);
-      m = *reinterpret_cast<const float4*>(mean + c0 + SC_CK + kt * 4);
-    }
-    if (kt < K) {
-#pragma unroll 4
-      for (int c = 0; c < SC_CK; c += 4) {
-        float4 f[2], p[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) f[i] = *reinterpret_cast<const float4*>(&s_f[(rt + 16 * i) * SC_LD + c]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const float4*>(&s_p[(kt + 16 * j) * SC_LD + c]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float t = acc[i][j];
-            t = __builtin_fmaf(f[i].x, p[j].x, t);
-            t = __builtin_fmaf(f[i].y, p[j].y, t);
-            t = __builtin_fmaf(f[i].z, p[j].z, t);
-            t = __builtin_fmaf(f[i].w, p[j].w, t);
-            acc[i][j] = t;
-          }
-      }
-    }
-  }
+  const ScAcc acc = sc_tile<sc_dot4, true, true>(feat, n, D, comp, K, mean, row0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int k = kt + 16 * j;
@@ -409,7 +356,7 @@ __global__ __launch_bounds__(256) void embed_project_kernel(const float* __restr
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int64_t row = row0 + rt + 16 * i;
-      if (row < n) out[row * ld + k] = s * acc[i][j];
+      if (row < n) out[row * ld + k] = s * acc.v[i][j];
     }
   }
 }
@@ -437,7 +384,7 @@ __device__ __forceinline__ void sk_pair(int pair, int T, int& ta, int& tb) {   /
   tb = ta + pair;
 }
 __device__ __forceinline__ float4 sk_centre(float4 v, float4 m, bool live) {
-  return live ? make_float4(v.x - m.x, v.y - m.y, v.z - m.z, v.w - m.w) : make_float4(0.f, 0.f, 0.f, 0.f);
+  return live ? sub4(v, m) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(256) void embed_scatter_kernel(const float* __restrict__ feat, int64_t n, int D,
@@ -757,6 +704,13 @@ int check_dims(const char* what, int64_t n, int32_t D, int32_t K) {
   return DH_OK;
 }
 
+// The launch of a 32 x 64 tile kernel: one workgroup per SC_ROWS rows, as many as one grid dimension holds.
+int sc_grid(const char* what, int64_t n, unsigned* grid) {
+  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "%s: n = %lld exceeds one launch", what, (long long)n);
+  *grid = (unsigned)((n + SC_ROWS - 1) / SC_ROWS);
+  return DH_OK;
+}
+
 }  // namespace
 
 extern "C" int dh_embed_normalize(const float* in, int64_t n, int32_t D, float* out, void* stream) {
@@ -773,12 +727,12 @@ extern "C" int dh_embed_normalize(const float* in, int64_t n, int32_t D, float* 
 extern "C" int dh_embed_scores(const float* feat, int64_t n, int32_t D, const float* proto, int32_t K, float scale, float* scores,
                                void* stream) {
   if (int rc = check_dims("dh_embed_scores", n, D, K)) return rc;
-  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_scores: n = %lld exceeds one launch", (long long)n);
+  unsigned grid;
+  if (int rc = sc_grid("dh_embed_scores", n, &grid)) return rc;
   if (n == 0) return DH_OK;
   DH_REQUIRE(feat && proto && scores, "dh_embed_scores: null feat_dev, proto_dev or scores_dev");
   DH_REQUIRE(aligned16(feat) && aligned16(proto), "dh_embed_scores: feat_dev / proto_dev not 16-byte aligned");
-  const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
-  hipLaunchKernelGGL(embed_scores_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, proto, K, scale, scores);
+  hipLaunchKernelGGL(embed_scores_kernel, dim3(grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, proto, K, scale, scores);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -787,7 +741,8 @@ extern "C" int dh_embed_assign(const float* feat, int64_t n, int32_t D, const fl
                                int32_t* label, float* dist, void* stream) {
   if (int rc = check_dims("dh_embed_assign", n, D, K)) return rc;
   DH_REQUIRE(k0 >= 0 && k0 <= 0x7fffffff - 64, "dh_embed_assign: k0 = %d out of range [0, 2^31 - 65]", k0);
-  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_assign: n = %lld exceeds one launch", (long long)n);
+  unsigned grid;
+  if (int rc = sc_grid("dh_embed_assign", n, &grid)) return rc;
   if (n == 0) return DH_OK;
   DH_REQUIRE(feat && centres && label && dist, "dh_embed_assign: null feat_dev, centres_dev, label_dev or dist_dev");
   DH_REQUIRE(aligned16(feat) && aligned16(centres), "dh_embed_assign: feat_dev / centres_dev not 16-byte aligned");
@@ -795,11 +750,10 @@ extern "C" int dh_embed_assign(const float* feat, int64_t n, int32_t D, const fl
              "dh_embed_assign: label_dev / dist_dev not 4-byte aligned");
   hipStream_t st = dh::as_stream(stream);
   if (K <= AS_KC) {
-    const int64_t grid = (n + AS_ROWS - 1) / AS_ROWS;
-    hipLaunchKernelGGL(embed_assign_rows_kernel, dim3((unsigned)grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
+    grid = (unsigned)((n + AS_ROWS - 1) / AS_ROWS);
+    hipLaunchKernelGGL(embed_assign_rows_kernel, dim3(grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
   } else {
-    const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
-    hipLaunchKernelGGL(embed_assign_kernel, dim3((unsigned)grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
+    hipLaunchKernelGGL(embed_assign_kernel, dim3(grid), dim3(256), 0, st, feat, n, D, centres, K, k0, merge, label, dist);
   }
   DH_LAUNCH_CHECK();
   return DH_OK;
@@ -874,14 +828,14 @@ extern "C" int dh_embed_project(const float* feat, int64_t n, int32_t D, const f
                                 const float* scale, float* out, int32_t ld, void* stream) {
   if (int rc = check_dims("dh_embed_project", n, D, K)) return rc;
   DH_REQUIRE(ld >= K && ld <= 4096 && ld % 4 == 0, "dh_embed_project: ld = %d unsupported (K = %d <= ld <= 4096, ld %% 4 == 0)", ld, K);
-  DH_REQUIRE(n <= (int64_t)SC_ROWS * 0x7fffffff, "dh_embed_project: n = %lld exceeds one launch", (long long)n);
+  unsigned grid;
+  if (int rc = sc_grid("dh_embed_project", n, &grid)) return rc;
   if (n == 0) return DH_OK;
   DH_REQUIRE(feat && mean && comp && out, "dh_embed_project: null feat_dev, mean_dev, comp_dev or out_dev");
   DH_REQUIRE(aligned16(feat) && aligned16(mean) && aligned16(comp) && aligned16(out),
              "dh_embed_project: feat_dev / mean_dev / comp_dev / out_dev not 16-byte aligned");
   DH_REQUIRE((reinterpret_cast<uintptr_t>(scale) & 3) == 0, "dh_embed_project: scale_dev not 4-byte aligned");
-  const int64_t grid = (n + SC_ROWS - 1) / SC_ROWS;
-  hipLaunchKernelGGL(embed_project_kernel, dim3((unsigned)grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, mean, comp, K, scale, out,
+  hipLaunchKernelGGL(embed_project_kernel, dim3(grid), dim3(256), 0, dh::as_stream(stream), feat, n, D, mean, comp, K, scale, out,
                      ld);
   DH_LAUNCH_CHECK();
   return DH_OK;

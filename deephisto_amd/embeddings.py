@@ -37,6 +37,32 @@ def _rows(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _vector(t: torch.Tensor, D: int, x: torch.Tensor, what: str) -> torch.Tensor:
+    """`_rows` for one dimension: float32[D] on the device of the rows `x`."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != x.device:
+        raise RuntimeError(f"{what} must live in GPU memory, on the features' device (HIP kernels; no CPU fallback)")
+    if t.dtype != torch.float32 or tuple(t.shape) != (D,):
+        raise ValueError(f"{what} must be float32[{D}], not {t.dtype}{list(t.shape)}")
+    return t.contiguous()
+
+
+def _count(value, most: int, what: str) -> int:
+    """`value` as an int, a ValueError unless it lies in [1, most]."""
+    if not 1 <= int(value) <= most:
+        raise ValueError(f"{what} must be in [1, {most}], not {value}")
+    return int(value)
+
+
+def _out_buffer(t: torch.Tensor | None, dtype, shape: tuple, dev, what: str) -> torch.Tensor:
+    """The output tensor a caller passed, checked (a ValueError of text `what` unless it is contiguous, of `dtype` and `shape`,
+    on `dev`), or a new one when there is none."""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+        raise ValueError(what)
+    return t
+
+
 # ---- the three kernels ---------------------------------------------------------------------------------------------
 def normalize_rows(features: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """float32[n, D]: every row divided by its Euclidean norm (`dh_embed_normalize`); a row whose sum of squares is 0 stays zero.
@@ -228,9 +254,7 @@ class PrototypeClassifier:
     without a labelled tile (their prototype is zero, their score 0)."""
 
     def __init__(self, n_classes: int, normalize: bool = True, scale: float = 1.0):
-        if not 1 <= int(n_classes) <= 64:
-            raise ValueError(f"n_classes must be in [1, 64], not {n_classes}")
-        self.n_classes, self.normalize, self.scale = int(n_classes), bool(normalize), float(scale)
+        self.n_classes, self.normalize, self.scale = _count(n_classes, 64, "n_classes"), bool(normalize), float(scale)
         self.prototypes = None
         self.counts = None
         self.empty_classes: list[int] = []

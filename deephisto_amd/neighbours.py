@@ -19,16 +19,10 @@ import torch
 
 from . import tiles
 from ._lib import check, lib
-from .embeddings import SlideEmbeddings, _rows, _stream, normalize_rows
+from .embeddings import SlideEmbeddings, _count, _out_buffer, _rows, _stream, normalize_rows
 
 MAX_K = 64   # of dh_embed_knn
 _FORMAT = "deephisto_amd.KNNClassifier/1"
-
-
-def _check_k(k, most: int = MAX_K) -> int:
-    if not 1 <= int(k) <= most:
-        raise ValueError(f"k must be in [1, {most}], not {k}")
-    return int(k)
 
 
 def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, out_index: torch.Tensor | None = None,
@@ -43,17 +37,13 @@ def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, out_index: t
     q, b = _rows(queries, "queries"), _rows(bank, "bank")
     if b.shape[1] != q.shape[1] or b.device != q.device:
         raise ValueError(f"the bank is {tuple(b.shape)} but the queries have {q.shape[1]} columns (one device)")
-    n, k = int(q.shape[0]), _check_k(k)
+    n, k = int(q.shape[0]), _count(k, MAX_K, "k")
     if merge and (out_index is None or out_dist is None):
         raise ValueError("merge=True starts from out_index and out_dist: both must be given")
-    if out_index is None:
-        out_index = torch.empty((n, k), dtype=torch.int32, device=q.device)
-    if out_dist is None:
-        out_dist = torch.empty((n, k), dtype=torch.float32, device=q.device)
-    for t, dt, what in ((out_index, torch.int32, "out_index must be a contiguous int32[n, k]"),
-                        (out_dist, torch.float32, "out_dist must be a contiguous float32[n, k]")):
-        if t.dtype != dt or tuple(t.shape) != (n, k) or t.device != q.device or not t.is_contiguous():
-            raise ValueError(f"{what} GPU tensor on the queries' device")
+    out_index = _out_buffer(out_index, torch.int32, (n, k), q.device,
+                            "out_index must be a contiguous int32[n, k] GPU tensor on the queries' device")
+    out_dist = _out_buffer(out_dist, torch.float32, (n, k), q.device,
+                           "out_dist must be a contiguous float32[n, k] GPU tensor on the queries' device")
     check(lib().dh_embed_knn(q.data_ptr(), n, b.data_ptr(), int(b.shape[0]), int(q.shape[1]), k, int(m0), int(bool(merge)),
                              out_index.data_ptr(), out_dist.data_ptr(), _stream(q.device)), "dh_embed_knn")
     return out_index, out_dist
@@ -137,7 +127,7 @@ class KNNClassifier:
     def __init__(self, n_classes: int, k: int = 5, normalize: bool = True):
         if not 1 <= int(n_classes) <= 64:
             raise ValueError(f"n_classes must be in [1, 64], not {n_classes}")
-        self.n_classes, self.k, self.normalize = int(n_classes), _check_k(k), bool(normalize)
+        self.n_classes, self.k, self.normalize = int(n_classes), _count(k, MAX_K, "k"), bool(normalize)
         self.bank = self.labels = self.counts = None
 
     def _prepared(self, features) -> torch.Tensor:
@@ -212,7 +202,7 @@ class KNNClassifier:
         wrong and stays out of the confusion matrix."""
         if self.bank is None or len(self.bank) == 0:
             raise ValueError("leave_one_out needs a fitted bank with at least one row")
-        k1 = _check_k(self.k + 1)   # k <= 63 here
+        k1 = _count(self.k + 1, MAX_K, "k")   # k <= 63 here
         m = int(self.bank.shape[0])
         index, dist = nearest_rows(self.bank, self.bank, k1)
         index, _ = drop_self(index, dist, torch.arange(m, dtype=torch.int32, device=index.device))
@@ -275,7 +265,7 @@ def similar_tiles(emb: SlideEmbeddings, query, k: int = 16, bank: SlideEmbedding
     if src.width != emb.width:
         raise ValueError(f"the bank's rows have {src.width} columns, the query's {emb.width}")
     drop = bool(exclude_self) and own_bank
-    k = _check_k(k, MAX_K - 1 if drop else MAX_K)
+    k = _count(k, MAX_K - 1 if drop else MAX_K, "k")
     row = tile_at(emb, query)
     xn = normalize_rows(x)
     bn = xn if own_bank else normalize_rows(b.to(xn.device))

@@ -21,19 +21,11 @@ import torch
 
 from . import tiles
 from ._lib import check, lib
-from .embeddings import SlideEmbeddings, _rows, _stream, class_sums, normalize_rows
+from .embeddings import SlideEmbeddings, _count, _rows, _stream, _vector, class_sums, normalize_rows
 
 MAX_COMPONENTS = 64   # of dh_embed_project
 _FORMAT = "deephisto_amd.PCA/1"
 _TINY = float(np.finfo(np.float32).tiny)   # the least variance a whitening divides by
-
-
-def _vector(t: torch.Tensor, D: int, x: torch.Tensor, what: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != x.device:
-        raise RuntimeError(f"{what} must live in GPU memory, on the features' device (HIP kernels; no CPU fallback)")
-    if t.dtype != torch.float32 or tuple(t.shape) != (D,):
-        raise ValueError(f"{what} must be float32[{D}], not {t.dtype}{list(t.shape)}")
-    return t.contiguous()
 
 
 # ---- the two kernels ----------------------------------------------------------------------------------------------------
@@ -111,12 +103,6 @@ def colour_levels(mean: torch.Tensor, covered: torch.Tensor, lo: float, hi: floa
     return torch.where(covered, lev, torch.zeros_like(lev)).to(torch.uint8)
 
 
-def _check_k(n_components) -> int:
-    if not 1 <= int(n_components) <= MAX_COMPONENTS:
-        raise ValueError(f"n_components must be in [1, {MAX_COMPONENTS}], not {n_components}")
-    return int(n_components)
-
-
 # ---- PCA --------------------------------------------------------------------------------------------------------------------
 class PCA:
     """Principal-component analysis of embedding rows, the same bits on every run and every rank.
@@ -135,7 +121,7 @@ class PCA:
     every rank computes the same basis and nothing is exchanged; one rank's share (`gather=False`) is refused."""
 
     def __init__(self, n_components: int, whiten: bool = False, normalize: bool = False):
-        self.n_components, self.whiten, self.normalize = _check_k(n_components), bool(whiten), bool(normalize)
+        self.n_components, self.whiten, self.normalize = _count(n_components, MAX_COMPONENTS, "n_components"), bool(whiten), bool(normalize)
         self.mean_ = self.components_ = self.explained_variance_ = self.explained_variance_ratio_ = None
         self.n_samples_ = 0
         self.timings_: dict = {}
