@@ -93,3 +93,25 @@ def get_model(n_classes: int, compute_dtype: str = "f32", arch: str = "resnet18"
     if arch == "resnet50":
         return ResNet50HIP(n_classes)
     raise ValueError(f"unknown architecture {arch!r} (resnet18, resnet50)")
+
+
+ARCHS = ("resnet18", "resnet50")
+
+
+def detect_arch(state_dict) -> str:
+    """Backbone of a checkpoint from its keys: a bottleneck's third convolution (`layer1.0.conv3.weight`) means ResNet-50."""
+    return "resnet50" if "layer1.0.conv3.weight" in state_dict else "resnet18"
+
+
+def resolve_arch(arch, state_dict=None) -> str:
+    """`arch` None / "auto": read it from `state_dict` (ResNet-18 without one, as the reference); an explicit arch must match the
+    checkpoint's keys."""
+    if arch not in (None, "auto") and arch not in ARCHS:
+        raise ValueError(f"unknown architecture {arch!r} (auto, {', '.join(ARCHS)})")
+    found = detect_arch(state_dict) if state_dict is not None else None
+    if arch in (None, "auto"):
+        return found or "resnet18"
+    if found is not None and found != arch:
+        raise ValueError(f"--arch {arch} does not match the checkpoint, whose keys are those of a {found} "
+                         f"({'has' if found == 'resnet50' else 'lacks'} layer1.0.conv3.weight)")
+    return arch
