@@ -137,6 +137,7 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "dh_train2_debug_act": (C.c_int, [_p, C.c_char_p, _i32, _p, _i64, _p]),
     "dh_resnet18_train_debug_act": (C.c_int, [_p, C.c_char_p, _i32, _p, _i64, _p]),
+    "dh_train2_debug_backward_tap": (C.c_int, [_p, _p, C.c_char_p, _p, _i64, _p, _p, _p, C.POINTER(_i32), _p]),
     "dh_debug_gemm1x1_bf16": (C.c_int, [_p, _p, _p, _p, _i64] + [_i32] * 8 + [_p]),
     "dh_debug_gemm1x1_fused_bf16": (C.c_int, [_p] * 7 + [_i64] + [_i32] * 8 + [_p]),
     "dh_debug_gemm1x1_bwdsums_bf16": (C.c_int, [_p] * 10 + [_i32, _p, _i64, _i32, _i32, _p]),

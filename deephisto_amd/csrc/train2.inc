@@ -486,31 +486,48 @@ int t2_bn_fwd(dh_train2* t, T2Conv& c, const bf16_t* res, bool relu, bool traini
   return DH_OK;
 }
 
+// The route record of one BN's backward pass (dh_train2_debug_backward_tap, include/deephisto_hip_debug.h): plain host values.
+enum { T2R_RELU = 0, T2R_PREMASKED, T2R_IN_MASK, T2R_HAVE_ROWS, T2R_REDUCE, T2R_APPLY, T2R_BRANCH, T2R_ROWS, T2R_N };
+enum { T2R_REDUCE_EPILOGUE = 0, T2R_REDUCE_SLICED = 1, T2R_REDUCE_BLOCKS = 2, T2R_REDUCE_POOL = 3 };
+enum { T2R_APPLY_FOLD = 1, T2R_APPLY_FINALIZE = 2 };
+enum { T2R_BRANCH_NONE = 0, T2R_BRANCH_BLOCK_HAS_DOWNSAMPLE = 1, T2R_BRANCH_IS_DOWNSAMPLE = 2 };
+struct T2BwdTap {   // one BN, named by its conv: device float32 copies of what its backward read and wrote, and the route on the host
+  const T2Conv* c;
+  float* grad_in;   // the tensor the BN's backward read as dy
+  float* g_out;     // the masked gradient it wrote (null where it writes none)
+  int32_t* route;   // host, T2R_N values
+};
+
 // relu: 0 none (no ReLU, or dy arrives masked), 1 pattern from y_mask (the BN output was joined with an identity before the ReLU),
 // 2 pattern recomputed from Z
 // have_rows > 0: the GEMM that produced dy already left that many rows of per-tile sums in t->partial (no reduction pass)
+// route (test hook, dh_train2_debug_backward_tap; null in every step): receives which launches ran, route[T2R_REDUCE .. T2R_ROWS]
 int t2_bn_bwd(dh_train2* t, T2Conv& c, const bf16_t* dy, const bf16_t* y_mask, int relu, bf16_t* dz, bf16_t* g_out, hipStream_t st,
-              int have_rows = 0) {
+              int have_rows = 0, int32_t* route = nullptr) {
   const int C = c.cout;
   const int64_t rows = (int64_t)t->B * c.Ho * c.Wo;
   const float* gamma = t->Pm + t->slot[c.bn + ".weight"].first;
   float* dgamma = t->G + t->slot[c.bn + ".weight"].first;
   float* dbeta = t->G + t->slot[c.bn + ".bias"].first;
   int nb = have_rows;
+  if (route) route[T2R_REDUCE] = T2R_REDUCE_EPILOGUE;
   if (nb <= 0 && t2_small_map(rows, C)) {   // small map: the channel-sliced reduction, one partial row per row group
     nb = t2_cs_groups(rows, C, 32);
+    if (route) route[T2R_REDUCE] = T2R_REDUCE_SLICED;
     if (!(g_t2_abl & 64)) hipLaunchKernelGGL((bn2_cs_reduce_kernel<1>), dim3((C / CS_CH) * nb), dim3(256), 0, st, c.Z, dy, y_mask, c.bnb.mean, c.bnb.invstd, c.bnb.scale,
                        c.bnb.shift, rows, C, relu, t->partial);
     have_rows = nb;
   }
   if (nb > 0 && nb <= CS_MAX_ROWS && t2_fold_ok(t, rows, C)) {   // no finalize launch: the apply pass adds the rows itself (bn_fold.inc)
     const int nrg = t2_cs_groups(rows, C, 256);
+    if (route) { route[T2R_APPLY] = T2R_APPLY_FOLD; route[T2R_ROWS] = nb; }
     if (!(g_t2_abl & 32)) hipLaunchKernelGGL(bn2_fold_bwd_apply_kernel, dim3((C / CS_CH) * nrg), dim3(256), 0, st, dy, y_mask, c.Z, t->partial, nb, (double)rows, gamma,
                        c.bnb.mean, c.bnb.invstd, c.bnb.scale, c.bnb.shift, dgamma, dbeta, dz, g_out, rows, C, relu);
     DH_LAUNCH_CHECK();
     return DH_OK;
   }
   if (nb <= 0) nb = t2_red_blocks(rows, C);
+  if (route) { route[T2R_APPLY] = T2R_APPLY_FINALIZE; route[T2R_ROWS] = nb; if (have_rows <= 0) route[T2R_REDUCE] = T2R_REDUCE_BLOCKS; }
   if (have_rows <= 0)
     if (!(g_t2_abl & 64)) hipLaunchKernelGGL(bn2_bwd_reduce_kernel, dim3(nb), dim3(256), 0, st, c.Z, dy, y_mask, c.bnb.mean, c.bnb.invstd, c.bnb.scale, c.bnb.shift, rows, C,
                        relu, t->partial);
@@ -771,11 +788,32 @@ extern "C" int dh_train2_forward(dh_train2* t, const float* x, int64_t n, int32_
 }
 
 namespace {
+// A block whose successor's first convolution is a stride-1 1x1 GEMM without a downsample branch receives its gradient ALREADY
+// masked by its own join-ReLU (t2_backward)
+bool t2_premasked(const dh_train2* t, int bi) {
+  if (bi + 1 >= (int)t->blocks.size()) return false;
+  const BlockDesc& nx = t->blocks[bi + 1];
+  const T2Conv& c0 = t->convs[nx.conv[0]];
+  return nx.ds < 0 && c0.ks == 1 && c0.stride == 1;
+}
+
 // `fused` (single-rank training): the Adam update and the bf16 repack of a block's tensors follow that block's weight gradients on
 // the side stream, instead of one update of the whole arena after the pass (same arithmetic per element: identical parameters).
-int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamArgs* fused) {
+// `tap` (dh_train2_debug_backward_tap only, null in every step): copies of one BN's operands, enqueued between the launches below; no
+// launch of the pass, no argument of one and no buffer it uses depends on it.
+int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamArgs* fused, const T2BwdTap* tap = nullptr) {
   const int B = t->B, ncls = t->n_classes;
   int rc;
+  // the tapped BN: a float32 copy of its incoming gradient (right before its first reader, after its only writer) and the route's host
+  // values; returns where t2_bn_bwd records its launches
+  auto tap_in = [&](const T2Conv& c, const bf16_t* g, int64_t n, int relu, bool pm, bool masked, int have_rows, int branch) -> int32_t* {
+    if (!tap || tap->c != &c) return nullptr;
+    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, g, tap->grad_in, n);
+    int32_t* r = tap->route;
+    r[T2R_RELU] = relu; r[T2R_PREMASKED] = pm; r[T2R_IN_MASK] = masked; r[T2R_HAVE_ROWS] = have_rows; r[T2R_BRANCH] = branch;
+    r[T2R_REDUCE] = r[T2R_APPLY] = r[T2R_ROWS] = 0;
+    return r;
+  };
   store_begin_backward(*t);
   auto mark_done = [&]() { store_mark_done(*t); };
   const T2Conv& lastc = t->convs[t->blocks.back().conv[t->blocks.back().nconv - 1]];
@@ -830,12 +868,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   // A block whose successor's first convolution is a stride-1 1x1 GEMM without a downsample branch receives its gradient ALREADY
   // masked by its own join-ReLU: that GEMM's dgrad epilogue computes (W^T dZ + identity gradient) * (block output > 0).  Its top
   // BN backward then reads neither the block output nor writes the masked copy: the incoming tensor IS the identity gradient.
-  auto premasked = [&](int bi) {
-    if (bi + 1 >= (int)t->blocks.size()) return false;
-    const BlockDesc& nx = t->blocks[bi + 1];
-    const T2Conv& c0 = t->convs[nx.conv[0]];
-    return nx.ds < 0 && c0.ks == 1 && c0.stride == 1;
-  };
+  auto premasked = [&](int bi) { return t2_premasked(t, bi); };
   for (int bi = (int)t->blocks.size() - 1; bi >= 0; --bi) {
     const BlockDesc& b = t->blocks[bi];
     const bf16_t* Xin = bi == 0 ? t->X1 : t->convs[t->blocks[bi - 1].conv[t->blocks[bi - 1].nconv - 1]].Y;
@@ -854,8 +887,13 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
       const bool top = i == b.nconv - 1;
       // top conv of the block: its BN output was joined with the identity and ReLU'd; the masked gradient also feeds the identity branch
       next_dz(c);
-      if (top && pm) { if ((rc = t2_bn_bwd(t, c, grad, nullptr, 0, dZ, nullptr, st, rows))) return rc; }
-      else if ((rc = t2_bn_bwd(t, c, grad, c.Y, top ? 1 : 2, dZ, top ? Gm : nullptr, st, top ? 0 : rows))) return rc;
+      const int64_t n_c = (int64_t)B * c.Ho * c.Wo * c.cout;
+      const int bn_rows = top && !pm ? 0 : rows;
+      int32_t* route = tap_in(c, grad, n_c, top ? (pm ? 0 : 1) : 2, pm, in_mask && b.ds < 0, bn_rows,
+                              b.ds >= 0 ? T2R_BRANCH_BLOCK_HAS_DOWNSAMPLE : T2R_BRANCH_NONE);
+      if (top && pm) { if ((rc = t2_bn_bwd(t, c, grad, nullptr, 0, dZ, nullptr, st, rows, route))) return rc; }
+      else if ((rc = t2_bn_bwd(t, c, grad, c.Y, top ? 1 : 2, dZ, top ? Gm : nullptr, st, top ? 0 : rows, route))) return rc;
+      if (route && top && !pm && tap->g_out) hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n_c)), dim3(256), 0, st, Gm, tap->g_out, n_c);
       rows = 0;
       const bf16_t* xin = i == 0 ? Xin : t->convs[b.conv[i - 1]].Y;
       if ((rc = wgrad_of(c, xin))) return rc;
@@ -873,7 +911,8 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
     if (b.ds >= 0) {
       T2Conv& d = t->convs[b.ds];
       next_dz(d);
-      if ((rc = t2_bn_bwd(t, d, gm, nullptr, 0, dZ, nullptr, st))) return rc;
+      int32_t* route = tap_in(d, gm, (int64_t)B * d.Ho * d.Wo * d.cout, 0, pm, false, 0, T2R_BRANCH_IS_DOWNSAMPLE);
+      if ((rc = t2_bn_bwd(t, d, gm, nullptr, 0, dZ, nullptr, st, 0, route))) return rc;
       if ((rc = wgrad_of(d, Xin))) return rc;
       if ((rc = t2_conv_dgrad(t, d, dZ, nullptr, dX, scr, true, st))) return rc;
       if (bucket_due() && (rc = join_side())) return rc;
@@ -885,6 +924,16 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   {   // stem: maxpool backward, BN + ReLU backward, weight gradient (f32 MFMA on the f32 input image)
     T2Conv& c = t->convs[0];
     dZ = t->GB[2];
+    const int Hp = (c.Ho + 2 - 3) / 2 + 1, Wp = (c.Wo + 2 - 3) / 2 + 1;
+    if (int32_t* route = tap_in(c, dOut, (int64_t)B * Hp * Wp * c.cout, 2, false, false, 0, T2R_BRANCH_NONE)) {
+      route[T2R_REDUCE] = T2R_REDUCE_POOL; route[T2R_APPLY] = T2R_APPLY_FINALIZE;
+      route[T2R_ROWS] = t2_red_blocks((int64_t)B * ((c.Ho + 1) / 2) * ((c.Wo + 1) / 2), 4 * c.cout);
+    }
+    // The stem's tail runs ALONE: next to the side stream's weight gradients of layer 1 the column sums of bn2_pool_bwd_reduce_kernel were
+    // not reproducible (ResNet-50, P = 96, B = 32: 8 to 39 of 39 identical steps differed in one to six channels of dgamma / dbeta by up to
+    // 3 % of the largest, operands bit-identical; none without the side stream: tests/test_gpu_step_bwd.py, FOUND).  Nothing is handed to
+    // the side stream after this point, so the join that the optimiser needs anyway moves in front of the tail.
+    if ((rc = join_side())) return rc;
     if ((rc = t2_bn_pool_bwd(t, c, dOut, t->pool_idx, dZ, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
     const int total_rows = B * c.Ho;
     const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
@@ -893,8 +942,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
     hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, t->stem_slabs, n_slabs,
                        t->G + t->slot["conv1.weight"].first);
     DH_LAUNCH_CHECK();
-    if ((rc = join_side())) return rc;   // the optimiser (and the last bucket) follow on the main stream
-    mark_done();
+    mark_done();   // the optimiser (and the last bucket) follow on the main stream, behind the join above
     if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
       if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, t->n_params - adam_off, st);
       if ((rc = adam_off == 0 ? t2_pack(t, st) : t2_pack(t, st, 0, 1))) return rc;
@@ -959,6 +1007,38 @@ extern "C" int dh_train2_debug_act(dh_train2* t, const char* conv_name, int32_t 
       return DH_OK;
     }
   dh::set_error("train2 debug: unknown conv_name '%s'", conv_name);
+  return DH_EINVAL;
+}
+
+// Test hook: dh_train2_backward with one BN's backward operands copied out (include/deephisto_hip_debug.h).  The same t2_backward, the
+// same launches in the same order; the copies read buffers of the pass between their writer and their next writer, on the same stream.
+extern "C" int dh_train2_debug_backward_tap(dh_train2* t, const float* dlogits, const char* conv_name, float* grad_in_dev, int64_t n_elem,
+                                            float* g_out_dev, float* mean_dev, float* invstd_dev, int32_t* route_host, void* stream) {
+  DH_REQUIRE(t && dlogits && conv_name && grad_in_dev && mean_dev && invstd_dev && route_host, "train2 backward tap: null argument");
+  DH_REQUIRE(t->B > 0 && t->last_training && !t->bwd_done,
+             "train2 backward tap: no training forward has run since the last backward (every tapped backward follows a forward of its own)");
+  hipStream_t st = dh::as_stream(stream);
+  for (size_t ci = 0; ci < t->convs.size(); ++ci) {
+    const T2Conv& c = t->convs[ci];
+    if (c.name != conv_name) continue;
+    const int Hp = (c.Ho + 2 - 3) / 2 + 1, Wp = (c.Wo + 2 - 3) / 2 + 1;
+    const int64_t n = ci == 0 ? (int64_t)t->B * Hp * Wp * c.cout : (int64_t)t->B * c.Ho * c.Wo * c.cout;
+    DH_REQUIRE(n == n_elem, "train2 backward tap: n_elem = %lld, grad_in of '%s' has %lld elements", (long long)n_elem, conv_name, (long long)n);
+    bool writes_g_out = false;   // the top BN of a block that is not pre-masked
+    for (int bi = 0; bi < (int)t->blocks.size(); ++bi) {
+      const BlockDesc& b = t->blocks[bi];
+      if (b.conv[b.nconv - 1] == (int)ci) writes_g_out = !t2_premasked(t, bi);
+    }
+    DH_REQUIRE(!g_out_dev || writes_g_out, "train2 backward tap: g_out_dev given, but the BN of '%s' writes no masked gradient (pass NULL)", conv_name);
+    const T2BwdTap tap{&c, grad_in_dev, g_out_dev, route_host};
+    for (int i = 0; i < T2R_N; ++i) route_host[i] = -1;
+    int rc = t2_backward(t, dlogits, st, nullptr, &tap);
+    if (rc) return rc;
+    DH_HIP(hipMemcpyAsync(mean_dev, c.bnb.mean, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DH_HIP(hipMemcpyAsync(invstd_dev, c.bnb.invstd, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return DH_OK;
+  }
+  dh::set_error("train2 backward tap: unknown conv_name '%s'", conv_name);
   return DH_EINVAL;
 }
 

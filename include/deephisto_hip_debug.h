@@ -28,6 +28,29 @@ extern "C" {
 int dh_train2_debug_act(dh_train2* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream);
 int dh_resnet18_train_debug_act(dh_resnet18* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream);
 
+/* dh_train2_debug_backward_tap: dh_train2_backward (same dlogits, no fused Adam, the side stream as configured; the same host code with the
+ * same launches in the same order) that also copies out, stream-ordered, what the backward of ONE batch norm -- named by its conv, as above --
+ * read and wrote, each copy enqueued after the tensor's writer and before the buffer's next writer:
+ *   grad_in_dev  float32[n_elem]: the tensor that BN's backward read as dy, [B][Ho][Wo][cout]: dOut for a block's top conv, dY for the others,
+ *                the identity gradient for a downsample BN; for "conv1" the POOLED gradient [B][Hp][Wp][64] (the stem never materialises dY)
+ *   g_out_dev    float32[n_elem]: the masked gradient that BN wrote.  Only the top BN of a block that is not pre-masked writes one: NULL for
+ *                every other BN, a non-NULL pointer there is refused; NULL is accepted everywhere
+ *   mean_dev, invstd_dev  float32[cout]: the saved forward statistics the backward kernels read
+ *   route_host   int32[8], plain host values, complete when the call returns:
+ *                [0] ReLU mode: 0 none / dy arrives masked, 1 pattern of the stored Y, 2 recomputed from Z
+ *                [1] 1: the BN's block is pre-masked (its successor's dgrad GEMM masked the block's incoming gradient)
+ *                [2] 1: the dgrad of the block's first conv masked its output with the predecessor's ReLU pattern (in_mask)
+ *                [3] have_rows as passed in: rows of BN-backward sums a 1x1 dgrad GEMM's epilogue left for this BN (0: own reduction)
+ *                [4] the reduction that ran: 0 none (epilogue sums), 1 channel-sliced, 2 bn2_bwd_reduce_kernel, 3 the stem's pool reduction
+ *                [5] 1 fold (bn2_fold_bwd_apply_kernel), 2 finalize launch + apply pass
+ *                [6] 0 a block without a downsample branch (or the stem), 1 a conv of a block with one, 2 the downsample BN itself
+ *                [7] partial rows the finalize / fold read
+ * Refused with DH_EINVAL (dh_last_error names the argument): a null argument other than g_out_dev / stream, an unknown conv_name, n_elem
+ * other than grad_in's size, g_out_dev where no masked gradient is written, and no training forward since the last backward: a tapped
+ * backward follows a forward of its own (after a backward the engine's state is that of a finished step; tests re-run the forward). */
+int dh_train2_debug_backward_tap(dh_train2* net, const float* dlogits_dev, const char* conv_name, float* grad_in_dev, int64_t n_elem,
+                                 float* g_out_dev, float* mean_dev, float* invstd_dev, int32_t* route_host, void* stream);
+
 /* test hooks of the engine's GEMM-shaped kernels on caller data (bf16 bits as uint16; synchronise; `repeat` launches for timing):
  * gemm1x1: out[M][N] = A[rows][K] . W[N][K]^T (+ res), stride 2 = row gather (b, 2 oy, 2 ox) from [B][Hi][Wi][K];
  * wgrad:   float32 dW[cout][cin][ks][ks] from x [B][Hi][Wi][cin] and dz [B][Ho][Wo][cout] (ks 1 or 3). */

@@ -380,6 +380,17 @@ def judge_pool(c: PoolCase, o: PoolOperands, out: dict) -> Report:
         w = np.argwhere(wrong)
         rep.fail(f"pool: {len(w)} decided windows differ in value or position; first (image, oy, ox, channel): got value / position, want\n" +
                  "\n".join(f"  {tuple(int(v) for v in t)}: {got[tuple(t)]!r} / {int(idx[tuple(t)])}, {want[tuple(t)]!r} / {int(pos[tuple(t)])}" for t in w[:8]))
+    pool_backward_gates(rep, c, o, out, pre, A, pos, und)
+    return rep
+
+
+def pool_backward_gates(rep: Report, c: PoolCase, o: PoolOperands, out: dict, pre, A, pos, und):
+    """The backward half of judge_pool (also the stem tail of a whole step, oracle/step_bwd_ref.py): dz, dgamma, dbeta of `out` against the
+    pooled gradient o.dpool scattered to the reference's positions `pos`; `und`: the undecided windows."""
+    B, H, C, Hp = c.B, c.H, c.C, c.Hp
+    n = B * H * H
+    imgs = np.arange(B)
+    mean, invstd = out["mean"], out["invstd"]
     # backward: the pooled gradient scattered to the REFERENCE's positions, masked by pre > 0
     dY, T = br.pool_scatter(o.dpool, pos, H, H), br.pool_scatter(o.dpool, pos, H, H, absolute=True)
     on = pre > 0

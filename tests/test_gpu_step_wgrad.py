@@ -40,10 +40,10 @@ Measured on an MI355X (records only, no threshold is derived from them; every el
                                     0.047 layer4.0.conv2 | 0.051 layer4.1.conv2 (float32: mean 0.089 / 0.091 over the layers)
 The worst ratios sit on the smallest maps, where gamma_K A is small next to the float32 unit of `want`.
 
-Out of scope here, the next slices: dgamma / dbeta and the dZ chain (a BN's incoming gradient is not kept after backward, and dZ, the
-projection of the masked gradient orthogonal to 1 and xhat, does not determine the two sums: that needs a retained dY or an interval
-reference through the bf16 rounding of the dgrad output); training-mode Y from Z with batch statistics (the coefficient error needs the
-chain-length bounds of oracle/bn_state_ref.py carried into scale and shift); the fc gradients (tests/test_gpu_head.py).
+Out of scope here, the next slices: training-mode Y from Z with batch statistics (the coefficient error needs the chain-length bounds of
+oracle/bn_state_ref.py carried into scale and shift); the float32 engine's backward chain (dgamma / dbeta and the dZ chain of tr_backward:
+the bf16 engine's are held by tests/test_gpu_step_bwd.py, which taps each BN's incoming gradient during the pass).  The fc gradients:
+tests/test_gpu_head.py.
 """
 import functools
 
