@@ -1440,7 +1440,7 @@ extern "C" int dh_resnet18_cam_tiles(dh_resnet18* net, const uint8_t* slide, int
 }
 
 // ---------------------------------------------------------------------------
-// Test hooks (declared in include/deephisto_hip.h under "debug"): run one conv
+// Test hooks (declared in include/deephisto_hip_debug.h): run one conv
 // layer on caller-provided NHWC data, and read back the stem activation of the
 // last forward.  They exist so the GPU parity tests can localise an error to a
 // kernel; the product path never calls them.
@@ -1610,5 +1610,6 @@ extern "C" int dh_debug_stem_strip_width(int32_t pc) {
 #include "bn_fold.inc"
 #include "gemm1x1.inc"
 #include "train2.inc"
+#include "train_hooks.inc"
 #include "gemm1x1_infer.inc"
 #include "resnet50_infer.inc"

@@ -1,6 +1,7 @@
 // train.inc -- training step of the ResNet-18 patch classifier (SURVEY row a7), float32.
 // Included at the end of resnet_kernels.hip (same translation unit: reuses the conv kernels), behind train_core.inc (the parameter
-// store, buckets, Adam launch and side-stream hand-off shared with the bf16 engine).
+// store, buckets, Adam launch and side-stream hand-off shared with the bf16 engine).  The file ends with its last product entry
+// point: the test hooks over this code are train_hooks.inc's, declared in include/deephisto_hip_debug.h.
 //
 // Replaces, for the network of models/patch_cls_simple/model.py:5-11, the work of
 //   outputs = model(inputs); loss = criterion(outputs, labels); loss.backward(); optimizer.step()
@@ -1234,7 +1235,7 @@ int tr_pack_all(dh_resnet18* net, hipStream_t st) {
   return rc ? rc : tr_pack(net, st, 1, (int)net->convs.size());
 }
 
-// The launch helpers below take what they use (no engine handle), so the test hooks at the end of this file run the very code of a step.
+// The launch helpers below take what they use (no engine handle), so the test hooks (train_hooks.inc) run the very code of a step.
 // `ones` / `zeros`: per-channel unit scale and zero shift (at least `cout` floats) of the inference kernels' epilogue.
 struct UnitAffine { const float *ones, *zeros; };
 
@@ -1338,6 +1339,20 @@ int tr_bn_pool_backward(const BnView& v, const float* dpool, const uint8_t* pool
                      v.bn.mean, v.bn.invstd, v.dgamma, v.dbeta, v.bn.k0, v.bn.k1, v.bn.k2);
   hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(grid_for(blocks4 * C / 4)), dim3(256), 0, st, v.Z, dpool, pool_idx, v.bn.k0, v.bn.k1,
                      v.bn.k2, v.bn.scale, v.bn.shift, dz, v.B, v.Ho, v.Wo, C, Hp, Wp);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// The stem's dW [64][3][7][7] (`dw`) from dz [B][Ho][Wo][64] and the NCHW image x [B][3][P][P]: per-slab partial sums over at most
+// STEM_WGRAD_SLABS runs of output rows (`slabs`: STEM_WGRAD_SLABS * 64 * 160 floats), then their fixed-order reduction.
+int tr_stem_wgrad(const float* dz, const float* x, float* slabs, float* dw, int B, int P, int Ho, int Wo, hipStream_t st) {
+  const int total_rows = B * Ho;
+  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
+  const int n_slabs = (total_rows + rpb - 1) / rpb;
+  const size_t lds = std::max<size_t>((size_t)21 * (P + 6) + (size_t)Wo * 64, (size_t)64 * 160) * sizeof(float);
+  DH_REQUIRE(lds <= 64 * 1024 && Wo * 16 <= 4 * SWG_T && P + 6 <= SWG_T, "stem wgrad: patch %d too wide for the row staging", P);
+  hipLaunchKernelGGL((stem_wgrad_kernel<float>), dim3(n_slabs), dim3(SWG_T), lds, st, dz, x, slabs, B, P, Ho, Wo, rpb);
+  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -1683,15 +1698,7 @@ int tr_backward(dh_resnet18* net, const float* dlogits, hipStream_t st, const Ad
     TrainConv& tc = t->tc[0];
     float* dZ0 = t->BIG1;
     if ((rc = tr_bn_pool_backward(tr_bn_view(net, 0), dOut, t->pool_idx, dZ0, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
-    const int total_rows = B * tc.Ho;
-    const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
-    const int n_slabs = (total_rows + rpb - 1) / rpb;
-    const size_t lds = std::max<size_t>((size_t)21 * (t->P + 6) + (size_t)tc.Wo * 64, (size_t)64 * 160) * sizeof(float);
-    DH_REQUIRE(lds <= 64 * 1024 && tc.Wo * 16 <= 4 * SWG_T && t->P + 6 <= SWG_T, "stem wgrad: patch %d too wide for the row staging", t->P);
-    hipLaunchKernelGGL((stem_wgrad_kernel<float>), dim3(n_slabs), dim3(SWG_T), lds, st, dZ0, t->x_in, t->stem_slabs, B, t->P, tc.Ho, tc.Wo, rpb);
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, t->stem_slabs, n_slabs,
-                       t->G + t->slot["conv1.weight"].first);
-    DH_LAUNCH_CHECK();
+    if ((rc = tr_stem_wgrad(dZ0, t->x_in, t->stem_slabs, t->G + t->slot["conv1.weight"].first, B, t->P, tc.Ho, tc.Wo, st))) return rc;
     if ((rc = join_side())) return rc;   // the optimiser (and the last bucket) follow on the main stream
     store_mark_done(*t);   // the stem
     if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
@@ -1766,230 +1773,4 @@ extern "C" int dh_resnet18_train_flat(dh_resnet18* net, int32_t kind, void** ptr
   DH_REQUIRE(net && net->train && ptr_out && n_out && kind >= 0 && kind <= 2, "train flat: bad arguments / no training state");
   store_flat(*net->train, kind, ptr_out, n_out);
   return DH_OK;
-}
-
-// Test hook: float32 copy of a tensor the last training forward / backward left in memory (dh_train2_debug_act of the float32 engine):
-// what = 0 Z, 1 Y, 2 dZ of conv `conv_name` (dZ as the weight-gradient kernel read it; the stem's lives in BIG1, which nothing else
-// uses), 3 the pooled block input X1 (under "conv1").  Read-only: the stem's Y, which the engine never stores, is refused.
-extern "C" int dh_resnet18_train_debug_act(dh_resnet18* net, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream) {
-  DH_REQUIRE(net && net->train && conv_name && out_dev && net->train->B > 0 && net->train->x_in, "train debug: bad arguments / no training forward");
-  DH_REQUIRE(what >= 0 && what <= 3, "train debug: what = %d (0 Z, 1 Y, 2 dZ, 3 X1)", what);
-  const dh_train* t = net->train;
-  for (size_t i = 0; i < net->convs.size(); ++i)
-    if (net->convs[i].name == conv_name) {
-      const TrainConv& tc = t->tc[i];
-      DH_REQUIRE(what != 3 || i == 0, "train debug: what = 3 (X1, the pooled block input) goes with 'conv1', not '%s'", conv_name);
-      DH_REQUIRE(what != 1 || i != 0, "train debug: what = 1 (Y) of 'conv1' is not kept (the stem pools in its BN pass: what = 3)");
-      const int H2 = (tc.Ho + 2 - 3) / 2 + 1;
-      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * tc.Ho * tc.Wo * net->convs[i].cout;
-      DH_REQUIRE(n == n_elem, "train debug: n_elem = %lld, '%s' (what = %d) has %lld elements", (long long)n_elem, conv_name, what, (long long)n);
-      if (what == 2) {
-        DH_REQUIRE(t->side != nullptr, "train debug: what = 2 (dZ) needs the per-convolution dZ buffers of the side-stream engine (created with DH_T1_SIDE=0)");
-        DH_REQUIRE(t->bwd_done, "train debug: what = 2 (dZ): no backward has run since the last forward");
-      }
-      const float* src = what == 0 ? tc.Z : what == 1 ? tc.Y : what == 3 ? t->X1 : i == 0 ? t->BIG1 : tc.dZ;
-      DH_HIP(hipMemcpyAsync(out_dev, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, dh::as_stream(stream)));
-      return DH_OK;
-    }
-  dh::set_error("train debug: unknown conv_name '%s'", conv_name);
-  return DH_EINVAL;
-}
-
-// =====================================================================================
-// Test hooks of the float32 training kernels (declared under "debug" in include/deephisto_hip.h): each runs ONE backward
-// building block on caller data exactly as dh_resnet18_backward launches it, so the GPU parity tests can hold every
-// kernel against torch autograd on its own instead of through the whole network.  They allocate their own scratch and
-// synchronise; the product path never calls them.
-// =====================================================================================
-namespace {
-struct DbgScratch {
-  std::vector<void*> a;
-  ~DbgScratch() { for (void* p : a) (void)hipFree(p); }
-  template <typename V> int get(V** p, int64_t n) { DH_HIP(hipMalloc((void**)p, (size_t)std::max<int64_t>(n, 1) * sizeof(V))); a.push_back(*p); return DH_OK; }
-};
-int dbg_finish(hipStream_t st, const char* what) {
-  hipError_t e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { dh::set_error("%s: %s", what, hipGetErrorString(e)); return DH_EHIP; }
-  return DH_OK;
-}
-}  // namespace
-
-// dW[cout][cin][ks][ks] of a conv (ks 1 or 3, pad ks/2) from NHWC x and dz; mode 0 = the path backward takes, 1 = force the per-tap kernel
-extern "C" int dh_debug_wgrad_f32(const float* dz_dev, const float* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi, int32_t cin,
-                                  int32_t cout, int32_t ks, int32_t stride, int32_t mode, void* stream) {
-  DH_REQUIRE(dz_dev && x_dev && dw_dev && (ks == 1 || ks == 3) && cin % 64 == 0 && cout % 64 == 0, "debug wgrad: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  float* slabs;
-  int rc = sc.get(&slabs, (int64_t)WGRAD3_WGS * 9 * 64 * 64);
-  if (rc) return rc;
-  ConvLayer c{{"dbg", "dbg", cin, cout, ks, stride}};
-  TrainConv tc;
-  tc.Hi = Hi; tc.Wi = Wi; tc.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; tc.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  if ((rc = tr_wgrad(slabs, dw_dev, c, tc, x_dev, dz_dev, B, st, mode == 1))) return rc;
-  return dbg_finish(st, "debug wgrad");
-}
-
-// stem: dW[64][3][7][7] from dz NHWC [B][P/2][P/2][64] and the NCHW input image
-extern "C" int dh_debug_stem_wgrad_f32(const float* dz_dev, const float* x_nchw_dev, float* dw_dev, int32_t B, int32_t P, void* stream) {
-  DH_REQUIRE(dz_dev && x_nchw_dev && dw_dev && B > 0 && P >= 32 && P % 2 == 0, "debug stem wgrad: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  float* slabs;
-  int rc = sc.get(&slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160);
-  if (rc) return rc;
-  const int Ho = P / 2, total_rows = B * Ho;
-  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS, n_slabs = (total_rows + rpb - 1) / rpb;
-  const size_t lds = std::max<size_t>((size_t)21 * (P + 6) + (size_t)Ho * 64, (size_t)64 * 160) * sizeof(float);
-  DH_REQUIRE(lds <= 64 * 1024 && Ho * 16 <= 8 * 256 && P + 6 <= SWG_T, "debug stem wgrad: patch %d too wide", P);
-  hipLaunchKernelGGL((stem_wgrad_kernel<float>), dim3(n_slabs), dim3(SWG_T), lds, st, dz_dev, x_nchw_dev, slabs, B, P, Ho, Ho, rpb);
-  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw_dev);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug stem wgrad");
-}
-
-// Both packed operators of a 3x3 convolution's master weights w[cout][cin][3][3]: by the training step's sub-tile kernel (wf_tile, wd_tile)
-// and by the element-wise kernel of the inference load path (wf_elem, wd_elem); the test compares them bit for bit.  cout*cin*9 floats each.
-extern "C" int dh_debug_pack_f32(const float* w_dev, int32_t cout, int32_t cin, float* wf_tile, float* wd_tile, float* wf_elem,
-                                 float* wd_elem, void* stream) {
-  DH_REQUIRE(w_dev && wf_tile && wd_tile && wf_elem && wd_elem && cout > 0 && cin > 0 && cout % 64 == 0 && cin % 64 == 0, "debug pack: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  PackDescF hd{w_dev, wf_tile, wd_tile, cout, cin, 3, 0};
-  PackDescF* dd;
-  int rc;
-  if ((rc = sc.get(&dd, 1))) return rc;
-  DH_HIP(hipMemcpyAsync(dd, &hd, sizeof hd, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(pack_all_f32_kernel, dim3(packf_blocks(cout, cin, 3)), dim3(256), PACKF_LDS, st, dd, 1, 0);
-  DH_LAUNCH_CHECK();
-  const int64_t nw = (int64_t)cout * cin * 9;
-  hipLaunchKernelGGL((pack_conv_dev_kernel<float, false>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, 3, wf_elem);
-  hipLaunchKernelGGL((pack_conv_dev_kernel<float, true>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, 3, wd_elem);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug pack");
-}
-
-// dX NHWC [B][Hi][Wi][cin] of a conv from dz and the float32 weights [cout][cin][ks][ks] (device): the flipped / transposed
-// operand is packed on the device, stride 2 goes through the four parity classes of dX (3x3) or the low-resolution product (1x1)
-extern "C" int dh_debug_dgrad_f32(const float* dz_dev, const float* w_dev, const float* res_dev, float* dx_dev, int32_t B, int32_t Hi,
-                                  int32_t Wi, int32_t cin, int32_t cout, int32_t ks, int32_t stride, void* stream) {
-  DH_REQUIRE(dz_dev && w_dev && dx_dev && (ks == 1 || ks == 3) && (stride == 1 || stride == 2) && cin % 64 == 0 && cout % 64 == 0,
-             "debug dgrad: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  const int Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1, Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  const int64_t nw = (int64_t)cout * cin * ks * ks;
-  float *wp_d, *ones, *zeros;
-  int rc;
-  if ((rc = sc.get(&wp_d, nw)) || (rc = sc.get(&ones, 512)) || (rc = sc.get(&zeros, 512))) return rc;
-  const UnitAffine u{ones, zeros};
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, ones, (int64_t)512, 1.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, zeros, (int64_t)512, 0.0f);
-  if (ks == 1) {   // the 1x1 data gradient is a GEMM over the transposed weights Wt[cin][cout] (what pack_all_f32_kernel keeps)
-    PackDescF d{w_dev, wp_d, wp_d, cout, cin, 1, 0}, *dd;
-    if ((rc = sc.get(&dd, 1))) return rc;
-    if (hipMemcpyAsync(dd, &d, sizeof d, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return DH_EHIP;
-    hipLaunchKernelGGL(pack_all_f32_kernel, dim3((unsigned)((nw + PACKF_PER_BLOCK - 1) / PACKF_PER_BLOCK)), dim3(256), 0, st, dd, 1, 0);
-  } else {
-    hipLaunchKernelGGL((pack_conv_dev_kernel<float, true>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, ks, wp_d);
-  }
-  if (ks == 3 && stride == 1) rc = tr_conv(u, cout, cin, 3, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
-  else if (ks == 3) rc = tr_dgrad_s2(u, cout, cin, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, Hi, Wi, st);   // the parity classes of dX over dZ itself
-  else if (stride == 1) rc = tr_conv(u, cout, cin, 1, 1, wp_d, dz_dev, res_dev, dx_dev, B, Ho, Wo, st);
-  else {   // 1x1 stride 2 (downsample branch): dx (+)= upsample(conv1x1(dz)); dx starts from res (or zero)
-    float* up;
-    if ((rc = sc.get(&up, (int64_t)B * Ho * Wo * cin))) return rc;
-    const int64_t nx = (int64_t)B * Hi * Wi * cin;
-    if (res_dev) (void)hipMemcpyAsync(dx_dev, res_dev, nx * 4, hipMemcpyDeviceToDevice, st);
-    else (void)hipMemsetAsync(dx_dev, 0, nx * 4, st);
-    rc = tr_conv(u, cout, cin, 1, 1, wp_d, dz_dev, nullptr, up, B, Ho, Wo, st);
-    const int64_t m4 = (int64_t)B * Ho * Wo * cin / 4;
-    if (!rc) hipLaunchKernelGGL(upsample2_add_kernel, dim3(grid_for(m4)), dim3(256), 0, st, up, dx_dev, B, Ho, Wo, cin);
-  }
-  if (rc) return rc;
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug dgrad");
-}
-
-namespace {
-// a BnView over caller data: scratch per-channel buffers and reduction workspace, running statistics starting from (0, 1)
-int dbg_bn_view(DbgScratch& sc, hipStream_t st, const float* z, const float* gamma, const float* beta, float* dgamma, float* dbeta, int64_t rows,
-                int B, int Ho, int Wo, int C, BnView* v) {
-  float *partial, *buf;
-  int rc;
-  if ((rc = sc.get(&partial, (int64_t)RED_NB * 2 * 512)) || (rc = sc.get(&buf, 9 * (int64_t)C))) return rc;
-  *v = {z, gamma, beta, buf + 7 * C, buf + 8 * C, dgamma, dbeta,
-        BnBufs{buf, buf + C, buf + 2 * C, buf + 3 * C, buf + 4 * C, buf + 5 * C, buf + 6 * C}, rows, C, B, Ho, Wo, partial};
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, v->run_mean, (int64_t)C, 0.0f);
-  hipLaunchKernelGGL(fill_kernel, dim3(2), dim3(256), 0, st, v->run_var, (int64_t)C, 1.0f);
-  return DH_OK;
-}
-}  // namespace
-
-// training-mode BN over NHWC rows through the engine's launch code (tr_bn_forward / tr_bn_backward): forward (batch statistics ->
-// y = [relu](z*scale + shift [+ res])) and, when dy_dev is given, backward (dz, optional masked gradient g, dgamma, dbeta).
-// relu: 0 none, 1 ReLU with the backward pattern read from y, 2 ReLU with the pattern recomputed from z (what the engine does for a BN
-// whose output goes straight into a ReLU: no residual, no masked gradient).  stats_out (optional): [mean C | invstd C | run_mean C |
-// run_var C] after one update from running (0, 1).
-extern "C" int dh_debug_bn_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, const float* res_dev, int32_t relu,
-                               float* y_dev, const float* dy_dev, float* dz_dev, float* g_dev, float* dgamma_dev, float* dbeta_dev,
-                               float* stats_out_dev, int64_t rows, int32_t C, void* stream) {
-  DH_REQUIRE(z_dev && gamma_dev && beta_dev && y_dev && rows > 0 && C % 4 == 0 && C <= 512 && 256 % (C / 4) == 0, "debug bn: bad arguments");
-  DH_REQUIRE(relu >= 0 && relu <= 2, "debug bn: relu=%d (0 none, 1 pattern from y, 2 pattern recomputed from z)", relu);
-  DH_REQUIRE(relu != 2 || (!res_dev && !g_dev), "debug bn: relu=2 (pattern recomputed from z) takes neither res_dev nor g_dev");
-  DH_REQUIRE(!dy_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn: backward outputs missing");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  BnView v;
-  int rc;
-  if ((rc = dbg_bn_view(sc, st, z_dev, gamma_dev, beta_dev, dgamma_dev, dbeta_dev, rows, 0, 0, 0, C, &v))) return rc;
-  if ((rc = tr_bn_forward(v, res_dev, relu != 0, y_dev, st))) return rc;
-  if (dy_dev && (rc = tr_bn_backward(v, dy_dev, relu == 1 ? y_dev : nullptr, relu != 0, dz_dev, g_dev, st))) return rc;
-  if (stats_out_dev) {
-    (void)hipMemcpyAsync(stats_out_dev, v.bn.mean, C * 4, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(stats_out_dev + C, v.bn.invstd, C * 4, hipMemcpyDeviceToDevice, st);
-    (void)hipMemcpyAsync(stats_out_dev + 2 * C, v.run_mean, 2 * (size_t)C * 4, hipMemcpyDeviceToDevice, st);
-  }
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug bn");
-}
-
-// The stem's fused tail of the float32 engine on caller data, through the engine's launch code (tr_bn_forward with a pooled target,
-// tr_bn_pool_backward): pooled [B][Hp][Wp][C] = maxpool3x3/2(relu(bn(z))) with batch statistics + first-maximum positions (uint8), and,
-// when dpool_dev is given, dz [B][Hi][Wi][C], dgamma, dbeta with the maxpool's gradient gathered inside the BN backward passes.
-extern "C" int dh_debug_bn_pool_f32(const float* z_dev, const float* gamma_dev, const float* beta_dev, float* pooled_dev, uint8_t* idx_dev,
-                                    const float* dpool_dev, float* dz_dev, float* dgamma_dev, float* dbeta_dev, int32_t B, int32_t Hi, int32_t Wi,
-                                    int32_t C, void* stream) {
-  DH_REQUIRE(z_dev && gamma_dev && beta_dev && pooled_dev && idx_dev && B > 0 && Hi > 0 && Wi > 0 && C % 4 == 0 && C <= 512 && 256 % (C / 4) == 0,
-             "debug bn pool: bad arguments");
-  DH_REQUIRE(!dpool_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn pool: backward outputs missing");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  BnView v;
-  int rc;
-  if ((rc = dbg_bn_view(sc, st, z_dev, gamma_dev, beta_dev, dgamma_dev, dbeta_dev, (int64_t)B * Hi * Wi, B, Hi, Wi, C, &v))) return rc;
-  if ((rc = tr_bn_forward(v, nullptr, true, nullptr, st, pooled_dev, idx_dev))) return rc;
-  if (dpool_dev && (rc = tr_bn_pool_backward(v, dpool_dev, idx_dev, dz_dev, st))) return rc;
-  return dbg_finish(st, "debug bn pool");
-}
-
-// maxpool 3x3 / 2 / pad 1 on NHWC float32: forward with the recorded first-maximum positions, and (dy_dev given) backward
-extern "C" int dh_debug_maxpool_f32(const float* x_dev, float* y_dev, const float* dy_dev, float* dx_dev, int32_t B, int32_t Hi, int32_t Wi,
-                                    int32_t C, void* stream) {
-  DH_REQUIRE(x_dev && y_dev && C % 4 == 0 && B > 0, "debug maxpool: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-  DbgScratch sc;
-  uint8_t* idx;
-  int rc = sc.get(&idx, (int64_t)B * Ho * Wo * C);
-  if (rc) return rc;
-  const int64_t n4 = (int64_t)B * Ho * Wo * C / 4;
-  hipLaunchKernelGGL(maxpool_fwd_idx_kernel, dim3(grid_for(n4)), dim3(256), 0, st, x_dev, y_dev, idx, B, Hi, Wi, C, Ho, Wo);
-  if (dy_dev) {
-    DH_REQUIRE(dx_dev != nullptr, "debug maxpool: dx missing");
-    const int64_t m4 = (int64_t)B * Hi * Wi * C / 4;
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(m4)), dim3(256), 0, st, idx, dy_dev, dx_dev, B, Hi, Wi, C, Ho, Wo);
-  }
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug maxpool");
 }

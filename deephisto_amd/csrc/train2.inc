@@ -1,7 +1,8 @@
 // train2.inc -- bf16 training / evaluation engine for the patch classifiers of BASELINE configs[4]:
 // ResNet-18 (BasicBlock) and ResNet-50 (Bottleneck, torchvision v1.5) with bf16 activations and bf16 MFMA
 // (f32 accumulation), f32 master weights, f32 gradients, Adam in f32.  Host side; kernels in train2_kernels.inc and
-// conv3x3.inc.  Included at the end of resnet_kernels.hip.
+// conv3x3.inc.  Included at the end of resnet_kernels.hip.  The file ends with its last product entry point: the test hooks over
+// this code are train_hooks.inc's, declared in include/deephisto_hip_debug.h.
 //
 // Replaces, for `get_model` with a ResNet-50 backbone (models/patch_cls_simple/model.py:5-11 builds the torchvision
 // network; BASELINE.json configs[4] names the ResNet-50 variant), the step of models/patch_cls_simple/train.py:166-172:
@@ -50,7 +51,7 @@ struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order
   int64_t wgrad_slab_floats = 0;
   const float* x_in = nullptr;
   bool last_training = false;
-  bool bwd_done = false;    // a backward pass has run since the last forward: every dZ buffer holds THIS step's gradient (dh_train2_debug_act)
+  bool bwd_done = false;    // a backward pass has run since the last forward: every dZ buffer holds THIS step's gradient (the dZ tap, train_hooks.inc)
   bool packed = false;
   PackDesc* pack_desc = nullptr;   // device table of t2_pack_all (one launch packs every conv)
   int pack_blocks = 0;
@@ -486,7 +487,7 @@ int t2_bn_fwd(dh_train2* t, T2Conv& c, const bf16_t* res, bool relu, bool traini
   return DH_OK;
 }
 
-// The route record of one BN's backward pass (dh_train2_debug_backward_tap, include/deephisto_hip_debug.h): plain host values.
+// The route record of one BN's backward pass (the backward tap of train_hooks.inc; the values: include/deephisto_hip_debug.h): plain host values.
 enum { T2R_RELU = 0, T2R_PREMASKED, T2R_IN_MASK, T2R_HAVE_ROWS, T2R_REDUCE, T2R_APPLY, T2R_BRANCH, T2R_ROWS, T2R_N };
 enum { T2R_REDUCE_EPILOGUE = 0, T2R_REDUCE_SLICED = 1, T2R_REDUCE_BLOCKS = 2, T2R_REDUCE_POOL = 3 };
 enum { T2R_APPLY_FOLD = 1, T2R_APPLY_FINALIZE = 2 };
@@ -501,7 +502,7 @@ struct T2BwdTap {   // one BN, named by its conv: device float32 copies of what 
 // relu: 0 none (no ReLU, or dy arrives masked), 1 pattern from y_mask (the BN output was joined with an identity before the ReLU),
 // 2 pattern recomputed from Z
 // have_rows > 0: the GEMM that produced dy already left that many rows of per-tile sums in t->partial (no reduction pass)
-// route (test hook, dh_train2_debug_backward_tap; null in every step): receives which launches ran, route[T2R_REDUCE .. T2R_ROWS]
+// route (the backward tap of train_hooks.inc; null in every step): receives which launches ran, route[T2R_REDUCE .. T2R_ROWS]
 int t2_bn_bwd(dh_train2* t, T2Conv& c, const bf16_t* dy, const bf16_t* y_mask, int relu, bf16_t* dz, bf16_t* g_out, hipStream_t st,
               int have_rows = 0, int32_t* route = nullptr) {
   const int C = c.cout;
@@ -562,12 +563,19 @@ int t2_bn_pool_bwd(dh_train2* t, T2Conv& c, const bf16_t* dpool, const uint8_t* 
   return DH_OK;
 }
 
-// stem weight-gradient slabs: bf16 MFMA (stem_wgrad_bf16_kernel)
-int t2_stem_wgrad(const bf16_t* dz, const float* x, float* slabs, int B, int P, int Ho, int Wo, int rpb, int n_slabs, hipStream_t st) {
+// The stem's dW [64][3][7][7] (`dw`, float32) from bf16 dz [B][Ho][Wo][64] and the float32 NCHW image x: per-slab partial sums over at
+// most STEM_WGRAD_SLABS runs of output rows on bf16 MFMA (stem_wgrad_bf16_kernel; `slabs`: STEM_WGRAD_SLABS * 64 * 160 floats), then
+// their fixed-order reduction.
+int t2_stem_wgrad(const bf16_t* dz, const float* x, float* slabs, float* dw, int B, int P, int Ho, int Wo, hipStream_t st) {
+  const int total_rows = B * Ho;
+  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
+  const int n_slabs = (total_rows + rpb - 1) / rpb;
   DH_REQUIRE(Wo * 8 <= 2 * SWG_T && P + 6 <= SWG_T, "stem wgrad: patch %d too wide for the row staging", P);
   DH_REQUIRE(Wo % 16 == 0, "stem wgrad (bf16 MFMA): the output width %d is not a multiple of 16 pixels", Wo);
   const size_t lds = std::max<size_t>(((size_t)((21 * (P + 6) + 7) & ~7) + (size_t)Wo * 64) * 2, (size_t)64 * 160 * sizeof(float));
   hipLaunchKernelGGL(stem_wgrad_bf16_kernel, dim3(n_slabs), dim3(SWG_T), lds, st, dz, x, slabs, B, P, Ho, Wo, rpb);
+  DH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -799,7 +807,7 @@ bool t2_premasked(const dh_train2* t, int bi) {
 
 // `fused` (single-rank training): the Adam update and the bf16 repack of a block's tensors follow that block's weight gradients on
 // the side stream, instead of one update of the whole arena after the pass (same arithmetic per element: identical parameters).
-// `tap` (dh_train2_debug_backward_tap only, null in every step): copies of one BN's operands, enqueued between the launches below; no
+// `tap` (the backward tap of train_hooks.inc only, null in every step): copies of one BN's operands, enqueued between the launches below; no
 // launch of the pass, no argument of one and no buffer it uses depends on it.
 int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamArgs* fused, const T2BwdTap* tap = nullptr) {
   const int B = t->B, ncls = t->n_classes;
@@ -935,13 +943,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
     // the side stream after this point, so the join that the optimiser needs anyway moves in front of the tail.
     if ((rc = join_side())) return rc;
     if ((rc = t2_bn_pool_bwd(t, c, dOut, t->pool_idx, dZ, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
-    const int total_rows = B * c.Ho;
-    const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
-    const int n_slabs = (total_rows + rpb - 1) / rpb;
-    if ((rc = t2_stem_wgrad(dZ, t->x_in, t->stem_slabs, B, t->P, c.Ho, c.Wo, rpb, n_slabs, st))) return rc;
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, t->stem_slabs, n_slabs,
-                       t->G + t->slot["conv1.weight"].first);
-    DH_LAUNCH_CHECK();
+    if ((rc = t2_stem_wgrad(dZ, t->x_in, t->stem_slabs, t->G + t->slot["conv1.weight"].first, B, t->P, c.Ho, c.Wo, st))) return rc;
     mark_done();   // the optimiser (and the last bucket) follow on the main stream, behind the join above
     if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
       if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, t->n_params - adam_off, st);
@@ -978,506 +980,4 @@ extern "C" int dh_train2_adam_step(dh_train2* t, float lr, float beta1, float be
   adam_range(*t, adam_args(*t, lr, beta1, beta2, eps, step), 0, t->n_params, st);
   DH_LAUNCH_CHECK();
   return t2_pack_all(t, st);
-}
-
-// Test hook: float32 copy of a tensor the last forward / backward left in memory: what = 0 Z, 1 Y, 2 dZ of conv `conv_name` (dZ: the
-// gradient with respect to Z as the weight-gradient kernel read it; the stem's lives in GB[2], which the side-stream engine uses for
-// nothing else), 3 the pooled block input X1 (under "conv1").  Read-only but for what = 1 on the stem, which rebuilds Y from Z.
-extern "C" int dh_train2_debug_act(dh_train2* t, const char* conv_name, int32_t what, float* out_dev, int64_t n_elem, void* stream) {
-  DH_REQUIRE(t && conv_name && out_dev && t->B > 0, "train2 debug: bad arguments / no forward");
-  DH_REQUIRE(what >= 0 && what <= 3, "train2 debug: what = %d (0 Z, 1 Y, 2 dZ, 3 X1)", what);
-  hipStream_t st = dh::as_stream(stream);
-  for (const T2Conv& c : t->convs)
-    if (c.name == conv_name) {
-      const bool stem = &c == &t->convs[0];
-      DH_REQUIRE(what != 3 || stem, "train2 debug: what = 3 (X1, the pooled block input) goes with 'conv1', not '%s'", conv_name);
-      const int H2 = (c.Ho + 2 - 3) / 2 + 1;
-      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * c.Ho * c.Wo * c.cout;
-      DH_REQUIRE(n == n_elem, "train2 debug: n_elem = %lld, '%s' (what = %d) has %lld elements", (long long)n_elem, conv_name, what, (long long)n);
-      const bf16_t* src = what == 0 ? c.Z : what == 1 ? c.Y : what == 3 ? t->X1 : stem ? t->GB[2] : c.dZ;
-      if (what == 2) {
-        DH_REQUIRE(t->side_wgrad, "train2 debug: what = 2 (dZ) needs the per-convolution dZ buffers of the side-stream engine (created with DH_T2_SIDE=0)");
-        DH_REQUIRE(t->bwd_done, "train2 debug: what = 2 (dZ): no backward has run since the last forward");
-      }
-      if (what == 1 && stem)   // the stem's normalised map is not kept (bn2_apply_pool_kernel): made here from Z and the saved coefficients
-        hipLaunchKernelGGL(bn2_apply_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, c.Z, c.bnb.scale, c.bnb.shift,
-                           static_cast<const bf16_t*>(nullptr), c.Y, n / 8, c.cout, 1);
-      hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, src, out_dev, n);
-      DH_LAUNCH_CHECK();
-      return DH_OK;
-    }
-  dh::set_error("train2 debug: unknown conv_name '%s'", conv_name);
-  return DH_EINVAL;
-}
-
-// Test hook: dh_train2_backward with one BN's backward operands copied out (include/deephisto_hip_debug.h).  The same t2_backward, the
-// same launches in the same order; the copies read buffers of the pass between their writer and their next writer, on the same stream.
-extern "C" int dh_train2_debug_backward_tap(dh_train2* t, const float* dlogits, const char* conv_name, float* grad_in_dev, int64_t n_elem,
-                                            float* g_out_dev, float* mean_dev, float* invstd_dev, int32_t* route_host, void* stream) {
-  DH_REQUIRE(t && dlogits && conv_name && grad_in_dev && mean_dev && invstd_dev && route_host, "train2 backward tap: null argument");
-  DH_REQUIRE(t->B > 0 && t->last_training && !t->bwd_done,
-             "train2 backward tap: no training forward has run since the last backward (every tapped backward follows a forward of its own)");
-  hipStream_t st = dh::as_stream(stream);
-  for (size_t ci = 0; ci < t->convs.size(); ++ci) {
-    const T2Conv& c = t->convs[ci];
-    if (c.name != conv_name) continue;
-    const int Hp = (c.Ho + 2 - 3) / 2 + 1, Wp = (c.Wo + 2 - 3) / 2 + 1;
-    const int64_t n = ci == 0 ? (int64_t)t->B * Hp * Wp * c.cout : (int64_t)t->B * c.Ho * c.Wo * c.cout;
-    DH_REQUIRE(n == n_elem, "train2 backward tap: n_elem = %lld, grad_in of '%s' has %lld elements", (long long)n_elem, conv_name, (long long)n);
-    bool writes_g_out = false;   // the top BN of a block that is not pre-masked
-    for (int bi = 0; bi < (int)t->blocks.size(); ++bi) {
-      const BlockDesc& b = t->blocks[bi];
-      if (b.conv[b.nconv - 1] == (int)ci) writes_g_out = !t2_premasked(t, bi);
-    }
-    DH_REQUIRE(!g_out_dev || writes_g_out, "train2 backward tap: g_out_dev given, but the BN of '%s' writes no masked gradient (pass NULL)", conv_name);
-    const T2BwdTap tap{&c, grad_in_dev, g_out_dev, route_host};
-    for (int i = 0; i < T2R_N; ++i) route_host[i] = -1;
-    int rc = t2_backward(t, dlogits, st, nullptr, &tap);
-    if (rc) return rc;
-    DH_HIP(hipMemcpyAsync(mean_dev, c.bnb.mean, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DH_HIP(hipMemcpyAsync(invstd_dev, c.bnb.invstd, (size_t)c.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return DH_OK;
-  }
-  dh::set_error("train2 backward tap: unknown conv_name '%s'", conv_name);
-  return DH_EINVAL;
-}
-
-// Both bf16 operators of a 3x3 convolution's float32 master weights w[cout][cin][3][3]: by the engine's re-pack kernel (one workgroup per
-// 64 x 64 tile through LDS: wf_tile, wd_tile) and by the element-wise packer of the inference load path (wf_elem, wd_elem); the test compares
-// them bit for bit.  cout * cin * 9 bf16 values each.
-extern "C" int dh_debug_pack_bf16(const float* w_dev, int32_t cout, int32_t cin, uint16_t* wf_tile, uint16_t* wd_tile, uint16_t* wf_elem,
-                                  uint16_t* wd_elem, void* stream) {
-  DH_REQUIRE(w_dev && wf_tile && wd_tile && wf_elem && wd_elem && cout > 0 && cin > 0 && cout % 64 == 0 && cin % 64 == 0, "debug pack: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  PackDesc hd{w_dev, wf_tile, wd_tile, cout, cin, 3, 0};
-  PackDesc* dd;
-  int rc;
-  if ((rc = sc.get(&dd, 1))) return rc;
-  DH_HIP(hipMemcpyAsync(dd, &hd, sizeof hd, hipMemcpyHostToDevice, st));
-  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&pack_all_kernel), PACK3_LDS))) return rc;
-  hipLaunchKernelGGL(pack_all_kernel, dim3((cout / 64) * (cin / 64)), dim3(256), PACK3_LDS, st, dd, 1, 0);
-  DH_LAUNCH_CHECK();
-  const int64_t nw = (int64_t)cout * cin * 9;
-  hipLaunchKernelGGL((pack_conv_dev_kernel<uint16_t, false>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, 3, wf_elem);
-  hipLaunchKernelGGL((pack_conv_dev_kernel<uint16_t, true>), dim3(grid_for(nw)), dim3(256), 0, st, w_dev, cout, cin, 3, wd_elem);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug pack");
-}
-
-// Test hooks of the bf16 engine's GEMM-shaped kernels on caller data (bf16 bits as uint16 on the device; synchronise):
-//   gemm1x1 : out[M][N] = A[rows][K] . W[N][K]^T (+ res); stride 2 gathers rows (b, 2 oy, 2 ox) of a [B][Hi][Wi][K] tensor
-//   wgrad   : dW[cout][cin][ks][ks] (float32) from x [B][Hi][Wi][cin] and dz [B][Ho][Wo][cout]
-extern "C" int dh_debug_gemm1x1_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const uint16_t* res_dev, uint16_t* out_dev, int64_t M,
-                                     int32_t N, int32_t K, int32_t stride, int32_t Ho, int32_t Wo, int32_t Hi, int32_t Wi, int32_t repeat,
-                                     void* stream) {
-  DH_REQUIRE(a_dev && w_dev && out_dev && repeat >= 1, "debug gemm: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  for (int i = 0; i < repeat; ++i) {
-    GemmFuse fu;
-    fu.res = res_dev;
-    int rc = t2_gemm(a_dev, w_dev, out_dev, M, N, K, stride, Ho, Wo, Hi, Wi, fu, st);
-    if (rc) return rc;
-  }
-  return dbg_finish(st, "debug gemm");
-}
-
-// The same GEMM with its fused epilogues (gemm1x1.inc): + res, ReLU mask taken from `mask_dev` (zero where that tensor is <= 0), and
-// the batch statistics of the bf16-rounded output: mean_dev / invstd_dev (float32[N], may be null) as the BN coefficients come out
-// of the fixed-point accumulator (eps 1e-5, biased variance) from the per-tile partial rows and the finalize launch.
-extern "C" int dh_debug_gemm1x1_fused_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const uint16_t* res_dev, const uint16_t* mask_dev,
-                                           uint16_t* out_dev, float* mean_dev, float* invstd_dev, int64_t M, int32_t N, int32_t K,
-                                           int32_t stride, int32_t Ho, int32_t Wo, int32_t Hi, int32_t Wi, int32_t repeat, void* stream) {
-  DH_REQUIRE(a_dev && w_dev && out_dev && repeat >= 1 && N > 0 && N <= 2048, "debug gemm fused: bad arguments");
-  DH_REQUIRE((mean_dev == nullptr) == (invstd_dev == nullptr), "debug gemm fused: mean and invstd come together");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  GemmFuse fu;
-  fu.res = res_dev;
-  int rc;
-  if (mask_dev) {   // the engine hands the GEMM the ReLU pattern as bytes (st8_bits): make them from the test's bf16 mask tensor
-    DH_REQUIRE(stride == 1, "debug gemm fused: the mask rides on the stride-1 GEMM");
-    uint8_t* mb = nullptr;
-    if ((rc = sc.get(&mb, M * N / 8))) return rc;
-    hipLaunchKernelGGL(relu_bits_pack_kernel, dim3(grid_for(M * N / 8)), dim3(256), 0, st, mask_dev, mb, M * N / 8);
-    fu.mask_bits = mb;
-  }
-  float* tmp = nullptr;
-  BnFinal f{};
-  const int64_t MB = (M + G2_BM - 1) / G2_BM;
-  if (mean_dev) {
-    DH_REQUIRE(MB * 2 * N <= T2_PARTIAL_FLOATS, "debug gemm fused: too many pixel tiles for the statistics buffer");
-    if ((rc = sc.get(&fu.partial, MB * 2 * N)) || (rc = sc.get(&tmp, (int64_t)6 * N))) return rc;
-    DH_HIP(hipMemsetAsync(tmp, 0, 6 * N * sizeof(float), st));
-    hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, st, tmp, (int64_t)N, 1.0f);   // gamma = 1 (beta = 0)
-    f.mean = mean_dev; f.invstd = invstd_dev; f.gamma = tmp; f.beta = tmp + N; f.scale = tmp + 2 * N;
-    f.shift = tmp + 3 * N; f.run_mean = tmp + 4 * N; f.run_var = tmp + 5 * N; f.n_rows = (double)M;
-  }
-  for (int i = 0; i < repeat; ++i) {
-    if ((rc = t2_gemm(a_dev, w_dev, out_dev, M, N, K, stride, Ho, Wo, Hi, Wi, fu, st))) return rc;
-    if (fu.partial) {
-      hipLaunchKernelGGL(bn_stat_finalize_onepass_kernel, dim3((N + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, fu.partial, (int)MB, N, f.n_rows, f.mean, f.invstd,
-                         f.gamma, f.beta, f.scale, f.shift, f.run_mean, f.run_var);
-      DH_LAUNCH_CHECK();
-    }
-  }
-  return dbg_finish(st, "debug gemm fused");
-}
-
-// The fused BN-backward sums of a dgrad GEMM (gemm1x1.inc, "bwd"): out = A . W^T (+ res) (masked), and for the BN whose dY `out` is
-// -- pre-activation z_dev [M][N], saved mean / invstd, and, for relu_mode 2, its scale / shift -- sums_dev[0..N) = sum g,
-// sums_dev[N..2N) = sum g xhat (float32, the per-tile rows added up in double as the finalize launch does).
-extern "C" int dh_debug_gemm1x1_bwdsums_bf16(const uint16_t* a_dev, const uint16_t* w_dev, const uint16_t* res_dev, const uint16_t* mask_dev,
-                                             uint16_t* out_dev, const uint16_t* z_dev, const float* mean_dev, const float* invstd_dev,
-                                             const float* scale_dev, const float* shift_dev, int32_t relu_mode, float* sums_dev, int64_t M,
-                                             int32_t N, int32_t K, void* stream) {
-  DH_REQUIRE(a_dev && w_dev && out_dev && z_dev && mean_dev && invstd_dev && sums_dev && (relu_mode == 0 || (relu_mode == 2 && scale_dev && shift_dev)),
-             "debug gemm bwd sums: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  const int64_t MB = (M + G2_BM - 1) / G2_BM;
-  DH_REQUIRE(MB * 2 * N <= T2_PARTIAL_FLOATS, "debug gemm bwd sums: too many pixel tiles for the rows buffer");
-  GemmFuse fu;
-  fu.res = res_dev;
-  float *ones, *scratch;
-  int rc;
-  if (mask_dev) {   // the ReLU pattern as bytes, the form the engine hands over (st8_bits)
-    uint8_t* mb = nullptr;
-    if ((rc = sc.get(&mb, M * N / 8))) return rc;
-    hipLaunchKernelGGL(relu_bits_pack_kernel, dim3(grid_for(M * N / 8)), dim3(256), 0, st, mask_dev, mb, M * N / 8);
-    fu.mask_bits = mb;
-  }
-  if ((rc = sc.get(&fu.partial, MB * 2 * N)) || (rc = sc.get(&ones, (int64_t)N)) || (rc = sc.get(&scratch, (int64_t)3 * N))) return rc;
-  T2Conv bn;
-  bn.cout = N; bn.Z = const_cast<bf16_t*>(z_dev);
-  bn.bnb.mean = const_cast<float*>(mean_dev); bn.bnb.invstd = const_cast<float*>(invstd_dev);
-  bn.bnb.scale = const_cast<float*>(scale_dev); bn.bnb.shift = const_cast<float*>(shift_dev);
-  fu.bwd_of = &bn; fu.bwd_relu = relu_mode;
-  if ((rc = t2_gemm(a_dev, w_dev, out_dev, M, N, K, 1, 1, 1, 1, 1, fu, st))) return rc;
-  // column sums of the rows through the engine's finalize kernel: dgamma = sum g xhat, dbeta = sum g
-  hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, st, ones, (int64_t)N, 1.0f);
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((N + FIN_CH - 1) / FIN_CH), dim3(256), 0, st, fu.partial, (int)MB, N, (double)M, ones, mean_dev, invstd_dev,
-                     sums_dev + N, sums_dev, scratch, scratch + N, scratch + 2 * N);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug gemm bwd sums");
-}
-
-// Test hook of the bf16 engine's batch-norm kernels on caller data (bf16 bits as uint16, [rows][C] channels-last), through the
-// engine's own launch code (t2_bn_fwd / t2_bn_bwd: per-workgroup partial sums -> finalize launch -> elementwise pass):
-//   forward  : y = [relu](bn(z) [+ res]) with batch statistics; mean / invstd (float32[C]) as saved for the backward pass;
-//   backward : (dy given) dz, dgamma, dbeta; relu_mode 0 none / pre-masked dy, 1 pattern from y, 2 pattern recomputed from z;
-//              g_out (may be null, relu_mode 1): the masked gradient.
-extern "C" int dh_debug_bn2_bf16(const uint16_t* z_dev, const uint16_t* res_dev, const float* gamma_dev, const float* beta_dev, int32_t relu,
-                                 uint16_t* y_dev, float* mean_dev, float* invstd_dev, const uint16_t* dy_dev, int32_t relu_mode,
-                                 uint16_t* dz_dev, uint16_t* g_out_dev, float* dgamma_dev, float* dbeta_dev, int64_t rows, int32_t C,
-                                 void* stream) {
-  DH_REQUIRE(z_dev && gamma_dev && beta_dev && y_dev && mean_dev && invstd_dev && rows > 0 && C >= 64 && C <= 2048 && C % 64 == 0 &&
-             (256 % (C / 8) == 0 || (C / 8) % 256 == 0), "debug bn2: bad arguments");
-  DH_REQUIRE(!dy_dev || (dz_dev && dgamma_dev && dbeta_dev && relu_mode >= 0 && relu_mode <= 2), "debug bn2: backward needs dz, dgamma, dbeta");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  dh_train2 t;
-  t.B = 1;
-  T2Conv c;
-  c.name = "dbg"; c.bn = "dbgbn"; c.cout = C; c.Ho = 1; c.Wo = (int)rows; c.ks = 3;
-  DH_REQUIRE(rows < ((int64_t)1 << 31), "debug bn2: too many rows");
-  int rc;
-  float* buf;
-  if ((rc = sc.get(&buf, (int64_t)9 * C))) return rc;
-  DH_HIP(hipMemsetAsync(buf, 0, 9 * C * sizeof(float), st));
-  // parameter / gradient / running-statistic "arenas" of this one layer
-  t.Pm = buf; t.G = buf + 2 * C; t.R = buf + 4 * C;
-  t.slot["dbgbn.weight"] = {0, C}; t.slot["dbgbn.bias"] = {C, C};
-  t.rslot["dbgbn.running_mean"] = {0, C}; t.rslot["dbgbn.running_var"] = {C, C};
-  DH_HIP(hipMemcpyAsync(t.Pm, gamma_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  DH_HIP(hipMemcpyAsync(t.Pm + C, beta_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  c.bnb.mean = mean_dev; c.bnb.invstd = invstd_dev; c.bnb.scale = buf + 6 * C; c.bnb.shift = buf + 7 * C;
-  if ((rc = sc.get(&t.partial, T2_PARTIAL_FLOATS))) return rc;
-  c.bnb.k0 = buf + 8 * C;
-  float* k12;
-  if ((rc = sc.get(&k12, (int64_t)2 * C))) return rc;
-  c.bnb.k1 = k12; c.bnb.k2 = k12 + C;
-  c.Z = const_cast<bf16_t*>(z_dev); c.Y = y_dev;
-  if ((rc = t2_bn_fwd(&t, c, res_dev, relu != 0, true, st, false))) return rc;
-  if (dy_dev) {
-    if ((rc = t2_bn_bwd(&t, c, dy_dev, relu_mode == 1 ? y_dev : nullptr, relu_mode, dz_dev, g_out_dev, st))) return rc;
-    DH_HIP(hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DH_HIP(hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  }
-  return dbg_finish(st, "debug bn2");
-}
-
-// dh_debug_bn2_bf16 with the engine's remaining routes through t2_bn_fwd / t2_bn_bwd selectable (tests/test_gpu_bn_bf16_parity.py):
-//   fold     : t->fold (1: small maps finalize inside the apply passes, bn_fold.inc; 0: partial sums -> finalize launch -> elementwise pass);
-//   bits     : (may be null) the ReLU pattern of y, [rows][C / 8] bytes (st8_bits), as a block's top BN leaves it;
-//   z2, gamma2, beta2 (all or none): the join of a downsample block -- the branch BN of z2 runs with apply = false (statistics and
-//              coefficients only; mean2 / invstd2 return them) and this BN applies it inside its own pass (bn2_apply_join_kernel).
-extern "C" int dh_debug_bn2_paths_bf16(const uint16_t* z_dev, const uint16_t* res_dev, const float* gamma_dev, const float* beta_dev, int32_t relu,
-                                       int32_t fold, uint16_t* y_dev, uint8_t* bits_dev, float* mean_dev, float* invstd_dev,
-                                       const uint16_t* z2_dev, const float* gamma2_dev, const float* beta2_dev, float* mean2_dev,
-                                       float* invstd2_dev, const uint16_t* dy_dev, int32_t relu_mode, uint16_t* dz_dev, uint16_t* g_out_dev,
-                                       float* dgamma_dev, float* dbeta_dev, int64_t rows, int32_t C, void* stream) {
-  DH_REQUIRE(z_dev && gamma_dev && beta_dev, "debug bn2 paths: null input (z_dev, gamma_dev or beta_dev)");
-  DH_REQUIRE(y_dev && mean_dev && invstd_dev, "debug bn2 paths: null output (y_dev, mean_dev or invstd_dev)");
-  DH_REQUIRE(rows > 0 && rows < ((int64_t)1 << 31), "debug bn2 paths: rows=%lld", (long long)rows);
-  DH_REQUIRE(C >= 64 && C <= 2048 && C % 64 == 0 && (256 % (C / 8) == 0 || (C / 8) % 256 == 0), "debug bn2 paths: C=%d (64 ... 2048, C / 8 divides 256)", C);
-  DH_REQUIRE(fold == 0 || fold == 1, "debug bn2 paths: fold=%d (0 or 1)", fold);
-  DH_REQUIRE(relu == 0 || relu == 1, "debug bn2 paths: relu=%d (0 or 1)", relu);
-  const bool join = z2_dev || gamma2_dev || beta2_dev || mean2_dev || invstd2_dev;
-  DH_REQUIRE(!join || (z2_dev && gamma2_dev && beta2_dev && mean2_dev && invstd2_dev),
-             "debug bn2 paths: the join needs z2_dev, gamma2_dev, beta2_dev, mean2_dev and invstd2_dev together");
-  DH_REQUIRE(!join || (relu == 1 && !res_dev), "debug bn2 paths: the join is a ReLU'd BN without res_dev (relu=%d)", relu);
-  DH_REQUIRE(!dy_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn2 paths: backward (dy_dev given) needs dz_dev, dgamma_dev and dbeta_dev");
-  DH_REQUIRE(!dy_dev || (relu_mode >= 0 && relu_mode <= 2), "debug bn2 paths: relu_mode=%d (0, 1 or 2)", relu_mode);
-  DH_REQUIRE(!g_out_dev || (dy_dev && relu_mode == 1), "debug bn2 paths: g_out_dev goes with dy_dev and relu_mode 1");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  dh_train2 t;
-  t.B = 1;
-  t.fold = fold != 0;
-  T2Conv c, d;
-  c.name = "dbg"; c.bn = "dbgbn"; c.cout = C; c.Ho = 1; c.Wo = (int)rows; c.ks = 3;
-  d.name = "dbgds"; d.bn = "dbgds"; d.cout = C; d.Ho = 1; d.Wo = (int)rows; d.ks = 1;
-  int rc;
-  float* buf;
-  if ((rc = sc.get(&buf, (int64_t)20 * C))) return rc;
-  DH_HIP(hipMemsetAsync(buf, 0, 20 * C * sizeof(float), st));
-  // parameter / gradient / running-statistic "arenas" of the two layers: [gamma, beta, gamma2, beta2]
-  t.Pm = buf; t.G = buf + 4 * C; t.R = buf + 8 * C;
-  t.slot["dbgbn.weight"] = {0, C}; t.slot["dbgbn.bias"] = {C, C};
-  t.slot["dbgds.weight"] = {2 * C, C}; t.slot["dbgds.bias"] = {3 * C, C};
-  t.rslot["dbgbn.running_mean"] = {0, C}; t.rslot["dbgbn.running_var"] = {C, C};
-  t.rslot["dbgds.running_mean"] = {2 * C, C}; t.rslot["dbgds.running_var"] = {3 * C, C};
-  DH_HIP(hipMemcpyAsync(t.Pm, gamma_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  DH_HIP(hipMemcpyAsync(t.Pm + C, beta_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  c.bnb.mean = mean_dev; c.bnb.invstd = invstd_dev; c.bnb.scale = buf + 12 * C; c.bnb.shift = buf + 13 * C;
-  c.bnb.k0 = buf + 14 * C; c.bnb.k1 = buf + 15 * C; c.bnb.k2 = buf + 16 * C;
-  if ((rc = sc.get(&t.partial, T2_PARTIAL_FLOATS))) return rc;
-  c.Z = const_cast<bf16_t*>(z_dev); c.Y = y_dev;
-  if (join) {
-    DH_HIP(hipMemcpyAsync(t.Pm + 2 * C, gamma2_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DH_HIP(hipMemcpyAsync(t.Pm + 3 * C, beta2_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    d.bnb.mean = mean2_dev; d.bnb.invstd = invstd2_dev; d.bnb.scale = buf + 17 * C; d.bnb.shift = buf + 18 * C;
-    d.Z = const_cast<bf16_t*>(z2_dev);
-    if ((rc = t2_bn_fwd(&t, d, nullptr, false, true, st, false, nullptr, nullptr, false))) return rc;
-  }
-  if ((rc = t2_bn_fwd(&t, c, res_dev, relu != 0, true, st, false, nullptr, nullptr, true, join ? &d : nullptr, 0, bits_dev))) return rc;
-  if (dy_dev) {
-    if ((rc = t2_bn_bwd(&t, c, dy_dev, relu_mode == 1 ? y_dev : nullptr, relu_mode, dz_dev, g_out_dev, st))) return rc;
-    DH_HIP(hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    DH_HIP(hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  }
-  return dbg_finish(st, "debug bn2 paths");
-}
-
-// The stem's fused tail on caller data, through the engine's launch code (t2_bn_fwd with a pooled target, t2_bn_pool_bwd):
-//   forward  : pooled [B][Hp][Wp][C] = maxpool3x3/2(relu(bn(z))) with batch statistics, first-maximum positions (uint8), mean / invstd;
-//   backward : (dpool given) dz [B][Hi][Wi][C], dgamma, dbeta.
-extern "C" int dh_debug_bn2_pool_bf16(const uint16_t* z_dev, const float* gamma_dev, const float* beta_dev, uint16_t* pooled_dev, uint8_t* idx_dev,
-                                      float* mean_dev, float* invstd_dev, const uint16_t* dpool_dev, uint16_t* dz_dev, float* dgamma_dev,
-                                      float* dbeta_dev, int32_t B, int32_t Hi, int32_t Wi, int32_t C, void* stream) {
-  DH_REQUIRE(z_dev && gamma_dev && beta_dev && pooled_dev && idx_dev && mean_dev && invstd_dev && B > 0 && Hi > 0 && Wi > 0 && C >= 64 &&
-             C <= 2048 && C % 64 == 0 && 256 % (C / 8) == 0, "debug bn2 pool: bad arguments");
-  DH_REQUIRE(!dpool_dev || (dz_dev && dgamma_dev && dbeta_dev), "debug bn2 pool: backward needs dz, dgamma, dbeta");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  dh_train2 t;
-  t.B = B;
-  T2Conv c;
-  c.name = "dbg"; c.bn = "dbgbn"; c.cout = C; c.Ho = Hi; c.Wo = Wi; c.ks = 7;
-  int rc;
-  float* buf;
-  if ((rc = sc.get(&buf, (int64_t)11 * C))) return rc;
-  DH_HIP(hipMemsetAsync(buf, 0, 11 * C * sizeof(float), st));
-  t.Pm = buf; t.G = buf + 2 * C; t.R = buf + 4 * C;
-  t.slot["dbgbn.weight"] = {0, C}; t.slot["dbgbn.bias"] = {C, C};
-  t.rslot["dbgbn.running_mean"] = {0, C}; t.rslot["dbgbn.running_var"] = {C, C};
-  DH_HIP(hipMemcpyAsync(t.Pm, gamma_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  DH_HIP(hipMemcpyAsync(t.Pm + C, beta_dev, C * sizeof(float), hipMemcpyDeviceToDevice, st));
-  c.bnb.mean = mean_dev; c.bnb.invstd = invstd_dev; c.bnb.scale = buf + 6 * C; c.bnb.shift = buf + 7 * C;
-  c.bnb.k0 = buf + 8 * C; c.bnb.k1 = buf + 9 * C; c.bnb.k2 = buf + 10 * C;
-  if ((rc = sc.get(&t.partial, T2_PARTIAL_FLOATS))) return rc;
-  c.Z = const_cast<bf16_t*>(z_dev);
-  rc = t2_bn_fwd(&t, c, nullptr, true, true, st, false, pooled_dev, idx_dev);
-  if (!rc && dpool_dev) {
-    rc = t2_bn_pool_bwd(&t, c, dpool_dev, idx_dev, dz_dev, st);
-    if (!rc && (hipMemcpyAsync(dgamma_dev, t.G, C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(dbeta_dev, t.G + C, C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)) rc = DH_EHIP;
-  }
-  if (rc) { (void)hipStreamSynchronize(st); return rc; }
-  return dbg_finish(st, "debug bn2 pool");
-}
-
-// The bf16 engine's stem weight gradient on caller data: dz bf16 [B][P/2][P/2][64] (NHWC), x float32 [B][3][P][P] -> dW float32 [64][3][7][7]
-// (x is rounded to bf16 on its way into LDS, as the forward stem does)
-extern "C" int dh_debug_stem_wgrad_bf16(const uint16_t* dz_dev, const float* x_nchw_dev, float* dw_dev, int32_t B, int32_t P, void* stream) {
-  DH_REQUIRE(dz_dev && x_nchw_dev && dw_dev && B > 0 && P >= 32 && P % 2 == 0, "debug stem wgrad: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  float* slabs;
-  int rc = sc.get(&slabs, (int64_t)STEM_WGRAD_SLABS * 64 * 160);
-  if (rc) return rc;
-  const int Ho = P / 2, total_rows = B * Ho;
-  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS, n_slabs = (total_rows + rpb - 1) / rpb;
-  if ((rc = t2_stem_wgrad(dz_dev, x_nchw_dev, slabs, B, P, Ho, Ho, rpb, n_slabs, st))) return rc;
-  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw_dev);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug stem wgrad bf16");
-}
-
-// Test hooks of the remaining HBM-bound kernels of the bf16 engine (bf16 bits as uint16, channels-last):
-//   maxpool2   : 3x3 / 2 pad 1 forward (y, first-maximum positions) and, when dy_dev is given, backward dx [B][Hi][Wi][C];
-//   upsample2  : dx[b][2i][2j][:] += t[b][i][j][:]   (the stride-2 downsample branch's gradient joining a block input);
-//   avgpool_fc : dX[b][q][c] = (sum_k dlogits[b][k] w[k][c]) / HW   (global average pool + fc, backward).
-extern "C" int dh_debug_maxpool2_bf16(const uint16_t* x_dev, uint16_t* y_dev, const uint16_t* dy_dev, uint16_t* dx_dev, int32_t B, int32_t Hi,
-                                      int32_t Wi, int32_t C, void* stream) {
-  DH_REQUIRE(x_dev && y_dev && B > 0 && Hi > 0 && Wi > 0 && C % 8 == 0 && (!dy_dev || dx_dev), "debug maxpool2: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-  DbgScratch sc;
-  uint8_t* idx;
-  int rc = sc.get(&idx, (int64_t)B * Ho * Wo * C);
-  if (rc) return rc;
-  hipLaunchKernelGGL(maxpool2_fwd_idx_kernel, dim3(grid_for((int64_t)B * Ho * Wo * C / 8)), dim3(256), 0, st, x_dev, y_dev, idx, B, Hi, Wi, C, Ho, Wo);
-  if (dy_dev)
-    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((int64_t)B * Hi * Wi * C / 8)), dim3(256), 0, st, idx, dy_dev, dx_dev, B, Hi, Wi, C, Ho, Wo);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug maxpool2");
-}
-// ... the same pair with the recorded first-maximum positions returned: idx_dev [B][Ho][Wo][C] bytes, dyy * 3 + dxx of the 3x3 window
-extern "C" int dh_debug_maxpool2_idx_bf16(const uint16_t* x_dev, uint16_t* y_dev, uint8_t* idx_dev, const uint16_t* dy_dev, uint16_t* dx_dev,
-                                          int32_t B, int32_t Hi, int32_t Wi, int32_t C, void* stream) {
-  DH_REQUIRE(x_dev, "debug maxpool2 idx: null input (x_dev)");
-  DH_REQUIRE(y_dev && idx_dev, "debug maxpool2 idx: null output (y_dev or idx_dev)");
-  DH_REQUIRE(!dy_dev || dx_dev, "debug maxpool2 idx: backward (dy_dev given) needs dx_dev");
-  DH_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "debug maxpool2 idx: B=%d Hi=%d Wi=%d", B, Hi, Wi);
-  DH_REQUIRE(C > 0 && C % 8 == 0, "debug maxpool2 idx: C=%d (a positive multiple of 8)", C);
-  hipStream_t st = dh::as_stream(stream);
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-  hipLaunchKernelGGL(maxpool2_fwd_idx_kernel, dim3(grid_for((int64_t)B * Ho * Wo * C / 8)), dim3(256), 0, st, x_dev, y_dev, idx_dev, B, Hi, Wi, C, Ho, Wo);
-  if (dy_dev)
-    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((int64_t)B * Hi * Wi * C / 8)), dim3(256), 0, st, idx_dev, dy_dev, dx_dev, B, Hi, Wi, C, Ho, Wo);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug maxpool2 idx");
-}
-extern "C" int dh_debug_upsample2_add_bf16(const uint16_t* t_dev, uint16_t* dx_dev, int32_t B, int32_t Ho, int32_t Wo, int32_t Hi, int32_t Wi,
-                                           int32_t C, void* stream) {
-  DH_REQUIRE(t_dev && dx_dev && B > 0 && C % 8 == 0 && 2 * (Ho - 1) < Hi && 2 * (Wo - 1) < Wi, "debug upsample2: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  hipLaunchKernelGGL(upsample2_add_bf16_kernel, dim3(grid_for((int64_t)B * Ho * Wo * C / 8)), dim3(256), 0, st, t_dev, dx_dev, B, Ho, Wo, Hi, Wi, C);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug upsample2");
-}
-extern "C" int dh_debug_avgpool_fc_dgrad2(const float* dlogits_dev, const float* w_dev, uint16_t* dx_dev, int32_t B, int32_t HW, int32_t C,
-                                          int32_t n_cls, void* stream) {
-  DH_REQUIRE(dlogits_dev && w_dev && dx_dev && B > 0 && HW > 0 && C % 8 == 0 && n_cls > 0, "debug avgpool fc: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, dx_dev);
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug avgpool fc");
-}
-// The classifier head of both engines on caller data, in the order a step launches it: global average pool (x_bf16 = 0: avgpool_kernel on
-// float32 x, the float32 engine; 1: avgpool2_kernel on bf16 x, the bf16 engine), fc_fwd_kernel, fc_wgrad_kernel on the caller's dlogits and
-// the pooled features just made, and the matching avgpool_fc_dgrad kernel (float32 / bf16 dx).  x, dx [B][HW][C]; w [n_cls][C]; bias [n_cls];
-// dlogits, logits [B][n_cls]; pooled [B][C]; dw [n_cls][C]; db [n_cls].
-extern "C" int dh_debug_head(const void* x_dev, int32_t x_bf16, const float* w_dev, const float* bias_dev, const float* dlogits_dev,
-                             float* pooled_dev, float* logits_dev, float* dw_dev, float* db_dev, void* dx_dev, int32_t B, int32_t HW,
-                             int32_t C, int32_t n_cls, void* stream) {
-  DH_REQUIRE(x_dev && w_dev && bias_dev && dlogits_dev, "debug head: null input (x_dev, w_dev, bias_dev or dlogits_dev)");
-  DH_REQUIRE(pooled_dev && logits_dev && dw_dev && db_dev && dx_dev, "debug head: null output (pooled_dev, logits_dev, dw_dev, db_dev or dx_dev)");
-  DH_REQUIRE(x_bf16 == 0 || x_bf16 == 1, "debug head: x_bf16=%d (0 float32, 1 bf16)", x_bf16);
-  DH_REQUIRE(B > 0 && B <= 65535, "debug head: B=%d", B);
-  DH_REQUIRE(HW > 0, "debug head: HW=%d", HW);
-  DH_REQUIRE(C > 0 && C % 8 == 0, "debug head: C=%d (a positive multiple of 8)", C);
-  DH_REQUIRE(n_cls > 0 && n_cls <= 1024, "debug head: n_cls=%d", n_cls);
-  hipStream_t st = dh::as_stream(stream);
-  if (x_bf16) hipLaunchKernelGGL(avgpool2_kernel, dim3(B), dim3(256), 0, st, static_cast<const bf16_t*>(x_dev), HW, C, pooled_dev);
-  else hipLaunchKernelGGL(avgpool_kernel, dim3(B), dim3(256), 0, st, static_cast<const float*>(x_dev), HW, C, pooled_dev);
-  hipLaunchKernelGGL(fc_fwd_kernel, dim3((B * n_cls + 3) / 4), dim3(256), 0, st, pooled_dev, w_dev, bias_dev, B, C, n_cls, logits_dev);
-  hipLaunchKernelGGL(fc_wgrad_kernel, dim3((n_cls * C + 255) / 256), dim3(256), 0, st, dlogits_dev, pooled_dev, B, C, n_cls, dw_dev, db_dev);
-  if (x_bf16) hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, static_cast<bf16_t*>(dx_dev));
-  else hipLaunchKernelGGL(avgpool_fc_dgrad_kernel, dim3(B), dim3(256), 0, st, dlogits_dev, w_dev, HW, C, n_cls, static_cast<float*>(dx_dev));
-  DH_LAUNCH_CHECK();
-  return dbg_finish(st, "debug head");
-}
-
-// One convolution of the bf16 engine on caller data, forward or data gradient, through the step's own launch code: the operands are
-// packed from float32 w[cout][cin][ks][ks] by pack_all_kernel (3x3: fragment order and its flipped / transposed twin; 1x1: W and Wt),
-// then t2_conv_fwd (t2_conv3 / t2_gemm) or t2_conv_dgrad runs on a scratch engine object and picks tile and variant as in a step.
-//   dgrad = 0 : in = x [B][Hi][Wi][cin], out = Z [B][Ho][Wo][cout] (raw, no epilogue); res must be null
-//   dgrad = 1 : in = dZ [B][Ho][Wo][cout], out = dX [B][Hi][Wi][cin] (+ res, the joining gradient, may be null); 1x1 / stride 2 is the
-//               engine's accumulate contract: out starts from res (or zero) and the low-resolution product (bf16 scratch) is added into it
-// Hi x Wi is always the convolution's INPUT size.
-extern "C" int dh_debug_conv_bf16(const uint16_t* in_dev, const float* w_dev, const uint16_t* res_dev, uint16_t* out_dev, int32_t B,
-                                  int32_t Hi, int32_t Wi, int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t dgrad,
-                                  void* stream) {
-  DH_REQUIRE(in_dev && w_dev && out_dev, "debug conv bf16: in, w and out must be given");
-  DH_REQUIRE(B > 0 && Hi > 0 && Wi > 0, "debug conv bf16: B=%d Hi=%d Wi=%d must be positive", B, Hi, Wi);
-  DH_REQUIRE(ks == 1 || ks == 3, "debug conv bf16: ks=%d is not 1 or 3", ks);
-  DH_REQUIRE(stride == 1 || stride == 2, "debug conv bf16: stride=%d is not 1 or 2", stride);
-  DH_REQUIRE(cin > 0 && cin % 64 == 0, "debug conv bf16: cin=%d is not a multiple of 64", cin);
-  DH_REQUIRE(cout > 0 && cout % 64 == 0, "debug conv bf16: cout=%d is not a multiple of 64", cout);
-  DH_REQUIRE(stride == 1 || Hi % 2 == 0, "debug conv bf16: Hi=%d is odd at stride 2 (the engine's maps are even: P %% 32 == 0)", Hi);
-  DH_REQUIRE(stride == 1 || Wi % 2 == 0, "debug conv bf16: Wi=%d is odd at stride 2 (the engine's maps are even: P %% 32 == 0)", Wi);
-  DH_REQUIRE(dgrad == 0 || dgrad == 1, "debug conv bf16: dgrad=%d is not 0 or 1", dgrad);
-  DH_REQUIRE(dgrad == 1 || !res_dev, "debug conv bf16: res belongs to the data gradient (dgrad = 1); the forward conv is raw Z");
-  hipStream_t st = dh::as_stream(stream);
-  DbgScratch sc;
-  dh_train2 t;
-  t.B = B;
-  T2Conv c;
-  c.name = "dbg"; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
-  c.Hi = Hi; c.Wi = Wi; c.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; c.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  const int64_t nw = (int64_t)cout * cin * ks * ks, nx = (int64_t)B * Hi * Wi * cin, nz = (int64_t)B * c.Ho * c.Wo * cout;
-  DH_REQUIRE(std::max(nx, nz) * 2 < ((int64_t)1 << 32), "debug conv bf16: B=%d makes a tensor of 4 GiB or more", B);
-  bf16_t *wf, *wd, *scratch = nullptr;
-  PackDesc* dd;
-  int rc;
-  if ((rc = sc.get(&wf, nw)) || (rc = sc.get(&wd, nw)) || (rc = sc.get(&dd, 1)) || (rc = sc.get(&t.ones, 2048)) || (rc = sc.get(&t.zeros, 2048))) return rc;
-  DH_HIP(hipMemsetAsync(t.zeros, 0, 2048 * sizeof(float), st));
-  hipLaunchKernelGGL(fill_kernel, dim3(8), dim3(256), 0, st, t.ones, (int64_t)2048, 1.0f);
-  const PackDesc hd{w_dev, wf, wd, cout, cin, ks, 0};
-  DH_HIP(hipMemcpyAsync(dd, &hd, sizeof hd, hipMemcpyHostToDevice, st));
-  DH_HIP(hipStreamSynchronize(st));   // `hd` is a stack object
-  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&pack_all_kernel), PACK3_LDS))) return rc;
-  const int tiles = (cout / 64) * (cin / 64);   // workgroups as t2_pack counts them
-  hipLaunchKernelGGL(pack_all_kernel, dim3(ks == 3 ? tiles : std::min(64, tiles)), dim3(256), PACK3_LDS, st, dd, 1, 0);
-  DH_LAUNCH_CHECK();
-  c.wp_f = wf; c.wp_d = wd;
-  if (!dgrad) {
-    c.Z = out_dev;
-    rc = t2_conv_fwd(&t, c, in_dev, st);
-  } else if (ks == 1 && stride == 2) {   // a downsample branch: the step has already written the other branch's gradient into dX
-    if ((rc = sc.get(&scratch, nz / cout * cin))) return rc;
-    if (res_dev) DH_HIP(hipMemcpyAsync(out_dev, res_dev, nx * sizeof(bf16_t), hipMemcpyDeviceToDevice, st));
-    else DH_HIP(hipMemsetAsync(out_dev, 0, nx * sizeof(bf16_t), st));
-    rc = t2_conv_dgrad(&t, c, in_dev, nullptr, out_dev, scratch, true, st);
-  } else {
-    rc = t2_conv_dgrad(&t, c, in_dev, res_dev, out_dev, nullptr, false, st);
-  }
-  if (rc) { (void)hipStreamSynchronize(st); return rc; }
-  return dbg_finish(st, "debug conv bf16");
-}
-
-extern "C" int dh_debug_wgrad_bf16(const uint16_t* dz_dev, const uint16_t* x_dev, float* dw_dev, int32_t B, int32_t Hi, int32_t Wi,
-                                   int32_t cin, int32_t cout, int32_t ks, int32_t stride, int32_t repeat, void* stream) {
-  DH_REQUIRE(dz_dev && x_dev && dw_dev && (ks == 1 || ks == 3) && cin % 64 == 0 && cout % 64 == 0 && repeat >= 1, "debug wgrad bf16: bad arguments");
-  hipStream_t st = dh::as_stream(stream);
-  dh_train2 t;
-  t.B = B;
-  T2Conv c;
-  c.name = "dbg"; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
-  c.Hi = Hi; c.Wi = Wi; c.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; c.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  Wg2Plan q;
-  int rc = t2_wgrad_plan(c, B, &q);
-  if (rc) return rc;
-  DbgScratch sc;
-  const int64_t nw = (int64_t)cout * cin * ks * ks;
-  t.wgrad_slab_floats = (int64_t)q.n_slabs * nw;
-  if ((rc = sc.get(&t.wgrad_slabs, t.wgrad_slab_floats))) return rc;
-  t.G = dw_dev;
-  t.slot["dbg.weight"] = {0, nw};
-  for (int i = 0; i < repeat; ++i)
-    if ((rc = t2_wgrad(&t, c, x_dev, dz_dev, st))) return rc;
-  return dbg_finish(st, "debug wgrad bf16");
 }

@@ -415,6 +415,40 @@ def test_bn2_bf16_kernels(dev, rows, C, relu, with_res, mode):
         assert torch.equal(gout.float().cpu(), (dy * (y.float().cpu() > 0).float()))
 
 
+@pytest.mark.parametrize("with_res,mode", [(True, 1), (False, 2)])
+@pytest.mark.parametrize("rows", [1000, 16448])
+def test_bn2_hook_equals_the_paths_hook(dev, rows, with_res, mode):
+    """dh_debug_bn2_bf16 is dh_debug_bn2_paths_bf16 with the engine's default fold (1), no pattern bytes and no join: the same operands
+    through both give the same bits in y, mean, invstd, dz, g_out, dgamma and dbeta.  C = 64; rows on either side of the DH_T2_FOLD_ROWS
+    default of 16384 (a folded small map, and the finalize launch + elementwise pass); residual + ReLU pattern from y with the masked
+    gradient written, and no residual + pattern recomputed from z."""
+    from deephisto_amd._lib import check, lib
+    C = 64
+    g = torch.Generator().manual_seed(rows + mode)
+    zd = (torch.randn(rows, C, generator=g) * (torch.rand(C, generator=g) + 0.5) + torch.randn(C, generator=g)).to(dev).bfloat16()
+    rd = torch.randn(rows, C, generator=g).to(dev).bfloat16() if with_res else None
+    gd, bd = (torch.rand(C, generator=g) + 0.5).to(dev), (torch.randn(C, generator=g) * 0.3).to(dev)
+    dyd = (torch.randn(rows, C, generator=g) * 1e-3).to(dev).bfloat16()
+    ptr = lambda t: t.data_ptr() if t is not None else None
+
+    def outputs():
+        o = {k: torch.full((rows, C), float("nan"), dtype=torch.bfloat16, device=dev) for k in ("y", "dz")}
+        o["g_out"] = torch.full((rows, C), float("nan"), dtype=torch.bfloat16, device=dev) if mode == 1 else None
+        o.update({k: torch.full((C,), float("nan"), dtype=torch.float32, device=dev) for k in ("mean", "invstd", "dgamma", "dbeta")})
+        return o
+
+    a, b = outputs(), outputs()
+    check(lib().dh_debug_bn2_bf16(ptr(zd), ptr(rd), ptr(gd), ptr(bd), 1, ptr(a["y"]), ptr(a["mean"]), ptr(a["invstd"]), ptr(dyd), mode,
+                                  ptr(a["dz"]), ptr(a["g_out"]), ptr(a["dgamma"]), ptr(a["dbeta"]), rows, C, None), "bn2")
+    check(lib().dh_debug_bn2_paths_bf16(ptr(zd), ptr(rd), ptr(gd), ptr(bd), 1, 1, ptr(b["y"]), None, ptr(b["mean"]), ptr(b["invstd"]),
+                                        None, None, None, None, None, ptr(dyd), mode, ptr(b["dz"]), ptr(b["g_out"]), ptr(b["dgamma"]),
+                                        ptr(b["dbeta"]), rows, C, None), "bn2 paths")
+    for k, t in a.items():
+        if t is not None:
+            assert not bool(torch.isnan(t.float()).any()), k      # written in full
+            assert torch.equal(t, b[k]), k
+
+
 @pytest.mark.parametrize("B,H,C", [(3, 112, 64), (2, 57, 64), (5, 14, 128)])
 def test_maxpool2_bf16_kernels(dev, B, H, C):
     from deephisto_amd._lib import check, lib
