@@ -13,7 +13,7 @@
 namespace {
 
 constexpr int CAM_KC = 8;         // classes per pass over the activation
-constexpr int CAM_MAX_CLS = 64;   // proba.hip's MAX_CLS: the maps built from these rows take no more
+constexpr int CAM_MAX_CLS = 64;   // accumulate.hip's MAX_CLS: the maps built from these rows take no more
 constexpr int CAM_MAX_HW = 1024;
 
 template <typename T, bool BLOCKED>

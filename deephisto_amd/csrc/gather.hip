@@ -1,95 +1,16 @@
-// Tile-side kernels of the deephisto hot path for MI355X (gfx950, wave64):
+// Tile gathers of the deephisto hot path for MI355X (gfx950, wave64):
 //   a1  dh_tile_grid            host integer restatement of the dense grid order
 //   --  dh_synth_slide          closed-form benchmark slide generated in HBM
 //   a2/a4/a5 dh_tile_gather     uint8 HWC slide -> [n,P,P,3] / [n,3,P,P] f32|bf16, exactly k/255
-//   a8  dh_accumulate_logits    ordered (bit-exact) canvas accumulation, dh_argmax_map; dh_accumulate_cam: S x S rows per tile
-// All of these are HBM-bound byte/integer work: no LDS, no MFMA; the design
+//   --  dh_tile_gather_aug / _stain_aug / _affine_aug   the training batch gather: flips, stain jitter, rotation and scale
+//   --  dh_tile_gather_raw, dh_tile_coords_f32          the random-branch sampler's raw tiles and float coordinates
+// All of these are HBM-bound byte/integer work: no MFMA, LDS only for the stain tables; the design
 // rules are full-width coalesced rows (one wave = one tile row) and 16-byte stores.
-#include <errno.h>
-#include <stdarg.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <algorithm>
-#include <vector>
+#include <type_traits>
 
 #include "dh_common.h"
-#include "env_knobs.h"
 #include "stain_fixed.h"
-
-namespace dh {
-static thread_local std::string g_err;
-void set_error(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-}  // namespace dh
-
-namespace dh {
-namespace {
-struct EnvKnob { const char* name; long def, lo, hi; const char* read; const char* effect; };
-#define DH_ENV_ROW(n, d, l, h, r, e) {#n, (long)(d), (long)(l), (long)(h), r, e},
-const EnvKnob g_env_knobs[] = {DH_ENV_KNOBS(DH_ENV_ROW)};
-#undef DH_ENV_ROW
-// 0: unset (default), 1: valid (*out), -1: set but not a decimal integer in [lo, hi]
-int env_parse(const EnvKnob& k, long* out) {
-  const char* v = getenv(k.name);
-  *out = k.def;
-  if (!v) return 0;
-  char* end = nullptr;
-  errno = 0;
-  const long x = strtol(v, &end, 10);
-  if (end == v || *end != '\0' || errno != 0 || x < k.lo || x > k.hi) return -1;
-  *out = x;
-  return 1;
-}
-void env_complain(const EnvKnob& k) {
-  set_error("%s='%s' is not an integer in [%ld, %ld] (default %ld): %s", k.name, getenv(k.name), k.lo, k.hi, k.def, k.effect);
-}
-}  // namespace
-
-int env_int(const char* name) {
-  for (const EnvKnob& k : g_env_knobs)
-    if (!strcmp(k.name, name)) {
-      long v;
-      if (env_parse(k, &v) < 0) {
-        env_complain(k);
-        fprintf(stderr, "libdeephisto_hip: %s -- default used\n", g_err.c_str());
-      }
-      return (int)v;
-    }
-  fprintf(stderr, "libdeephisto_hip: internal error: environment knob %s is not in env_knobs.h\n", name);
-  abort();
-}
-
-int env_check() {
-  for (const EnvKnob& k : g_env_knobs) {
-    long v;
-    if (env_parse(k, &v) < 0) { env_complain(k); return DH_EINVAL; }
-  }
-  return DH_OK;
-}
-}  // namespace dh
-
-// test hook: the table of env_knobs.h as text, one "NAME default lo hi read" line per knob (INTEGRATION.md carries the same table)
-extern "C" int dh_debug_env_knobs(char* buf, int64_t cap) {
-  std::string s;
-  char line[256];
-  for (const dh::EnvKnob& k : dh::g_env_knobs) {
-    snprintf(line, sizeof line, "%s %ld %ld %ld %s\n", k.name, k.def, k.lo, k.hi, k.read);
-    s += line;
-  }
-  DH_REQUIRE(buf && (int64_t)s.size() + 1 <= cap, "dh_debug_env_knobs: buffer of %lld bytes too small (%zu needed)", (long long)cap, s.size() + 1);
-  memcpy(buf, s.c_str(), s.size() + 1);
-  return DH_OK;
-}
-
-extern "C" int dh_abi_version(void) { return 1; }
-extern "C" const char* dh_last_error(void) { return dh::g_err.c_str(); }
 
 // ---------------------------------------------------------------------------
 // a1: tile grid (host).  Reference: patch_samplers/full_samplers.py:374-404.
@@ -220,6 +141,28 @@ __device__ __forceinline__ void st_u2(uint16_t* p, uint32_t x, uint32_t y) {
   else *reinterpret_cast<uint2*>(p) = make_uint2(x, y);
 }
 
+// The (layout, dtype) codes of deephisto_hip.h: the one test of what is a code, and the one place that turns a pair of codes into
+// the kernels' <BF16, NCHW> template pair -- `launch` is a generic lambda called with the two as std::bool_constant values.
+static inline bool known_layout(int32_t layout) { return layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW; }
+static inline bool known_dtype(int32_t dtype) { return dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16; }
+
+static int require_layout_dtype(const char* who, int32_t layout, int32_t dtype) {
+  DH_REQUIRE(known_layout(layout), "%s: bad layout %d", who, layout);
+  DH_REQUIRE(known_dtype(dtype), "%s: bad dtype %d", who, dtype);
+  return DH_OK;
+}
+
+template <class Launch>
+static void for_layout_dtype(int32_t layout, int32_t dtype, Launch&& launch) {
+  if (layout == DH_LAYOUT_NCHW) {
+    if (dtype == DH_DTYPE_F32) launch(std::false_type{}, std::true_type{});
+    else launch(std::true_type{}, std::true_type{});
+  } else {
+    if (dtype == DH_DTYPE_F32) launch(std::false_type{}, std::false_type{});
+    else launch(std::true_type{}, std::false_type{});
+  }
+}
+
 // NCHW: one wave = one tile row; lane j owns pixels 4j..4j+3 (12 contiguous bytes) and
 // writes one 16-B (f32) / 8-B (bf16) store into each of the three planes.
 template <bool BF16>
@@ -319,8 +262,7 @@ extern "C" int dh_tile_gather(const uint8_t* slide, int64_t h, int64_t w, const 
   DH_REQUIRE(slide && yx_dev && out, "tile gather: null pointer");
   DH_REQUIRE(P > 0 && h >= P && w >= P, "tile gather: patch %d does not fit %lldx%lld", P,
              (long long)h, (long long)w);
-  DH_REQUIRE(layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW, "tile gather: bad layout %d", layout);
-  DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "tile gather: bad dtype %d", dtype);
+  if (const int rc = require_layout_dtype("tile gather", layout, dtype)) return rc;
   if (yx_host_check)
     for (int64_t i = 0; i < n; ++i) {
       const int64_t y = yx_host_check[2 * i], x = yx_host_check[2 * i + 1];
@@ -328,31 +270,19 @@ extern "C" int dh_tile_gather(const uint8_t* slide, int64_t h, int64_t w, const 
                  "tile gather: origin %lld = (%lld,%lld) outside slide", (long long)i, (long long)y,
                  (long long)x);
     }
-  const int esz = dtype == DH_DTYPE_F32 ? 4 : 2;
   const bool fast = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-  (void)esz;
   hipStream_t st = dh::as_stream(stream);
   const int64_t rb = w * 3;
-  if (fast) {
-    dim3 grid((P + GATHER_ROWS - 1) / GATHER_ROWS, (unsigned)n), block(256);
-    if (layout == DH_LAYOUT_NCHW) {
-      if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL(gather_nchw_kernel<false>, grid, block, 0, st, slide, rb, yx_dev, P, out);
-      else hipLaunchKernelGGL(gather_nchw_kernel<true>, grid, block, 0, st, slide, rb, yx_dev, P, out);
-    } else {
-      if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL(gather_nhwc_kernel<false>, grid, block, 0, st, slide, rb, yx_dev, P, out);
-      else hipLaunchKernelGGL(gather_nhwc_kernel<true>, grid, block, 0, st, slide, rb, yx_dev, P, out);
-    }
-  } else {
-    const int64_t per_tile = (int64_t)P * P * 3;
-    dim3 grid((unsigned)std::min<int64_t>((per_tile + 255) / 256, 1024), (unsigned)n), block(256);
-    if (layout == DH_LAYOUT_NCHW) {
-      if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL((gather_generic_kernel<false, true>), grid, block, 0, st, slide, rb, yx_dev, P, out);
-      else hipLaunchKernelGGL((gather_generic_kernel<true, true>), grid, block, 0, st, slide, rb, yx_dev, P, out);
-    } else {
-      if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL((gather_generic_kernel<false, false>), grid, block, 0, st, slide, rb, yx_dev, P, out);
-      else hipLaunchKernelGGL((gather_generic_kernel<true, false>), grid, block, 0, st, slide, rb, yx_dev, P, out);
-    }
-  }
+  const int64_t per_tile = (int64_t)P * P * 3;
+  const dim3 block(256);
+  const dim3 grid = fast ? dim3((P + GATHER_ROWS - 1) / GATHER_ROWS, (unsigned)n)
+                         : dim3((unsigned)std::min<int64_t>((per_tile + 255) / 256, 1024), (unsigned)n);
+  for_layout_dtype(layout, dtype, [&](auto bf16, auto nchw) {
+    constexpr bool BF = decltype(bf16)::value, NC = decltype(nchw)::value;
+    if (!fast) hipLaunchKernelGGL((gather_generic_kernel<BF, NC>), grid, block, 0, st, slide, rb, yx_dev, P, out);
+    else if constexpr (NC) hipLaunchKernelGGL(gather_nchw_kernel<BF>, grid, block, 0, st, slide, rb, yx_dev, P, out);
+    else hipLaunchKernelGGL(gather_nhwc_kernel<BF>, grid, block, 0, st, slide, rb, yx_dev, P, out);
+  });
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -388,19 +318,15 @@ extern "C" int dh_tile_gather_aug(const uint8_t* slide, int64_t h, int64_t w, co
   DH_REQUIRE(n >= 0 && n <= 65535, "tile gather aug: n=%lld out of range", (long long)n);
   if (n == 0) return DH_OK;
   DH_REQUIRE(slide && yx_dev && out && P > 0 && h >= P && w >= P && h <= INT32_MAX && w <= INT32_MAX, "tile gather aug: bad arguments");
-  DH_REQUIRE((layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW) && (dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16),
-             "tile gather aug: bad layout/dtype");
+  DH_REQUIRE(known_layout(layout) && known_dtype(dtype), "tile gather aug: bad layout/dtype");
   hipStream_t st = dh::as_stream(stream);
   const int64_t per_tile = (int64_t)P * P * 3;
   dim3 grid((unsigned)std::min<int64_t>((per_tile + 255) / 256, 1024), (unsigned)n), block(256);
   const int64_t rb = w * 3;
-  if (layout == DH_LAYOUT_NCHW) {
-    if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL((gather_aug_kernel<false, true>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
-    else hipLaunchKernelGGL((gather_aug_kernel<true, true>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
-  } else {
-    if (dtype == DH_DTYPE_F32) hipLaunchKernelGGL((gather_aug_kernel<false, false>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
-    else hipLaunchKernelGGL((gather_aug_kernel<true, false>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, P, flip_h, flip_v, out);
-  }
+  for_layout_dtype(layout, dtype, [&](auto bf16, auto nchw) {
+    hipLaunchKernelGGL((gather_aug_kernel<decltype(bf16)::value, decltype(nchw)::value>), grid, block, 0, st, slide, rb, (int)h, (int)w,
+                       yx_dev, P, flip_h, flip_v, out);
+  });
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -472,11 +398,28 @@ __global__ __launch_bounds__(256) void gather_stain_aug_kernel(const uint8_t* __
   }
 }
 
+// What both stain entries ask of the stain arguments; `who` opens every message.
+static int require_stain_args(const char* who, int32_t lut_n, const uint8_t* lut_dev, int32_t shift, const int32_t* od_host,
+                              const int32_t* params_host_check, int64_t n) {
+  using namespace dh_stain;
+  DH_REQUIRE(lut_n > 0 && lut_n <= kLutMax, "%s: lut_n = %d, an output table has 1 to %d entries", who, lut_n, kLutMax);
+  DH_REQUIRE(((uintptr_t)lut_dev & 15) == 0, "%s: lut_dev must be 16-byte aligned", who);
+  DH_REQUIRE(shift >= 0 && shift < 40, "%s: shift %d outside [0, 40)", who, shift);
+  for (int i = 0; i < 256; ++i)
+    DH_REQUIRE(od_host[i] >= 0 && od_host[i] <= kOdMax, "%s: od table entry %d = %d outside [0, %d]", who, i, od_host[i], kOdMax);
+  if (params_host_check)
+    for (int64_t i = 0; i < 12 * n; ++i) {
+      const int32_t v = params_host_check[i], lim = i % 12 < 9 ? kCoefMax : kBiasMax;
+      DH_REQUIRE(v >= -lim && v <= lim, "%s: params row %lld, %s entry %d = %d outside +-%d", who, (long long)(i / 12),
+                 i % 12 < 9 ? "matrix" : "bias", (int)(i % 12 < 9 ? i % 12 : i % 12 - 9), v, lim);
+    }
+  return DH_OK;
+}
+
 extern "C" int dh_tile_gather_stain_aug(const uint8_t* slide, int64_t h, int64_t w, const int32_t* yx_dev, const int32_t* params_dev,
                                         const int32_t* params_host_check, int64_t n, int32_t P, int32_t layout, int32_t dtype,
                                         int32_t flip_h, int32_t flip_v, const int32_t* od_dev, const int32_t* od_host, int32_t shift,
                                         const uint8_t* lut_dev, int32_t lut_n, void* out, void* stream) {
-  using namespace dh_stain;
   DH_REQUIRE(n >= 0 && n <= 65535, "tile gather stain aug: n=%lld out of range [0, 65535]", (long long)n);
   if (n == 0) return DH_OK;
   DH_REQUIRE(slide && yx_dev && params_dev && od_dev && od_host && lut_dev && out, "tile gather stain aug: null pointer");
@@ -484,36 +427,17 @@ extern "C" int dh_tile_gather_stain_aug(const uint8_t* slide, int64_t h, int64_t
              (long long)w);
   DH_REQUIRE(P > 0 && h >= P && w >= P && P <= INT32_MAX - kStainPxPerWg, "tile gather stain aug: patch %d does not fit %lldx%lld", P,
              (long long)h, (long long)w);
-  DH_REQUIRE(layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW, "tile gather stain aug: bad layout %d", layout);
-  DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "tile gather stain aug: bad dtype %d", dtype);
-  DH_REQUIRE(lut_n > 0 && lut_n <= kLutMax, "tile gather stain aug: lut_n = %d, an output table has 1 to %d entries", lut_n, kLutMax);
-  DH_REQUIRE(((uintptr_t)lut_dev & 15) == 0, "tile gather stain aug: lut_dev must be 16-byte aligned");
-  DH_REQUIRE(shift >= 0 && shift < 40, "tile gather stain aug: shift %d outside [0, 40)", shift);
-  for (int i = 0; i < 256; ++i)
-    DH_REQUIRE(od_host[i] >= 0 && od_host[i] <= kOdMax, "tile gather stain aug: od table entry %d = %d outside [0, %d]", i, od_host[i],
-               kOdMax);
-  if (params_host_check)
-    for (int64_t i = 0; i < 12 * n; ++i) {
-      const int32_t v = params_host_check[i], lim = i % 12 < 9 ? kCoefMax : kBiasMax;
-      DH_REQUIRE(v >= -lim && v <= lim, "tile gather stain aug: params row %lld, %s entry %d = %d outside +-%d", (long long)(i / 12),
-                 i % 12 < 9 ? "matrix" : "bias", (int)(i % 12 < 9 ? i % 12 : i % 12 - 9), v, lim);
-    }
+  if (const int rc = require_layout_dtype("tile gather stain aug", layout, dtype)) return rc;
+  if (const int rc = require_stain_args("tile gather stain aug", lut_n, lut_dev, shift, od_host, params_host_check, n)) return rc;
   const int64_t blocks = ((int64_t)P * P + kStainPxPerWg - 1) / kStainPxPerWg;
   DH_REQUIRE(blocks <= INT32_MAX, "tile gather stain aug: patch %d too large", P);
   hipStream_t st = dh::as_stream(stream);
   dim3 grid((unsigned)blocks, (unsigned)n), block(256);
   const int64_t rb = w * 3;
-#define DH_STAIN_AUG_LAUNCH(BF, NC)                                                                                              \
-  hipLaunchKernelGGL((gather_stain_aug_kernel<BF, NC>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, params_dev, P, flip_h, \
-                     flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out)
-  if (layout == DH_LAYOUT_NCHW) {
-    if (dtype == DH_DTYPE_F32) DH_STAIN_AUG_LAUNCH(false, true);
-    else DH_STAIN_AUG_LAUNCH(true, true);
-  } else {
-    if (dtype == DH_DTYPE_F32) DH_STAIN_AUG_LAUNCH(false, false);
-    else DH_STAIN_AUG_LAUNCH(true, false);
-  }
-#undef DH_STAIN_AUG_LAUNCH
+  for_layout_dtype(layout, dtype, [&](auto bf16, auto nchw) {
+    hipLaunchKernelGGL((gather_stain_aug_kernel<decltype(bf16)::value, decltype(nchw)::value>), grid, block, 0, st, slide, rb, (int)h,
+                       (int)w, yx_dev, params_dev, P, flip_h, flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out);
+  });
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -526,8 +450,11 @@ extern "C" int dh_tile_gather_stain_aug(const uint8_t* slide, int64_t h, int64_t
 // v = ((a (256 - fx) + b fx)(256 - fy) + (c (256 - fx) + d fx) fy + 32768) >> 16, and v goes where the slide byte goes in the
 // kernels above: div255(v), or od -> matrix + bias -> lut -> div255 when STAIN.  A pixel none of whose taps of non-zero weight
 // lies inside the slide is written as 0 and not transformed, which for an identity row is the rule of gather_stain_aug_kernel.
-// One thread per output pixel in output order; the tile's 4 (+ 12) parameters are uniform loads; each lane reads two 6-byte row
+// The tile's 4 (+ 12) parameters are uniform loads; each lane reads two 6-byte row
 // pairs straight from the slide (neighbouring lanes walk a rotated line: a wave's taps stay within a few cache lines).
+// The table staging, the stain stage, the pixel of a workgroup and the stores are spelled out here as in gather_stain_aug_kernel:
+// written over shared device helpers this kernel's bf16 rows measured 0.7-1.1 % slower at the training shape, more than the same
+// code's own spread (profiles/tile_split_ab.json).
 constexpr int kAffineMaxPatch = 4096;   // |U2|, |V2| <= P - 1 < 2^12 and |m| <= 2^16: products below 2^28
 constexpr int kAffineCoefMax = 1 << 16;
 
@@ -628,7 +555,6 @@ extern "C" int dh_tile_gather_affine_aug(const uint8_t* slide, int64_t h, int64_
                                          int64_t n, int32_t P, int32_t layout, int32_t dtype, int32_t flip_h, int32_t flip_v,
                                          const int32_t* od_dev, const int32_t* od_host, int32_t shift, const uint8_t* lut_dev,
                                          int32_t lut_n, void* out, void* stream) {
-  using namespace dh_stain;
   DH_REQUIRE(n >= 0 && n <= 65535, "tile gather affine aug: n=%lld out of range [0, 65535]", (long long)n);
   if (n == 0) return DH_OK;
   DH_REQUIRE(slide && yx_dev && affine_dev && out, "tile gather affine aug: null pointer");
@@ -641,22 +567,9 @@ extern "C" int dh_tile_gather_affine_aug(const uint8_t* slide, int64_t h, int64_
              (long long)w);
   DH_REQUIRE(P >= 1 && P <= kAffineMaxPatch, "tile gather affine aug: patch %d outside [1, %d]", P, kAffineMaxPatch);
   DH_REQUIRE(h >= P && w >= P, "tile gather affine aug: patch %d does not fit %lldx%lld", P, (long long)h, (long long)w);
-  DH_REQUIRE(layout == DH_LAYOUT_NHWC || layout == DH_LAYOUT_NCHW, "tile gather affine aug: bad layout %d", layout);
-  DH_REQUIRE(dtype == DH_DTYPE_F32 || dtype == DH_DTYPE_BF16, "tile gather affine aug: bad dtype %d", dtype);
-  if (stain) {
-    DH_REQUIRE(lut_n > 0 && lut_n <= kLutMax, "tile gather affine aug: lut_n = %d, an output table has 1 to %d entries", lut_n, kLutMax);
-    DH_REQUIRE(((uintptr_t)lut_dev & 15) == 0, "tile gather affine aug: lut_dev must be 16-byte aligned");
-    DH_REQUIRE(shift >= 0 && shift < 40, "tile gather affine aug: shift %d outside [0, 40)", shift);
-    for (int i = 0; i < 256; ++i)
-      DH_REQUIRE(od_host[i] >= 0 && od_host[i] <= kOdMax, "tile gather affine aug: od table entry %d = %d outside [0, %d]", i,
-                 od_host[i], kOdMax);
-    if (params_host_check)
-      for (int64_t i = 0; i < 12 * n; ++i) {
-        const int32_t v = params_host_check[i], lim = i % 12 < 9 ? kCoefMax : kBiasMax;
-        DH_REQUIRE(v >= -lim && v <= lim, "tile gather affine aug: params row %lld, %s entry %d = %d outside +-%d", (long long)(i / 12),
-                   i % 12 < 9 ? "matrix" : "bias", (int)(i % 12 < 9 ? i % 12 : i % 12 - 9), v, lim);
-      }
-  }
+  if (const int rc = require_layout_dtype("tile gather affine aug", layout, dtype)) return rc;
+  if (stain)
+    if (const int rc = require_stain_args("tile gather affine aug", lut_n, lut_dev, shift, od_host, params_host_check, n)) return rc;
   if (affine_host_check)
     for (int64_t i = 0; i < 4 * n; ++i)
       DH_REQUIRE(affine_host_check[i] >= -kAffineCoefMax && affine_host_check[i] <= kAffineCoefMax,
@@ -666,20 +579,15 @@ extern "C" int dh_tile_gather_affine_aug(const uint8_t* slide, int64_t h, int64_
   hipStream_t st = dh::as_stream(stream);
   dim3 grid((unsigned)blocks, (unsigned)n), block(256);
   const int64_t rb = w * 3;
-#define DH_AFFINE_AUG_LAUNCH(BF, NC, ST)                                                                                            \
-  hipLaunchKernelGGL((gather_affine_aug_kernel<BF, NC, ST>), grid, block, 0, st, slide, rb, (int)h, (int)w, yx_dev, affine_dev,    \
-                     params_dev, P, flip_h, flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out)
-#define DH_AFFINE_AUG_PICK(ST)                                  \
-  if (layout == DH_LAYOUT_NCHW) {                               \
-    if (dtype == DH_DTYPE_F32) DH_AFFINE_AUG_LAUNCH(false, true, ST);  \
-    else DH_AFFINE_AUG_LAUNCH(true, true, ST);                  \
-  } else {                                                      \
-    if (dtype == DH_DTYPE_F32) DH_AFFINE_AUG_LAUNCH(false, false, ST); \
-    else DH_AFFINE_AUG_LAUNCH(true, false, ST);                 \
-  }
-  if (stain) { DH_AFFINE_AUG_PICK(true) } else { DH_AFFINE_AUG_PICK(false) }
-#undef DH_AFFINE_AUG_PICK
-#undef DH_AFFINE_AUG_LAUNCH
+  for_layout_dtype(layout, dtype, [&](auto bf16, auto nchw) {
+    constexpr bool BF = decltype(bf16)::value, NC = decltype(nchw)::value;
+    auto launch = [&](auto with_stain) {
+      hipLaunchKernelGGL((gather_affine_aug_kernel<BF, NC, decltype(with_stain)::value>), grid, block, 0, st, slide, rb, (int)h, (int)w,
+                         yx_dev, affine_dev, params_dev, P, flip_h, flip_v, od_dev, (int)shift, lut_dev, (int)lut_n, out);
+    };
+    if (stain) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -722,322 +630,5 @@ extern "C" int dh_tile_coords_f32(const int32_t* yx_dev, int64_t n, float* out, 
   hipLaunchKernelGGL(coords_kernel, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0,
                      dh::as_stream(stream), yx_dev, 2 * n, out);
   DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// a8: ordered accumulation.  The canvas is cut into bins of G x G cells
-// (G = max(1, P/d)); the host builds, per bin, the list of tiles that touch it,
-// in tile order.  One workgroup owns one bin, so every canvas cell has exactly
-// one writer that applies the covering tiles' logits sequentially in the
-// reference's order: float32 results are bit-identical to the NumPy `+=` loop,
-// with no atomics.  Traffic: canvas read+write once, logits/lists from L2.
-// ---------------------------------------------------------------------------
-using dh::BinGeom;
-
-// CAM (dh_accumulate_cam): `logits` holds S x S rows per tile, S = P / 32, one per 32 x 32-pixel position,
-// and a covered cell takes the row of the one position whose 32-pixel sub-tile owns it -- position i = ceil(((cy + 1) d - y) / 32) - 1
-// along y, likewise along x: the sub-tiles' cell ranges partition the tile's.  Same plan, same bins, same order of additions.
-template <bool CAM>
-__global__ __launch_bounds__(256) void accumulate_bins_kernel(
-    const float* __restrict__ logits, const int32_t* __restrict__ yx,
-    const int32_t* __restrict__ bin_start, const int32_t* __restrict__ bin_tiles, BinGeom g,
-    float* __restrict__ canvas) {
-  __shared__ int32_t s_t[256], s_y0[256], s_y1[256], s_x0[256], s_x1[256];
-  __shared__ int32_t s_y[CAM ? 256 : 1], s_x[CAM ? 256 : 1];
-  const int S = g.P >> 5;
-  const int bin = blockIdx.x;
-  const int beg = bin_start[bin], end = bin_start[bin + 1];
-  if (beg == end) return;  // uniform for the block
-  const int by = bin / g.bins_x, bx = bin - by * g.bins_x;
-  const int cells = g.G * g.G, items = cells * g.n_cls;
-  for (int it0 = 0; it0 < items; it0 += 256) {
-    const int it = it0 + threadIdx.x;
-    const int cell = it / g.n_cls, cls = it - cell * g.n_cls;
-    const int cy = by * g.G + cell / g.G, cx = bx * g.G + cell % g.G;
-    const bool live = it < items && cy < g.dh && cx < g.dw;
-    const int64_t addr = ((int64_t)cy * g.dw + cx) * g.n_cls + cls;
-    float acc = live ? canvas[addr] : 0.f;
-    for (int l0 = beg; l0 < end; l0 += 256) {
-      __syncthreads();
-      const int l = l0 + threadIdx.x;
-      if (l < end) {
-        const int t = bin_tiles[l];
-        const int y = yx[2 * t], x = yx[2 * t + 1];
-        s_t[threadIdx.x] = t;
-        s_y0[threadIdx.x] = y / g.d; s_y1[threadIdx.x] = (y + g.P) / g.d;
-        s_x0[threadIdx.x] = x / g.d; s_x1[threadIdx.x] = (x + g.P) / g.d;
-        if constexpr (CAM) { s_y[threadIdx.x] = y; s_x[threadIdx.x] = x; }
-      }
-      __syncthreads();
-      const int m = min(256, end - l0);
-      if (live)
-        for (int k = 0; k < m; ++k)
-          if (cy >= s_y0[k] && cy < s_y1[k] && cx >= s_x0[k] && cx < s_x1[k]) {
-            int64_t row = s_t[k];
-            if constexpr (CAM) row = dh::cam_row(row, S, g.d, cy, cx, s_y[k], s_x[k]);
-            acc = acc + logits[row * g.n_cls + cls];
-          }
-    }
-    if (live) canvas[addr] = acc;
-  }
-}
-
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ canvas, int64_t n_cells,
-                                                     int n_cls, int64_t* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cells;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float* p = canvas + i * n_cls;
-    float best = p[0];
-    int bi = 0;
-    for (int c = 1; c < n_cls; ++c) {  // NumPy argmax: first maximum; a NaN wins once
-      const float v = p[c];
-      if (v > best || (v != v && best == best)) { best = v; bi = c; }
-    }
-    out[i] = bi;
-  }
-}
-
-extern "C" int dh_argmax_map(const float* canvas, int64_t n_cells, int32_t n_cls, int64_t* map,
-                             void* stream) {
-  DH_REQUIRE(canvas && map && n_cells >= 0 && n_cls > 0, "argmax map: bad arguments");
-  if (n_cells == 0) return DH_OK;
-  const int grid = (int)std::min<int64_t>((n_cells + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(argmax_kernel, dim3(grid), dim3(256), 0, dh::as_stream(stream), canvas, n_cells,
-                     n_cls, map);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// The bin lists depend only on (origins, P, d, h, w): whole-slide prediction repeats the same
-// grid slide after slide, so the last plan (host CSR + its device copies) is kept and reused
-// when the origins compare equal -- no rebuild, no upload, no stream synchronisation.  Shared by
-// every ordered accumulation (dh_accumulate_logits, dh_accumulate_mean): the class map and the
-// probabilities of one slide are built from one plan.
-namespace dh {
-int bin_plan(const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int64_t h, int64_t w, hipStream_t st, BinPlan* out) {
-  struct Plan {
-    std::vector<int32_t> yx; int32_t P = 0, d = 0; int64_t h = 0, w = 0, nbins = 0, total = 0; int G = 0, bins_x = 0;
-    int32_t *d_start = nullptr, *d_tiles = nullptr, *d_yx = nullptr; int device = -1;
-  };
-  static thread_local Plan plan;
-  const int64_t dh_ = h / d, dw_ = w / d;
-  int dev_id = 0;
-  DH_HIP(hipGetDevice(&dev_id));
-  const bool hit = plan.device == dev_id && plan.P == P && plan.d == d && plan.h == h && plan.w == w &&
-                   (int64_t)plan.yx.size() == 2 * n && memcmp(plan.yx.data(), yx_host, (size_t)n * 8) == 0;
-  if (!hit) {
-    const int G = std::max(1, std::min(P / d, 64));
-    const int64_t bins_y = (dh_ + G - 1) / G, bins_x = (dw_ + G - 1) / G;
-    const int64_t nbins = bins_y * bins_x;
-    DH_REQUIRE(nbins < INT32_MAX, "accumulate: too many bins");
-    std::vector<int32_t> start(nbins + 1, 0);
-    auto span = [&](int64_t i, int64_t& cy0, int64_t& cy1, int64_t& cx0, int64_t& cx1) {
-      const int64_t y = yx_host[2 * i], x = yx_host[2 * i + 1];
-      cy0 = std::max<int64_t>(y / d, 0); cy1 = std::min<int64_t>((y + P) / d, dh_);
-      cx0 = std::max<int64_t>(x / d, 0); cx1 = std::min<int64_t>((x + P) / d, dw_);
-      return y >= 0 && x >= 0 && cy1 > cy0 && cx1 > cx0;
-    };
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      int64_t a, b, c, e;
-      DH_REQUIRE(yx_host[2 * i] >= 0 && yx_host[2 * i + 1] >= 0, "accumulate: negative origin");
-      if (!span(i, a, b, c, e)) continue;
-      for (int64_t by = a / G; by <= (b - 1) / G; ++by)
-        for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) { ++start[by * bins_x + bx + 1]; ++total; }
-    }
-    DH_REQUIRE(total < INT32_MAX, "accumulate: incidence list too long");
-    for (int64_t b = 0; b < nbins; ++b) start[b + 1] += start[b];
-    std::vector<int32_t> fill(start.begin(), start.end() - 1), tiles((size_t)std::max<int64_t>(total, 1));
-    for (int64_t i = 0; i < n; ++i) {
-      int64_t a, b, c, e;
-      if (!span(i, a, b, c, e)) continue;
-      for (int64_t by = a / G; by <= (b - 1) / G; ++by)
-        for (int64_t bx = c / G; bx <= (e - 1) / G; ++bx) tiles[fill[by * bins_x + bx]++] = (int32_t)i;
-    }
-    DH_HIP(hipStreamSynchronize(st));  // the previous plan's buffers may still be in use on this stream
-    if (plan.d_start) { (void)hipFree(plan.d_start); (void)hipFree(plan.d_tiles); (void)hipFree(plan.d_yx); }
-    plan = Plan();
-    const size_t sb = (size_t)(nbins + 1) * 4, tb = (size_t)std::max<int64_t>(total, 1) * 4, yb = (size_t)n * 8;
-    DH_HIP(hipMalloc((void**)&plan.d_start, sb));
-    DH_HIP(hipMalloc((void**)&plan.d_tiles, tb));
-    DH_HIP(hipMalloc((void**)&plan.d_yx, yb));
-    DH_HIP(hipMemcpy(plan.d_start, start.data(), sb, hipMemcpyHostToDevice));
-    DH_HIP(hipMemcpy(plan.d_tiles, tiles.data(), tb, hipMemcpyHostToDevice));
-    DH_HIP(hipMemcpy(plan.d_yx, yx_host, yb, hipMemcpyHostToDevice));
-    plan.yx.assign(yx_host, yx_host + 2 * n);
-    plan.P = P; plan.d = d; plan.h = h; plan.w = w; plan.nbins = nbins; plan.total = total; plan.G = G;
-    plan.bins_x = (int)bins_x; plan.device = dev_id;
-  }
-  *out = BinPlan{plan.G, (int32_t)plan.bins_x, plan.nbins, plan.total, plan.d_start, plan.d_tiles, plan.d_yx};
-  return DH_OK;
-}
-}  // namespace dh
-
-extern "C" int dh_accumulate_logits(const float* logits, const int32_t* yx_host, int64_t n,
-                                    int32_t P, int32_t d, int32_t n_cls, int64_t h, int64_t w,
-                                    float* canvas, int64_t* map, void* stream) {
-  DH_REQUIRE(logits && yx_host && canvas, "accumulate: null pointer");
-  DH_REQUIRE(P > 0 && d > 0 && n_cls > 0 && h > 0 && w > 0 && n >= 0, "accumulate: bad sizes");
-  DH_REQUIRE(n <= INT32_MAX / 8, "accumulate: too many tiles");
-  const int64_t dh_ = h / d, dw_ = w / d;
-  hipStream_t st = dh::as_stream(stream);
-  if (dh_ == 0 || dw_ == 0) return DH_OK;
-  DH_REQUIRE(dh_ * dw_ <= (int64_t)INT32_MAX, "accumulate: canvas too large");
-  if (n > 0) {
-    dh::BinPlan plan;
-    if (const int rc = dh::bin_plan(yx_host, n, P, d, h, w, st, &plan)) return rc;
-    if (plan.total > 0) {
-      dh::BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
-      hipLaunchKernelGGL(accumulate_bins_kernel<false>, dim3((unsigned)plan.nbins), dim3(256), 0, st, logits, plan.d_yx,
-                         plan.d_start, plan.d_tiles, g, canvas);
-      DH_LAUNCH_CHECK();
-    }
-  }
-  if (map) return dh_argmax_map(canvas, dh_ * dw_, n_cls, map, stream);
-  return DH_OK;
-}
-
-extern "C" int dh_accumulate_cam(const float* cam, const int32_t* yx_host, int64_t n, int32_t P, int32_t d, int32_t n_cls, int64_t h,
-                                 int64_t w, float* canvas, int64_t* map, void* stream) {
-  DH_REQUIRE(cam && yx_host && canvas, "accumulate cam: null pointer");
-  DH_REQUIRE(P > 0 && P % 32 == 0, "accumulate cam: patch %d is not a positive multiple of 32", P);
-  DH_REQUIRE(d > 0 && n_cls > 0 && n >= 0, "accumulate cam: bad sizes");
-  DH_REQUIRE(h > 0 && w > 0 && h <= dh::CAM_MAX_SIDE && w <= dh::CAM_MAX_SIDE, "accumulate cam: h=%lld, w=%lld outside [1, %lld]",
-             (long long)h, (long long)w, (long long)dh::CAM_MAX_SIDE);
-  DH_REQUIRE(n <= INT32_MAX / 8, "accumulate cam: too many tiles");
-  const int64_t dh_ = h / d, dw_ = w / d;
-  hipStream_t st = dh::as_stream(stream);
-  if (dh_ == 0 || dw_ == 0) return DH_OK;
-  DH_REQUIRE(dh_ * dw_ <= (int64_t)INT32_MAX, "accumulate cam: canvas too large");
-  if (n > 0) {
-    dh::BinPlan plan;
-    if (const int rc = dh::bin_plan(yx_host, n, P, d, h, w, st, &plan)) return rc;
-    if (plan.total > 0) {
-      dh::BinGeom g{plan.G, plan.bins_x, (int32_t)dh_, (int32_t)dw_, n_cls, P, d};
-      hipLaunchKernelGGL(accumulate_bins_kernel<true>, dim3((unsigned)plan.nbins), dim3(256), 0, st, cam, plan.d_yx, plan.d_start,
-                         plan.d_tiles, g, canvas);
-      DH_LAUNCH_CHECK();
-    }
-  }
-  if (map) return dh_argmax_map(canvas, dh_ * dw_, n_cls, map, stream);
-  return DH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Visualisation of the class map (examples/predict_full_patched.py:81-113): HBM-bound byte work.
-// ---------------------------------------------------------------------------
-namespace {
-__global__ __launch_bounds__(256) void colorize_kernel(const int64_t* __restrict__ map, int64_t n, const uint8_t* __restrict__ lut,
-                                                       int n_cls, uint8_t* __restrict__ rgb) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t c = map[i];
-    uint8_t r = 0, g = 0, b = 0;
-    if (c >= 0 && c < n_cls) { r = lut[3 * c]; g = lut[3 * c + 1]; b = lut[3 * c + 2]; }
-    rgb[3 * i] = r; rgb[3 * i + 1] = g; rgb[3 * i + 2] = b;
-  }
-}
-__global__ __launch_bounds__(256) void overlay_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ col, int64_t n,
-                                                      double alpha, uint8_t* __restrict__ out) {
-  const double beta = 1.0 - alpha;   // NumPy evaluates (1 - alpha) in float64 first
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (uint8_t)((double)img[i] * alpha + (double)col[i] * beta);   // values are in [0, 255]: the cast truncates
-}
-}  // namespace
-
-extern "C" int dh_colorize_map(const int64_t* map, int64_t n, const uint8_t* lut, int32_t n_cls, uint8_t* rgb, void* stream) {
-  DH_REQUIRE(n >= 0 && n_cls >= 0, "colorize: bad sizes");
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(map && rgb && (lut || n_cls == 0), "colorize: null pointer");
-  hipLaunchKernelGGL(colorize_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, dh::as_stream(stream),
-                     map, n, lut, n_cls, rgb);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-extern "C" int dh_overlay_blend(const uint8_t* img, const uint8_t* col, int64_t n, double alpha, uint8_t* out, void* stream) {
-  DH_REQUIRE(n >= 0 && alpha >= 0.0 && alpha <= 1.0, "overlay: bad arguments");
-  if (n == 0) return DH_OK;
-  DH_REQUIRE(img && col && out, "overlay: null pointer");
-  hipLaunchKernelGGL(overlay_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65535)), dim3(256), 0, dh::as_stream(stream),
-                     img, col, n, alpha, out);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// ---------------------------------------------------------------------------
-// e1: the one exchange step of the sharded whole-slide prediction (every rank contributes the logits of its
-// contiguous tile range, every rank receives all of them) as a C-ABI entry for hosts that are not torch.distributed programs.
-// `comm` is the caller's ncclComm_t (RCCL).  The ncclAllGather that is called MUST come from the library instance that created `comm`
-// (a second copy of RCCL handed a foreign communicator corrupts memory or hangs: ADVICE r4), so this shared object neither links
-// against RCCL nor loads one on its own account.  Resolution order at the first exchange:
-//   1. dh_set_rccl(handle): the host passes the dlopen handle of ITS RCCL (the exact answer; required when that copy was loaded
-//      RTLD_LOCAL under a private path, e.g. a bundled torch/lib/librccl.so);
-//   2. DH_RCCL_LIB=<file>: that file, which must ALREADY be loaded in the process (RTLD_NOLOAD probe; otherwise an error);
-//   3. a global ncclAllGather symbol (RTLD_DEFAULT), then librccl.so.1 / librccl.so if already loaded (RTLD_NOLOAD).
-// Nothing already loaded => DH_EINVAL: a process without RCCL cannot own a communicator.  (The Python shims exchange through
-// torch.distributed, whose RCCL never gets here.)  rccl.h is included for ncclFloat32 / ncclResult_t only: no symbol is linked.
-// ---------------------------------------------------------------------------
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-#include <mutex>
-namespace {
-typedef ncclResult_t (*rccl_allgather_fn)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t);
-typedef const char* (*rccl_errstr_fn)(ncclResult_t);
-struct RcclEntry { rccl_allgather_fn allgather = nullptr; rccl_errstr_fn errstr = nullptr; std::string why; bool resolved = false; };
-std::mutex g_rccl_mu;
-RcclEntry g_rccl;
-void rccl_from_handle(RcclEntry& r, void* h, const char* what) {
-  void* sym = dlsym(h, "ncclAllGather");
-  if (!sym) { r.why = std::string(what) + " has no ncclAllGather"; return; }
-  r.allgather = reinterpret_cast<rccl_allgather_fn>(sym);
-  r.errstr = reinterpret_cast<rccl_errstr_fn>(dlsym(h, "ncclGetErrorString"));
-}
-void rccl_resolve(RcclEntry& r) {
-  r.resolved = true;
-  if (const char* nm = getenv("DH_RCCL_LIB"); nm && *nm) {
-    void* h = dlopen(nm, RTLD_NOW | RTLD_NOLOAD);
-    if (!h) { r.why = std::string("DH_RCCL_LIB=") + nm + " is not loaded in this process (the communicator's own library must be named)"; return; }
-    rccl_from_handle(r, h, nm);
-    return;
-  }
-  if (void* sym = dlsym(RTLD_DEFAULT, "ncclAllGather")) {
-    r.allgather = reinterpret_cast<rccl_allgather_fn>(sym);
-    r.errstr = reinterpret_cast<rccl_errstr_fn>(dlsym(RTLD_DEFAULT, "ncclGetErrorString"));
-    return;
-  }
-  for (const char* nm : {"librccl.so.1", "librccl.so"})
-    if (void* h = dlopen(nm, RTLD_NOW | RTLD_NOLOAD)) { rccl_from_handle(r, h, nm); return; }
-  r.why = "no RCCL is loaded in this process (pass the handle of the communicator's library with dh_set_rccl, or name it in DH_RCCL_LIB)";
-}
-}  // namespace
-
-extern "C" int dh_set_rccl(void* dl_handle) {
-  std::lock_guard<std::mutex> lk(g_rccl_mu);
-  g_rccl = RcclEntry();
-  if (!dl_handle) return DH_OK;   // back to automatic resolution at the next exchange
-  g_rccl.resolved = true;
-  rccl_from_handle(g_rccl, dl_handle, "the handle given to dh_set_rccl");
-  DH_REQUIRE(g_rccl.allgather, "dh_set_rccl: %s", g_rccl.why.c_str());
-  return DH_OK;
-}
-
-extern "C" int dh_allgather_logits(void* comm, const float* send_dev, float* recv_dev, int64_t n_per_rank, int32_t n_cls, void* stream) {
-  DH_REQUIRE(comm, "allgather_logits: null communicator");
-  DH_REQUIRE(n_per_rank >= 0 && n_cls > 0, "allgather_logits: bad sizes");
-  if (n_per_rank == 0) return DH_OK;
-  DH_REQUIRE(send_dev && recv_dev, "allgather_logits: null pointer");
-  RcclEntry e;
-  {
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (!g_rccl.resolved) rccl_resolve(g_rccl);
-    e = g_rccl;
-  }
-  DH_REQUIRE(e.allgather, "allgather_logits: %s", e.why.empty() ? "RCCL not found" : e.why.c_str());
-  const ncclResult_t rc = e.allgather(send_dev, recv_dev, (size_t)n_per_rank * (size_t)n_cls, ncclFloat32, static_cast<ncclComm_t>(comm), dh::as_stream(stream));
-  if (rc != ncclSuccess) {
-    dh::set_error("allgather_logits: ncclAllGather failed: %s (%d)", e.errstr ? e.errstr(rc) : "?", (int)rc);
-    return DH_EHIP;
-  }
   return DH_OK;
 }

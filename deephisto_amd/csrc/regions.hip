@@ -22,7 +22,7 @@
 
 namespace {
 
-constexpr int MAX_CLS = 64;      // as proba.hip, score.hip
+constexpr int MAX_CLS = 64;      // as accumulate.hip, score.hip
 constexpr int kThreads = 256;
 constexpr int TS = 64;           // tile side in cells
 constexpr int kTileCells = TS * TS;

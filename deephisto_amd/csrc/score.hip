@@ -15,7 +15,7 @@
 #include "dh_common.h"
 
 namespace {
-constexpr int MAX_CLS = 64;   // as proba.hip
+constexpr int MAX_CLS = 64;   // as accumulate.hip
 constexpr int RG = 32;        // bin side in cells: one uint32 of inside bits per row
 constexpr int CH = 512;       // edges of a ring per LDS stage
 constexpr double MAX_COORD = 1e15;

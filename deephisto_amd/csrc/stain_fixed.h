@@ -1,4 +1,4 @@
-// Fixed-point limits shared by the stain kernels (stain.hip) and the stain-jitter gather (tile_kernels.hip); the host's copies
+// Fixed-point limits shared by the stain kernels (stain.hip) and the stain-jitter gather (gather.hip); the host's copies
 // are in deephisto_amd/stain.py (OD_MAX, LUT_SIZE, COEF_MAX).
 #pragma once
 #include <stdint.h>

@@ -9,7 +9,6 @@ class map or a similarity heat map without a training step, on three small deter
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 
 import numpy as np
@@ -20,13 +19,10 @@ from ._lib import check, lib
 from .patch_samplers.full_samplers import FullImageDenseSampler
 from .plan import Lanes, TileGrid, exchange_rows, finish, launch_tiles, normalised_first, plan_tiles, require_dense_resident
 from .quality import QualityFilter
+from .tiles import _stream
 from .tissue import TissueFilter, fill_uncovered
 
 CHUNK_ROWS = 1024   # DH_EMBED_CHUNK_ROWS: the chunking of class_sums' summation order
-
-
-def _stream(dev) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _rows(t: torch.Tensor, what: str) -> torch.Tensor:

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from ..._lib import BUCKET_CB, check, lib
+from ...tiles import _stream
 from .ddp import DEFAULT_BUCKET_BYTES, BucketReducer
 
 
@@ -30,10 +31,6 @@ class _DevView:
 
     def __init__(self, ptr: int, n: int):
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 2}
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def ce_loss(logits: torch.Tensor, labels: torch.Tensor, want_grad: bool = False):

@@ -21,7 +21,7 @@ from . import tiles
 from ._lib import check, lib
 from .patch_samplers.region_samplers import RegionAnnotation, _load_annotation, _parse_annotations
 
-MAX_CLASSES = 64   # MAX_CLS of csrc/proba.hip and csrc/score.hip
+MAX_CLASSES = 64   # MAX_CLS of csrc/accumulate.hip and csrc/score.hip
 
 
 class _LayerSize:

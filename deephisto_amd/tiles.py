@@ -34,6 +34,38 @@ def dtype_code(dtype) -> int:
     raise ValueError(f"unsupported dtype {dtype!r}")
 
 
+def _gather_out(n: int, patch: int, layout: int, dtype, device) -> tuple[torch.Tensor, int]:
+    """The output tensor of a gather, (n, 3, P, P) (NCHW) or (n, P, P, 3) in the coded dtype, and the dtype's code."""
+    code = dtype_code(dtype)
+    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
+    return torch.empty(shape, dtype=_TORCH_DTYPE[code], device=device), code
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _param_rows(dev_t: torch.Tensor, host, n: int, k: int, what: str):
+    """Per-tile parameter rows: `dev_t` must be int32[n, k] on the device; returns the optional host copy as a contiguous
+    int32[n, k] array for the entry's check (None: not checked)."""
+    _require_cuda(dev_t, what)
+    if dev_t.dtype != torch.int32 or tuple(dev_t.shape) != (n, k):
+        raise ValueError(f"{what} must be int32[{n}, {k}], not {str(dev_t.dtype).replace('torch.', '')}{list(dev_t.shape)}")
+    if host is None:
+        return None
+    host = np.ascontiguousarray(host, dtype=np.int32)
+    if host.shape != (n, k):
+        raise ValueError(f"{what}_host must be int32[{n}, {k}], not {list(host.shape)}")
+    return host
+
+
+def _stain_table_args(device) -> tuple:
+    """(od_dev, od_host, shift, lut_dev, lut_n) of the stain gathers' entries, from the tables of stain.py."""
+    from . import stain as S
+    od_dev, _, lut, od = S._tables(device)
+    return od_dev.data_ptr(), _host_ptr(od), S.APPLY_SHIFT, lut.data_ptr(), S.LUT_SIZE
+
+
 def tile_grid(h: int, w: int, patch: int, stride: int, batch: int) -> tuple[np.ndarray, int]:
     """(int32[n_padded, 2] (y, x) origins in the reference's order, n_unique).
 
@@ -70,11 +102,8 @@ def gather_tiles(slide: torch.Tensor, origins, patch: int, layout: int = DH_LAYO
         host = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1, 2))
         yx_dev = torch.from_numpy(host).to(slide.device)
     n = int(yx_dev.shape[0])
-    code = dtype_code(dtype)
-    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
-    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
-    check(lib().dh_tile_gather(slide.data_ptr(), h, w, yx_dev.data_ptr(),
-                               host.ctypes.data_as(C.c_void_p) if (check_bounds and host is not None) else None,
+    out, code = _gather_out(n, patch, layout, dtype, slide.device)
+    check(lib().dh_tile_gather(slide.data_ptr(), h, w, yx_dev.data_ptr(), _host_ptr(host if check_bounds else None),
                                n, patch, layout, code, out.data_ptr(), _stream(slide.device)), "dh_tile_gather")
     return out
 
@@ -85,9 +114,7 @@ def gather_tiles_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch: int,
     _require_cuda(slide, "slide")
     _require_cuda(origins_dev, "origins")
     n = int(origins_dev.shape[0])
-    code = dtype_code(dtype)
-    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
-    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
+    out, code = _gather_out(n, patch, layout, dtype, slide.device)
     check(lib().dh_tile_gather_aug(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n,
                                    patch, layout, code, int(flip_h), int(flip_v), out.data_ptr(), _stream(slide.device)),
           "dh_tile_gather_aug")
@@ -99,27 +126,15 @@ def gather_tiles_stain_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patch
     """gather_tiles_aug with a per-tile stain jitter fused in (dh_tile_gather_stain_aug).
     `params_dev`: int32[n, 12] on the device, the rows of stain.jitter_params; `params_host`: the same rows on the host, checked
     by the entry before the launch (None: not checked)."""
-    from . import stain as S
     _require_cuda(slide, "slide")
     _require_cuda(origins_dev, "origins")
-    _require_cuda(params_dev, "params")
     n = int(origins_dev.shape[0])
-    if params_dev.dtype != torch.int32 or tuple(params_dev.shape) != (n, 12):
-        raise ValueError(f"params must be int32[{n}, 12], not {str(params_dev.dtype).replace('torch.', '')}{list(params_dev.shape)}")
-    host = None
-    if params_host is not None:
-        host = np.ascontiguousarray(params_host, dtype=np.int32)
-        if host.shape != (n, 12):
-            raise ValueError(f"params_host must be int32[{n}, 12], not {list(host.shape)}")
-    code = dtype_code(dtype)
-    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
-    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
-    od_dev, _, lut, od = S._tables(slide.device)
+    p_host = _param_rows(params_dev, params_host, n, 12, "params")
+    out, code = _gather_out(n, patch, layout, dtype, slide.device)
     check(lib().dh_tile_gather_stain_aug(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(),
-                                         params_dev.data_ptr(), host.ctypes.data_as(C.c_void_p) if host is not None else None, n,
-                                         patch, layout, code, int(flip_h), int(flip_v), od_dev.data_ptr(),
-                                         od.ctypes.data_as(C.c_void_p), S.APPLY_SHIFT, lut.data_ptr(), S.LUT_SIZE, out.data_ptr(),
-                                         _stream(slide.device)), "dh_tile_gather_stain_aug")
+                                         params_dev.data_ptr(), _host_ptr(p_host), n, patch, layout, code, int(flip_h), int(flip_v),
+                                         *_stain_table_args(slide.device), out.data_ptr(), _stream(slide.device)),
+          "dh_tile_gather_stain_aug")
     return out
 
 
@@ -133,39 +148,18 @@ def gather_tiles_affine_aug(slide: torch.Tensor, origins_dev: torch.Tensor, patc
     s * P * sqrt(2) / 2 from it; where it leaves the slide it reads 0."""
     _require_cuda(slide, "slide")
     _require_cuda(origins_dev, "origins")
-    _require_cuda(affine_dev, "affine")
     n = int(origins_dev.shape[0])
-
-    def rows(dev_t, host, k, what):
-        if dev_t.dtype != torch.int32 or tuple(dev_t.shape) != (n, k):
-            raise ValueError(f"{what} must be int32[{n}, {k}], not {str(dev_t.dtype).replace('torch.', '')}{list(dev_t.shape)}")
-        if host is None:
-            return None
-        host = np.ascontiguousarray(host, dtype=np.int32)
-        if host.shape != (n, k):
-            raise ValueError(f"{what}_host must be int32[{n}, {k}], not {list(host.shape)}")
-        return host
-
-    a_host = rows(affine_dev, affine_host, 4, "affine")
+    a_host = _param_rows(affine_dev, affine_host, n, 4, "affine")
     p_host = None
     if params_dev is not None:
-        _require_cuda(params_dev, "params")
-        p_host = rows(params_dev, params_host, 12, "params")
+        p_host = _param_rows(params_dev, params_host, n, 12, "params")
     elif params_host is not None:
         raise ValueError("params_host without params_dev")
-    code = dtype_code(dtype)
-    shape = (n, 3, patch, patch) if layout == DH_LAYOUT_NCHW else (n, patch, patch, 3)
-    out = torch.empty(shape, dtype=_TORCH_DTYPE[code], device=slide.device)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
-    if params_dev is not None:
-        from . import stain as S
-        od_dev, _, lut, od = S._tables(slide.device)
-        stain_args = (od_dev.data_ptr(), ptr(od), S.APPLY_SHIFT, lut.data_ptr(), S.LUT_SIZE)
-    else:
-        stain_args = (None, None, 0, None, 0)
+    out, code = _gather_out(n, patch, layout, dtype, slide.device)
+    stain_args = _stain_table_args(slide.device) if params_dev is not None else (None, None, 0, None, 0)
     check(lib().dh_tile_gather_affine_aug(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(),
-                                          params_dev.data_ptr() if params_dev is not None else None, ptr(p_host),
-                                          affine_dev.data_ptr(), ptr(a_host), n, patch, layout, code, int(flip_h), int(flip_v),
+                                          params_dev.data_ptr() if params_dev is not None else None, _host_ptr(p_host),
+                                          affine_dev.data_ptr(), _host_ptr(a_host), n, patch, layout, code, int(flip_h), int(flip_v),
                                           *stain_args, out.data_ptr(), _stream(slide.device)), "dh_tile_gather_affine_aug")
     return out
 
@@ -231,7 +225,7 @@ def gather_tiles_raw(slide: torch.Tensor, origins_dev: torch.Tensor, patch: int)
     _require_cuda(slide, "slide")
     _require_cuda(origins_dev, "origins")
     n = int(origins_dev.shape[0])
-    out = torch.empty((n, patch, patch, 3), dtype=torch.float32, device=slide.device)
+    out, _ = _gather_out(n, patch, DH_LAYOUT_NHWC, torch.float32, slide.device)
     check(lib().dh_tile_gather_raw(slide.data_ptr(), int(slide.shape[0]), int(slide.shape[1]), origins_dev.data_ptr(), n,
                                    patch, out.data_ptr(), _stream(slide.device)), "dh_tile_gather_raw")
     return out
@@ -247,6 +241,24 @@ def tile_coords(origins_dev: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _origin_rows(origins_host, n: int, rows: str) -> np.ndarray:
+    """The host origins of an accumulation as contiguous int32[n, 2]; `rows` names what there are n of."""
+    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
+    if yx.shape[0] != n:
+        raise ValueError(f"{rows} but {yx.shape[0]} origins")
+    return yx
+
+
+def _sum_canvas(canvas: torch.Tensor | None, shape: tuple, device) -> torch.Tensor:
+    """The float32[h//d, w//d, n_cls] canvas of the sums: the caller's, checked, or a new one of zeros."""
+    if canvas is None:
+        return torch.zeros(shape, dtype=torch.float32, device=device)
+    _require_cuda(canvas, "canvas")
+    if tuple(canvas.shape) != shape or canvas.dtype != torch.float32:
+        raise ValueError("canvas must be float32[h//d, w//d, n_cls]")
+    return canvas
+
+
 def accumulate_logits(logits: torch.Tensor, origins_host: np.ndarray, patch: int, downscale: int,
                       h: int, w: int, canvas: torch.Tensor | None = None,
                       want_map: bool = True) -> tuple[torch.Tensor, torch.Tensor | None]:
@@ -255,17 +267,10 @@ def accumulate_logits(logits: torch.Tensor, origins_host: np.ndarray, patch: int
     _require_cuda(logits, "logits")
     if logits.dtype != torch.float32 or logits.dim() != 2:
         raise ValueError("logits must be float32[n, n_cls]")
-    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
     n, n_cls = int(logits.shape[0]), int(logits.shape[1])
-    if yx.shape[0] != n:
-        raise ValueError(f"{n} logit rows but {yx.shape[0]} origins")
+    yx = _origin_rows(origins_host, n, f"{n} logit rows")
     dh_, dw_ = h // downscale, w // downscale
-    if canvas is None:
-        canvas = torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=logits.device)
-    else:
-        _require_cuda(canvas, "canvas")
-        if tuple(canvas.shape) != (dh_, dw_, n_cls) or canvas.dtype != torch.float32:
-            raise ValueError("canvas must be float32[h//d, w//d, n_cls]")
+    canvas = _sum_canvas(canvas, (dh_, dw_, n_cls), logits.device)
     cmap = torch.empty((dh_, dw_), dtype=torch.int64, device=logits.device) if want_map else None
     check(lib().dh_accumulate_logits(logits.data_ptr(), yx.ctypes.data_as(C.c_void_p), n, patch, downscale,
                                      n_cls, h, w, canvas.data_ptr(),
@@ -344,6 +349,26 @@ class SlideProbabilities:
         return self
 
 
+def _proba_state(state: SlideProbabilities | None, dh_: int, dw_: int, n_cls: int, device) -> SlideProbabilities:
+    """The unfinished state of a mean accumulation over a dh_ x dw_ canvas: the caller's, checked, or a new one of zeros."""
+    if not 1 <= n_cls <= 64:
+        raise ValueError(f"n_cls = {n_cls}: the probability kernels take 1 to 64 classes")
+    if state is None:
+        return SlideProbabilities(torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=device),
+                                  torch.zeros((dh_, dw_), dtype=torch.int32, device=device))
+    if not isinstance(state, SlideProbabilities):
+        raise ValueError("state must be a SlideProbabilities")
+    if state.finished:
+        raise ValueError("state is already finished (its sums were divided): continue from finish=False results only")
+    for t, what, dt, shape in ((state.proba, "state.proba", torch.float32, (dh_, dw_, n_cls)),
+                               (state.count, "state.count", torch.int32, (dh_, dw_))):
+        _require_cuda(t, what)
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be {str(dt).replace('torch.', '')}{list(shape)} "
+                             f"(canvas h//d x w//d of this call), not {str(t.dtype).replace('torch.', '')}{list(t.shape)}")
+    return state
+
+
 def accumulate_probabilities(logits: torch.Tensor, origins_host: np.ndarray, patch: int, downscale: int, h: int, w: int,
                              state: SlideProbabilities | None = None, fill_class: int = -1,
                              finish: bool = True) -> SlideProbabilities:
@@ -354,27 +379,9 @@ def accumulate_probabilities(logits: torch.Tensor, origins_host: np.ndarray, pat
     _require_cuda(logits, "logits")
     if logits.dtype != torch.float32 or logits.dim() != 2:
         raise ValueError("logits must be float32[n, n_cls]")
-    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
     n, n_cls = int(logits.shape[0]), int(logits.shape[1])
-    if yx.shape[0] != n:
-        raise ValueError(f"{n} logit rows but {yx.shape[0]} origins")
-    if not 1 <= n_cls <= 64:
-        raise ValueError(f"n_cls = {n_cls}: the probability kernels take 1 to 64 classes")
-    dh_, dw_ = h // downscale, w // downscale
-    if state is None:
-        state = SlideProbabilities(torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=logits.device),
-                                   torch.zeros((dh_, dw_), dtype=torch.int32, device=logits.device))
-    else:
-        if not isinstance(state, SlideProbabilities):
-            raise ValueError("state must be a SlideProbabilities")
-        if state.finished:
-            raise ValueError("state is already finished (its sums were divided): continue from finish=False results only")
-        for t, what, dt, shape in ((state.proba, "state.proba", torch.float32, (dh_, dw_, n_cls)),
-                                   (state.count, "state.count", torch.int32, (dh_, dw_))):
-            _require_cuda(t, what)
-            if t.dtype != dt or tuple(t.shape) != shape:
-                raise ValueError(f"{what} must be {str(dt).replace('torch.', '')}{list(shape)} "
-                                 f"(canvas h//d x w//d of this call), not {str(t.dtype).replace('torch.', '')}{list(t.shape)}")
+    yx = _origin_rows(origins_host, n, f"{n} logit rows")
+    state = _proba_state(state, h // downscale, w // downscale, n_cls, logits.device)
     probs = softmax_rows(logits)
     if finish:
         state._outputs()
@@ -410,10 +417,8 @@ def _cam_rows(cam: torch.Tensor, origins_host, patch: int):
     s = patch // 32
     if cam.dtype != torch.float32 or cam.dim() not in (3, 4) or int(np.prod(cam.shape[1:-1])) != s * s:
         raise ValueError(f"cam must be float32[n, {s}, {s}, n_cls] for patch {patch}")
-    yx = np.ascontiguousarray(np.asarray(origins_host, dtype=np.int32).reshape(-1, 2))
     n, n_cls = int(cam.shape[0]), int(cam.shape[-1])
-    if yx.shape[0] != n:
-        raise ValueError(f"class activation maps of {n} tiles but {yx.shape[0]} origins")
+    yx = _origin_rows(origins_host, n, f"class activation maps of {n} tiles")
     return cam.contiguous(), yx, n, n_cls
 
 
@@ -425,12 +430,7 @@ def accumulate_cam(cam: torch.Tensor, origins_host: np.ndarray, patch: int, down
     Returns (canvas f32[dh, dw, n_cls], map int64[dh, dw])."""
     cam, yx, n, n_cls = _cam_rows(cam, origins_host, patch)
     dh_, dw_ = h // downscale, w // downscale
-    if canvas is None:
-        canvas = torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=cam.device)
-    else:
-        _require_cuda(canvas, "canvas")
-        if tuple(canvas.shape) != (dh_, dw_, n_cls) or canvas.dtype != torch.float32:
-            raise ValueError("canvas must be float32[h//d, w//d, n_cls]")
+    canvas = _sum_canvas(canvas, (dh_, dw_, n_cls), cam.device)
     cmap = torch.empty((dh_, dw_), dtype=torch.int64, device=cam.device) if want_map else None
     check(lib().dh_accumulate_cam(cam.data_ptr(), yx.ctypes.data_as(C.c_void_p), n, int(patch), downscale, n_cls, h, w,
                                   canvas.data_ptr(), cmap.data_ptr() if cmap is not None else None, _stream(cam.device)),
@@ -444,11 +444,7 @@ def accumulate_cam_probabilities(cam: torch.Tensor, origins_host: np.ndarray, pa
     softmax of every position's scores (dh_softmax_rows over n * S * S rows), per-cell sums and hit counts in tile order
     (dh_accumulate_cam_mean), mean, first-maximum class and confidence.  Returns a finished SlideProbabilities."""
     cam, yx, n, n_cls = _cam_rows(cam, origins_host, patch)
-    if not 1 <= n_cls <= 64:
-        raise ValueError(f"n_cls = {n_cls}: the probability kernels take 1 to 64 classes")
-    dh_, dw_ = h // downscale, w // downscale
-    state = SlideProbabilities(torch.zeros((dh_, dw_, n_cls), dtype=torch.float32, device=cam.device),
-                               torch.zeros((dh_, dw_), dtype=torch.int32, device=cam.device))
+    state = _proba_state(None, h // downscale, w // downscale, n_cls, cam.device)
     probs = softmax_rows(cam.view(-1, n_cls))
     state._outputs()
     state.fill_class = int(fill_class)

@@ -66,6 +66,34 @@ def test_gather_bit_exact(dev, P):
         assert torch.equal(got.cpu().view(torch.int16), want.view(torch.int16))
 
 
+@pytest.mark.parametrize("P", [8, 7])
+def test_gather_aug_and_raw_over_the_border_bit_exact(dev, P):
+    """Tiles that hang over the slide border against a NumPy restatement (tests/helpers/stain_aug_ref.py): k/255 inside, 0 outside."""
+    import sys
+    from pathlib import Path
+    sys.path.insert(0, str(Path(__file__).resolve().parent / "helpers"))
+    import stain_aug_ref as A
+    from deephisto_amd import tiles
+    from deephisto_amd._lib import DH_LAYOUT_NCHW, DH_LAYOUT_NHWC
+    h, w = 40, 56
+    host = np.random.default_rng(40 * 56).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    slide = torch.from_numpy(host).to(dev)
+    o = np.array([(-3, -2), (0, 0), (h - P + 2, w - P + 5), (11, 23), (h - 1, w - 1)], np.int32)
+    o_dev = torch.from_numpy(o).to(dev)
+    for layout in (DH_LAYOUT_NHWC, DH_LAYOUT_NCHW):
+        for flip_h, flip_v in ((False, False), (True, False), (False, True), (True, True)):
+            ref = A.plain(host, o, P, flip_h, flip_v, nchw=layout == DH_LAYOUT_NCHW)
+            got = tiles.gather_tiles_aug(slide, o_dev, P, layout, torch.float32, flip_h, flip_v)
+            assert got.shape == ref.shape and np.array_equal(got.cpu().numpy().view(np.uint32), ref.view(np.uint32)), (layout, flip_h, flip_v)
+            got = tiles.gather_tiles_aug(slide, o_dev, P, layout, torch.bfloat16, flip_h, flip_v)
+            want = torch.from_numpy(ref).to(torch.bfloat16)   # round-to-nearest-even of the float32 reference
+            assert got.shape == want.shape and torch.equal(got.cpu().view(torch.int16), want.view(torch.int16)), (layout, flip_h, flip_v)
+    px, inside = A.source_pixels(host, o, P)
+    assert not inside[0].all() and inside[1].all() and not inside[2].all() and inside[4].sum() == 1
+    got = tiles.gather_tiles_raw(slide, o_dev, P).cpu().numpy()
+    assert got.shape == px.shape and np.array_equal(got.view(np.uint32), px.astype(np.float32).view(np.uint32))
+
+
 def test_gather_rejects_out_of_bounds(dev):
     from deephisto_amd import _lib, tiles
     slide = torch.zeros((300, 300, 3), dtype=torch.uint8, device=dev)
