@@ -34,7 +34,7 @@ def _tap(img, yy, xx):
 def blend(img, origins, P, rows, flip_h=False, flip_v=False):
     """(uint8[n, P, P, 3] the interpolated value v of every output pixel; bool[n, P, P]: a tap of non-zero weight lies inside the
     slide -- the others are written as 0 and not transformed)."""
-    img = np.asarray(img)
+    img = img if hasattr(img, "shape") else np.asarray(img)   # an array, or a virtual image (slide_scale.py): .shape and img[yy, xx]
     x, y = coordinates(origins, P, rows, flip_h, flip_v)
     xi, yi = x >> 16, y >> 16                                   # arithmetic shifts: floor
     fx, fy = ((x >> 8) & 255)[..., None], ((y >> 8) & 255)[..., None]

@@ -8,7 +8,7 @@ from deephisto_amd import stain as S
 
 def source_pixels(img, origins, P, flip_h=False, flip_v=False):
     """(uint8[n, P, P, 3] source bytes of every OUTPUT pixel, 0 outside the slide; bool[n, P, P] inside the slide)."""
-    img = np.asarray(img)
+    img = img if hasattr(img, "shape") else np.asarray(img)   # an array, or a virtual image (slide_scale.py): .shape and img[yy, xx]
     h, w = img.shape[:2]
     o = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
     r = np.arange(P)

@@ -201,7 +201,8 @@ def test_fused_bf16_stem_pool_every_pixel(dev, P, side):
     torch-CPU restatement with the SAME roundings (pixels k/255 -> bf16, weights -> bf16, f32 accumulation, BN in f32, one
     rounding to bf16): every pooled pixel of every tile, tiles in the slide's corners included (the first and the last byte of
     the allocation lie inside their windows).  Only the f32 summation order differs, so values agree to one bf16 ulp and
-    nearly all are identical."""
+    nearly all are identical.  These slides have at most 737 px a side; window offsets past 2^31 and 2^32 bytes are held by
+    tests/test_gpu_slide_scale.py."""
     from deephisto_amd._lib import check, lib
     oracle = oracle_net.seeded_model(77, 5, perturb_bn=True).eval()
     model = _hip_model(oracle, dev, "bf16")

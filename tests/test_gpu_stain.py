@@ -2,7 +2,8 @@
 
 Every device result -- the ten moments, the angle histogram, the two concentration histograms, the applied slide -- is an integer
 function of the bytes and is compared bit for bit.  With `stain=` the prediction functions and the region samplers give exactly
-what they give over the normalised slide."""
+what they give over the normalised slide.  The largest slide here has 8.4e6 pixels; the four passes over 1.4e9 pixels (offsets past 2^32
+bytes, the counters at slide scale) are held by tests/test_gpu_slide_scale.py."""
 import os
 import subprocess
 import sys

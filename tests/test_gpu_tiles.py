@@ -1,6 +1,7 @@
 """GPU parity, tile side (rows a1-a5, a8): HIP kernels vs the oracle and vs the
 fixtures produced by the reference.  Everything here is integer/byte work or
-exactly-rounded float32, so the bar is BIT-EXACT."""
+exactly-rounded float32, so the bar is BIT-EXACT.  The slides here are small; source offsets and outputs past 2^31 and
+2^32 bytes are held by tests/test_gpu_slide_scale.py."""
 import hashlib
 
 import numpy as np
