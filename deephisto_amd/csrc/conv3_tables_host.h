@@ -1,6 +1,6 @@
 // conv3_tables_host.h -- HOST-ONLY integer code behind the 3x3 convolution kernel (conv3x3.inc): tile-shape choice, per-thread
 // geometry, per-tile schedule and mask tables.  Every LDS-DMA source address and every output address of the kernel comes out of
-// these tables, so the file is kept free of HIP: resnet_kernels.hip includes it for the product, and
+// these tables, so the file is kept free of HIP: resnet_kernels.hip includes it (through conv3_plan_host.h, the launch plan) for the product, and
 // tests/host/conv3_tables_sweep.cpp compiles it with `g++ -fsanitize=address,undefined` and sweeps the shapes the engines use,
 // asserting that every offset lies inside its tensor and fits its integer type (tests/test_conv_tables_host.py, CPU only).
 //
@@ -39,8 +39,10 @@ struct HostTables {
   bool xcd_group = false;
 };
 
-template <int STRIDE, int NT, int WAVES>
-constexpr int max_window_pieces() { return (STRIDE == 2) ? (WAVES == 8 ? 5 : 10) : (NT == 2 ? 6 : 4); }
+constexpr int kWaves = 8;   // waves of a workgroup, every variant
+// the kernel variant as data; conv3x3_launch.inc lists the conv3x3_kernel instantiations that exist
+struct Variant { int stride = 1, nt = 1, mt = 2, ds = 0, wres = 0, cls = -1, half = 0, m16 = 0; };
+inline int max_window_pieces(int stride, int nt) { return stride == 2 ? 5 : nt == 2 ? 6 : 4; }   // window DMA instructions per wave (MAXJ)
 
 // Tile shapes of the stride-1 kernel from the largest down: {TH, TW, IMGS, HP, variant}; variant 0: NT=2 MT=2 (512 pixels),
 // 1: NT=1 MT=2 (256), 2: NT=1 MT=1 (128).  The first candidate that gives the launch `min_tiles` tiles wins, else the smallest.
@@ -255,11 +257,11 @@ inline int m16_read_conflicts(const int (&bl)[64]) {
 // Returns nullptr, or the reason the shape cannot be scheduled.  `grid_override` > 0: the launch's share of a merged launch.
 // HALF: half-chunk stages of the wide stride-2 variant -- a window piece (1 KiB) is 32 pixels x 32 bytes (lane l: pixel l >> 1, landing
 // slot l & 1, which holds global slot (l & 1) ^ ((pixel >> 3) & 1)); waves pair up on pixels although each owns two cout tiles.
-template <int STRIDE, int NT, int WAVES, int ESZ, int MT, class P, bool HALF = false, bool M16 = false>
-const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out) {
-  static_assert(!M16 || (STRIDE == 1 && !HALF && ESZ == 2), "M16: the stride-1 bf16 kernels");
-  constexpr int MAXJ = max_window_pieces<STRIDE, NT, WAVES>();
-  constexpr int NB = M16 ? 2 * NT : NT;
+template <class P> const char* build_tables(const Variant& v, int ESZ, const P& p, int ncb, int grid_override, HostTables* out) {
+  const int STRIDE = v.stride, NT = v.nt, MT = v.mt, WAVES = kWaves;
+  const bool HALF = v.half, M16 = v.m16;
+  if (M16 && (STRIDE != 1 || HALF || ESZ != 2)) return "conv3x3: 16x16x32 MFMAs are for the stride-1 bf16 kernels";
+  const int MAXJ = max_window_pieces(STRIDE, NT), NB = M16 ? 2 * NT : NT;
   const int threads = WAVES * 64, stride = 2 * NT + NB + MAXJ;
   // Invariants the KERNEL relies on and cannot check, stated where its addresses are made:
   //  * at least two channel stages per tile: the mask word of the NEXT tile is fetched by the cursor step that enters the second stage
@@ -268,13 +270,13 @@ const char* build_tables(const P& p, int ncb, int grid_override, HostTables* out
   //  * the staged window fits 64 KiB: the hoisted per-lane fragment offsets are kept as 16-bit halves (conv3x3.inc, HOIST), and a DMA
   //    instruction lands 1 KiB, so n_win_instr KiB must cover the window and stay <= 64;
   //  * a descriptor word holds the cout block in bits 0-15, `valid` in bit 16 and the mask row in bits 20-31.
-  constexpr int STAGE_PX_BYTES = HALF ? kChunkBytes / 2 : kChunkBytes;
+  const int STAGE_PX_BYTES = HALF ? kChunkBytes / 2 : kChunkBytes;
   if ((int64_t)p.Cin * ESZ < 2 * STAGE_PX_BYTES || ((int64_t)p.Cin * ESZ) % STAGE_PX_BYTES) return "conv3x3: needs at least two whole channel stages per tile";
   const int64_t win_px = (int64_t)p.IMGS * p.HR * p.HP + p.WTAIL;
   const int IP = p.IP ? p.IP : p.HR * p.HP;   // pixels between image segments (0 = unset: dense)
   if (win_px * STAGE_PX_BYTES > 65536) return "conv3x3: staged window larger than 64 KiB (16-bit fragment offsets)";
   if ((int64_t)p.n_win_instr * 1024 < win_px * STAGE_PX_BYTES) return "conv3x3: the DMA plan does not cover the staged window";
-  constexpr int NTILE32 = (HALF ? WAVES / 2 : WAVES * MT / 2) * NT;   // 32-pixel n-tiles of a workgroup
+  const int NTILE32 = (HALF ? WAVES / 2 : WAVES * MT / 2) * NT;   // 32-pixel n-tiles of a workgroup
   if (p.FIT) {
     if (STRIDE != 1 || HALF) return "conv3x3: fit tiles are stride-1 tiles";
     if (p.IMGS * p.TH * p.TW > NTILE32 * 32) return "conv3x3: fit tile larger than the workgroup's slots";

@@ -91,8 +91,7 @@ int r50_forward_impl(dh_resnet50* net, const float* x, const uint8_t* slide, int
     const int Ho = (H - 1) / b.stride + 1;
     if ((rc = r50_gemm(c1, X, nullptr, T1, B, H, H, true, st))) return rc;
     if ((rc = tap_after<__bf16>(tap, c1.name, T1, c1.cout, H, H, 32, st))) return rc;
-    rc = b.stride == 1 ? launch_conv3x3<__bf16, 1>(c2, T1, nullptr, T2, B, H, H, true, st, Ho, Ho, nullptr, nullptr, true)
-                       : launch_conv3x3<__bf16, 2>(c2, T1, nullptr, T2, B, H, H, true, st, Ho, Ho, nullptr, nullptr, true);
+    rc = launch_conv3x3<__bf16>(b.stride, c2, T1, nullptr, T2, B, H, H, true, st, Ho, Ho, nullptr, nullptr, true);
     if (rc) return rc;
     if ((rc = tap_after<__bf16>(tap, c2.name, T2, c2.cout, Ho, Ho, 32, st))) return rc;
     const bf16_t* idt = X;

@@ -35,7 +35,7 @@
 #include <vector>
 
 #include "dh_common.h"
-#include "conv3_tables_host.h"
+#include "conv3_plan_host.h"   // (includes conv3_tables_host.h)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -741,378 +741,7 @@ int zero_page(const void** out) {
   return DH_OK;
 }
 
-// Host-built lookup tables of the conv3x3 kernel, cached per (device, layer shape): per-thread geometry and per-tile
-// decode, a few KiB each.  The key holds the batch only through the tile count; the cache is bounded (a caller that
-// sweeps batch sizes would otherwise grow it without end): past CONV3_TABLE_CAP entries of a device it is emptied
-// (hipFree waits for kernels that still read a table).
-struct Conv3Tables { int* lane = nullptr; int4* tile = nullptr; unsigned* mask = nullptr; };
-std::map<std::vector<int>, Conv3Tables> g_conv3_tables;
-constexpr size_t CONV3_TABLE_CAP = 256;
-
-template <int STRIDE, int NT, int WAVES, int ESZ, int MT, bool HALF = false, bool M16 = false>
-int conv3_tables(const Conv3Params& p, int ncb, int groups_img, Conv3Tables* out, int grid_override = 0) {
-  const std::vector<int> key = {current_device(), STRIDE, NT, WAVES, MT + (HALF ? 100 : 0) + (M16 ? 200 : 0), ESZ, p.TH, p.TW, p.IMGS, p.HR, p.HC, p.HP, p.HPH, p.Hi, p.Wi,
-                                p.Cin, p.B, p.tiles_y, p.tiles_x, ncb, p.n_win_instr, p.WTAIL, p.FIT, p.IP, p.in_px_bytes, p.Ho, p.Wo, p.Cout, p.out_px,
-                                p.out_cb, (int)(p.o_img & 0x7FFFFFFF), (int)(p.o_img >> 31), p.o_row, p.o_px, p.o_base, grid_override, p.iters,
-                                p.r_row, p.r_px, p.r_cb, p.r_base};
-  std::lock_guard<std::mutex> lk(g_host_mu);
-  auto it = g_conv3_tables.find(key);
-  if (it != g_conv3_tables.end()) { *out = it->second; return DH_OK; }
-  if (g_conv3_tables.size() >= CONV3_TABLE_CAP) {
-    for (auto& kv : g_conv3_tables) { (void)hipFree(kv.second.lane); (void)hipFree(kv.second.tile); (void)hipFree(kv.second.mask); }
-    g_conv3_tables.clear();
-  }
-  dh_conv3::HostTables ht;   // pure integer host code (conv3_tables_host.h; swept under sanitizers by tests/test_conv_tables_host.py)
-  if (const char* why = dh_conv3::build_tables<STRIDE, NT, WAVES, ESZ, MT, Conv3Params, HALF, M16>(p, ncb, grid_override, &ht)) { dh::set_error("%s", why); return DH_EINVAL; }
-  static_assert(sizeof(dh_conv3::TileDesc) == sizeof(int4), "tile descriptor = int4");
-  const std::vector<int>& lane = ht.lane;
-  const std::vector<dh_conv3::TileDesc>& tile = ht.tile;
-  const std::vector<unsigned>& mask = ht.mask;
-  Conv3Tables tb;
-  DH_HIP(hipMalloc((void**)&tb.lane, lane.size() * sizeof(int)));
-  DH_HIP(hipMalloc((void**)&tb.tile, tile.size() * sizeof(int4)));
-  DH_HIP(hipMalloc((void**)&tb.mask, mask.size() * sizeof(unsigned)));
-  DH_HIP(hipMemcpy(tb.lane, lane.data(), lane.size() * sizeof(int), hipMemcpyHostToDevice));
-  DH_HIP(hipMemcpy(tb.tile, tile.data(), tile.size() * sizeof(int4), hipMemcpyHostToDevice));
-  DH_HIP(hipMemcpy(tb.mask, mask.data(), mask.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-  g_conv3_tables[key] = tb;
-  *out = tb;
-  (void)groups_img;
-  return DH_OK;
-}
-
-template <typename T, int STRIDE, int NT, int WAVES, bool DS = false, int MT = 2, bool WRES = false, int CLS = -1, bool HALF = false, bool M16 = false>
-int launch_conv3x3_cfg(Conv3Params& p, const ConvLayer& L, hipStream_t st) {
-  constexpr int STAGE_PX_BYTES = HALF ? CHUNK_BYTES / 2 : CHUNK_BYTES, CO_BLK = HALF ? 128 : 64;
-  const int win_px = p.IMGS * p.HR * p.HP + p.WTAIL;
-  const int win_bytes = win_px * STAGE_PX_BYTES;
-  const size_t wslab = (size_t)(9 + (DS ? 1 : 0)) * SLAB_TAP, win_alloc = (win_bytes + 1023) & ~1023;
-  const size_t nchunks = (size_t)L.cin * sizeof(T) / STAGE_PX_BYTES;
-  // 2-deep ring of [weight slab | window] (WRES: all weight slabs once + ring of windows) + [2][scale|shift(|ds scale|ds shift)]
-  const size_t lds = (WRES ? nchunks * wslab + 2 * win_alloc : 2 * (wslab + win_alloc)) + (HALF ? 4096 : DS ? 2048 : 1024);
-
-  constexpr int MAXJ = (STRIDE == 2) ? (WAVES == 8 ? 5 : 10) : (NT == 2 ? 6 : 4);
-  p.n_win_instr = HALF ? (win_px + 31) / 32 : (win_px + 15) / 16;
-  DH_REQUIRE(p.n_win_instr <= MAXJ * WAVES, "conv3x3: staging window too large for the DMA plan");
-  DH_REQUIRE(lds <= 160 * 1024, "conv3x3: LDS budget exceeded (%zu B)", lds);
-  DH_REQUIRE(p.FIT ? p.IMGS * p.TH * p.TW <= (WAVES * MT / 2) * NT * 32 && STRIDE == 1 && !HALF
-                   : p.IMGS * p.TH * p.TW == (HALF ? WAVES / 2 : WAVES * MT / 2) * NT * 32, "conv3x3: tile/pixel mismatch");
-  DH_REQUIRE(L.cin * (int)sizeof(T) >= 2 * CHUNK_BYTES, "conv3x3: needs at least two channel chunks");
-  const int groups = ((p.B + p.IMGS - 1) / p.IMGS) * p.tiles_y * p.tiles_x;
-  p.ntiles = groups * (L.cout / CO_BLK);
-  const int grid = std::min(256, p.ntiles);  // persistent: one workgroup per CU
-  DH_REQUIRE(!WRES || grid % (L.cout / 64) == 0, "conv3x3: resident weights need a fixed cout block per workgroup");
-  p.iters = (p.ntiles + grid - 1) / grid;
-  Conv3Tables tb;
-  int rc = conv3_tables<STRIDE, NT, WAVES, (int)sizeof(T), MT, HALF, M16>(p, L.cout / CO_BLK, groups, &tb);
-  if (rc) return rc;
-  p.lane_tab = tb.lane; p.tile_tab = tb.tile; p.mask_tab = tb.mask;
-  if constexpr (CLS >= 0) {   // parity class of a stride-2 data gradient: no cycle-stamped twin
-    if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, CLS>), 160 * 1024))) return rc;
-    hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, CLS>), dim3(grid), dim3(WAVES * 64), lds, st, p);
-    DH_LAUNCH_CHECK();
-    return DH_OK;
-  }
-  if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF, M16>), 160 * 1024)) ||
-      (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF, M16>), 160 * 1024))) return rc;
-  if (p.stamps) hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, true, DS, MT, WRES, -1, HALF, M16>), dim3(grid), dim3(WAVES * 64), lds, st, p);
-  else hipLaunchKernelGGL((conv3x3_kernel<T, STRIDE, NT, WAVES, false, DS, MT, WRES, -1, HALF, M16>), dim3(grid), dim3(WAVES * 64), lds, st, p);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// Will a 3x3 / stride-2 conv + fused downsample of this shape run on the wide kernel (conv3x3.inc, HALF)?  Then its INPUT must be written in
-// 16-channel planes by the conv before it (forward_impl decides with this before launching that conv).
-inline bool s2_wide_eligible(const ConvLayer& c1, const ConvLayer& ds, int esz, int Wo) {
-  static const bool on = dh::env_int("DH_CONV_S2_WIDE") != 0;
-  return on && esz == 2 && c1.w2_dev && ds.w2_dev && c1.cout % 128 == 0 && Wo > 4;
-}
-
-// MFMA shape of a stride-1 bf16 layer (conv3x3.inc, M16): 16x16x32 where the same-box per-layer A/B wins (profiles/conv_mfma16.txt): 64 -> 64, 256 -> 256
-// and 512 -> 512 (-2.0 / -3.2 / -4.9 % kernel time); 128 -> 128 measured -0.9 and -0.3 % on two boxes, a wash under the stamped build, and stays on
-// 32x32x16.  A function of the channel counts ONLY -- never of B, H, W or the tile variant: one layer gives the same bits at every launch size.
-// DH_CONV_MFMA16=0: 32x32x16 everywhere; so does a -DDH_CONV_HOIST=0 build (M16 reads the window through the hoisted offsets only).
-inline bool conv3_mfma16_layer(int cin, int cout) {
-  static const bool on = dh::env_int("DH_CONV_MFMA16") != 0;
-  return DH_CONV_HOIST && on && cin == cout && (cin == 64 || cin == 256 || cin == 512);
-}
-std::atomic<int> g_last_conv3_variant{-1}, g_last_conv3_mfma{0};   // dh_debug_last_conv3: tile variant / MFMA shape (M of MxMxK) of the last 3x3 launch
-
-// CLS >= 0: parity class (CLS >> 1, CLS & 1) of a stride-2 data gradient -- `in` = dZ [B][Hi][Wi][L.cin], Ho x Wo = the class's
-// rows x columns, out = the FULL-SIZE dX [B][full_h][full_w][L.cout] (NHWC), of which the class owns pixels (2 i + py, 2 j + px).
-template <typename T, int STRIDE, int CLS = -1>
-int launch_conv3x3(const ConvLayer& L, const void* in, const void* res, void* out, int B, int Hi, int Wi,
-                   bool relu, hipStream_t st, int Ho, int Wo, const ConvLayer* ds = nullptr, void* ds_out = nullptr,
-                   bool blocked = false, int full_h = 0, int full_w = 0, bool in16 = false, bool out16 = false) {
-  Conv3Params p;
-  static_assert(CLS < 0 || STRIDE == 1, "parity classes run on the stride-1 kernel");
-  DH_REQUIRE(blocked || (!in16 && !out16), "conv3x3: 16-channel planes are a variant of the channel-blocked layout");
-  DH_REQUIRE(CLS < 0 || (!blocked && !ds && full_h > 0 && full_w > 0), "conv3x3: a parity class needs the NHWC layout and the size of dX");
-  DH_REQUIRE(!blocked || sizeof(T) == 2, "conv3x3: the channel-blocked layout is the bf16 inference layout");
-  if (blocked) {   // [image][C/32][H][W][32]
-    p.in_px_bytes = CHUNK_BYTES; p.in_chunk_bytes = Hi * Wi * CHUNK_BYTES;
-    p.out_px = 32; p.out_mt = Ho * Wo * 32; p.out_cb = 2 * p.out_mt;
-  } else {         // NHWC
-    p.in_px_bytes = L.cin * (int)sizeof(T); p.in_chunk_bytes = CHUNK_BYTES;
-    p.out_px = L.cout; p.out_mt = 32; p.out_cb = 64;
-  }
-  if (CLS >= 0) {
-    p.o_img = (int64_t)full_h * full_w * L.cout; p.o_row = 2 * full_w * L.cout; p.o_px = 2 * L.cout;
-    p.o_base = ((CLS >> 1) * full_w + (CLS & 1)) * L.cout;
-  } else {
-    p.o_img = (int64_t)Ho * Wo * L.cout; p.o_row = Wo * p.out_px; p.o_px = p.out_px; p.o_base = 0;
-  }
-  // the residual shares the output's layout ...
-  p.out_pr = 16; p.res_mt = p.out_mt; p.res_pr = 16; p.r_row = p.o_row; p.r_px = p.o_px; p.r_cb = p.out_cb; p.r_base = p.o_base;
-  // ... unless this conv writes 16-channel planes [image][C/16][H][W][16] for the wide stride-2 kernel that follows (conv3x3.inc, HALF:
-  // its half-chunk stages then read whole cache lines); the residual -- the block's input -- stays in 32-channel planes
-  if (out16) {
-    p.out_px = 16; p.out_pr = Ho * Wo * 16; p.out_mt = 2 * p.out_pr; p.out_cb = 2 * p.out_mt;
-    p.o_row = Wo * 16; p.o_px = 16;
-  }
-  if (in16) { p.in_px_bytes = 32; p.in_chunk_bytes = Hi * Wi * 32; }
-  p.ds_w = ds ? ds->w_dev : nullptr; p.ds_scale = ds ? ds->scale_dev : nullptr;
-  p.ds_shift = ds ? ds->shift_dev : nullptr; p.ds_out = ds_out;
-  p.in = in; p.w = L.w_dev; p.scale = L.scale_dev; p.shift = L.shift_dev; p.res = res; p.out = out;
-  p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = L.cin; p.Cout = L.cout; p.Ho = Ho; p.Wo = Wo;
-  p.relu = relu ? 1 : 0;
-  if (int zrc = zero_page(&p.zero_page)) return zrc;
-  p.stamps = nullptr;
-  if (g_stamps_on) {
-    if (!g_stamps_dev) {
-      DH_HIP(hipMalloc((void**)&g_stamps_dev, 64 * sizeof(unsigned long long)));
-      DH_HIP(hipMemset(g_stamps_dev, 0, 64 * sizeof(unsigned long long)));
-    }
-    // one row of 8 counters per layer class: rows 0..3 stride 1 by cin 64..512, 4..6 stride 2
-    const int row = (STRIDE == 1) ? (L.cin == 64 ? 0 : L.cin == 128 ? 1 : L.cin == 256 ? 2 : 3)
-                                  : (L.cin == 64 ? 4 : L.cin == 128 ? 5 : 6);
-    p.stamps = g_stamps_dev + 8 * row;
-  }
-  bool sample = false;
-  // sampled: the dominant variant only (stride 1, 512-slot tiles: layers 1-3, and since round 5 layer 4 on its fit tiles)
-  auto maybe_sample = [&](bool dominant) -> int {
-    if (dominant && g_prof.on && g_prof.used + 2 <= g_prof.ev.size() && (g_prof.counter++ % g_prof.every) == 0) {
-      sample = true;
-      DH_HIP(hipEventRecord(g_prof.ev[g_prof.used], st));
-    }
-    return DH_OK;
-  };
-  int rc;
-  if constexpr (STRIDE == 1) {
-    p.HPH = 0;
-    // 512-pixel tiles (NT = 2) when that still gives every CU a tile; small batches of small maps (training at
-    // batch 64: 14x14 and 7x7) drop to 256- and 128-pixel tiles instead of leaving half the chip idle
-    int variant;  // 0: NT=2 MT=2 (512 px)   1: NT=1 MT=2 (256 px)   2: NT=1 MT=1 (128 px)
-    // candidates from the largest tile down; the first that gives every CU a tile wins, else the smallest (round 3: a launch
-    // with few pixels -- a parity class of a stride-2 data gradient at batch 64 -- used to run 512-pixel tiles on half the chip)
-    constexpr int min_tiles = 256;
-    // DH_CONV_FIT=0: the round-4 candidate list (power-of-two tiles only) for A/B; default: fit tiles for 7 x 7 and 14 x 14 maps too
-    static const bool fit_tiles = dh::env_int("DH_CONV_FIT") != 0;
-    const dh_conv3::Cand cd = dh_conv3::pick_stride1(B, Ho, Wo, L.cout, min_tiles, fit_tiles && CLS < 0);   // conv3_tables_host.h
-    dh_conv3::set_stride1_geometry(p, cd, Ho, Wo);
-    variant = cd.variant;
-    if ((rc = maybe_sample(variant == 0 && CLS < 0))) return rc;
-    // weights resident in LDS when the layer has one cout block and its slabs fit beside the window ring (bf16 64 -> 64)
-    const size_t wres_lds = (size_t)L.cin * sizeof(T) / CHUNK_BYTES * 9 * SLAB_TAP + 2 * (((size_t)(p.IMGS * p.HR * p.HP + p.WTAIL) * CHUNK_BYTES + 1023) & ~(size_t)1023) + 1024;
-    g_last_conv3_variant = -1; g_last_conv3_mfma = 32;
-    if constexpr (CLS >= 0)
-      rc = variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, false, CLS>(p, L, st)
-         : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8, false, 2, false, CLS>(p, L, st)
-                        : launch_conv3x3_cfg<T, 1, 1, 8, false, 1, false, CLS>(p, L, st);
-    else {
-      constexpr bool BF16 = sizeof(T) == 2;
-      const bool wres = BF16 && variant == 0 && wres_lds <= 160 * 1024;
-      bool m16 = false;
-#if DH_CONV_HOIST
-      if constexpr (BF16) m16 = conv3_mfma16_layer(L.cin, L.cout);
-#endif
-      g_last_conv3_variant = variant; g_last_conv3_mfma = m16 ? 16 : 32;
-      if constexpr (BF16 && DH_CONV_HOIST) {
-        if (m16)
-          rc = wres         ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, true, -1, false, true>(p, L, st)
-             : variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, false, -1, false, true>(p, L, st)
-             : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8, false, 2, false, -1, false, true>(p, L, st)
-                            : launch_conv3x3_cfg<T, 1, 1, 8, false, 1, false, -1, false, true>(p, L, st);
-      }
-      if (!m16)
-        rc = wres         ? launch_conv3x3_cfg<T, 1, 2, 8, false, 2, BF16>(p, L, st)
-           : variant == 0 ? launch_conv3x3_cfg<T, 1, 2, 8>(p, L, st)
-           : variant == 1 ? launch_conv3x3_cfg<T, 1, 1, 8>(p, L, st)
-                          : launch_conv3x3_cfg<T, 1, 1, 8, false, 1>(p, L, st);
-    }
-  } else {
-    g_last_conv3_variant = -1; g_last_conv3_mfma = 32;
-    // round 4: the wide variant (128 couts x 256 pixels per workgroup on half-chunk stages; conv3x3.inc, HALF) where its packing exists
-    // (bf16 inference, fused downsample, cout % 128 == 0) and the map is at least 16 pixels wide.  DH_CONV_S2_WIDE=0: the 128-pixel kernel
-    static const bool s2_wide = dh::env_int("DH_CONV_S2_WIDE") != 0;
-    if constexpr (sizeof(T) == 2) {
-      if (in16) {
-        DH_REQUIRE(s2_wide && ds && blocked && L.w2_dev && ds->w2_dev && L.cout % 128 == 0 && dh_conv3::set_stride2_wide_geometry(p, Ho, Wo),
-                   "conv3x3: an input in 16-channel planes needs the wide stride-2 kernel");
-        p.w = L.w2_dev; p.ds_w = ds->w2_dev;
-        p.out_cb = 4 * p.out_mt;   // a workgroup's cout block = four 32-cout planes
-        return launch_conv3x3_cfg<T, 2, 2, 8, true, 2, false, -1, true>(p, L, st);
-      }
-    }
-    dh_conv3::set_stride2_geometry(p, Ho, Wo);   // conv3_tables_host.h
-    // 128-pixel tiles, 8 waves: wave pairs share pixels and split the 64 couts (two waves per SIMD)
-    const size_t wres_lds = (size_t)L.cin * sizeof(T) / CHUNK_BYTES * (ds ? 10 : 9) * SLAB_TAP
-                          + 2 * (((size_t)p.IMGS * p.HR * p.HP * CHUNK_BYTES + 1023) & ~(size_t)1023) + 2048;
-    if (ds && sizeof(T) == 2 && wres_lds <= 160 * 1024) rc = launch_conv3x3_cfg<T, 2, 1, 8, true, 1, true>(p, L, st);
-    else rc = ds ? launch_conv3x3_cfg<T, 2, 1, 8, true, 1>(p, L, st) : launch_conv3x3_cfg<T, 2, 1, 8, false, 1>(p, L, st);
-  }
-  if (rc) return rc;
-  if (sample) {
-    DH_HIP(hipEventRecord(g_prof.ev[g_prof.used + 1], st));
-    g_prof.used += 2;
-    g_prof.flops += 2.0 * B * Ho * Wo * (double)L.cout * 9 * L.cin;
-  }
-  return DH_OK;
-}
-
-// Data gradient of a 3x3 / stride-2 / pad-1 convolution WITHOUT the zero-upsampled copy of dZ: four stride-1 launches, one per
-// parity class of the dX pixel (1, 2, 2 and 4 taps of the flipped + transposed operator `L.w_dev`; conv3x3.inc, CLS).  dz is
-// [B][Ho][Wo][L.cin], dx (and res, the gradient joining from another branch, may be null) [B][Hi][Wi][L.cout], NHWC.
-// (The classes write disjoint pixels and each fills at most half the chip at batch 64; running them on four streams, forked and
-// joined by events, was measured SLOWER: float32 ResNet-18 step 9.64 -> 10.63 ms -- six cross-stream dependencies per convolution
-// cost more than the idle CUs.  One stream.)
-template <typename T, int NT, int WAVES, int MT>
-int launch_dgrad_s2_merged_cfg(Conv3Params (&pc)[4], const int (&tiles_c)[4], const ConvLayer& L, hipStream_t st) {
-  // pc[k]: the parameters of class order[k] (same tile shape, own Ho x Wo and output base); one launch over all of them
-  static const int order[4] = {3, 1, 2, 0}, taps[4] = {4, 2, 2, 1};
-  constexpr int MAXJ = NT == 2 ? 6 : 4;
-  const Conv3Params& p0 = pc[0];
-  const int win_bytes = p0.IMGS * p0.HR * p0.HP * CHUNK_BYTES;
-  const size_t lds = 2 * ((size_t)9 * SLAB_TAP + ((win_bytes + 1023) & ~1023)) + 1024;
-  const int n_win_instr = (p0.IMGS * p0.HR * p0.HP + 15) / 16;
-  DH_REQUIRE(n_win_instr <= MAXJ * WAVES, "dgrad s2: staging window too large for the DMA plan");
-  DH_REQUIRE(lds <= 160 * 1024, "dgrad s2: LDS budget exceeded (%zu B)", lds);
-  DH_REQUIRE(p0.IMGS * p0.TH * p0.TW == (WAVES * MT / 2) * NT * 32, "dgrad s2: tile/pixel mismatch");
-  DH_REQUIRE(L.cin * (int)sizeof(T) >= 2 * CHUNK_BYTES, "dgrad s2: needs at least two channel chunks");
-  // workgroups per class: one at a time to the class whose (tiles per workgroup) x (taps) is largest
-  int wg[4] = {0, 0, 0, 0}, total = 0;
-  for (int k = 0; k < 4; ++k) if (tiles_c[k] > 0) { wg[k] = 1; ++total; }
-  auto cost = [&](int k) { return wg[k] > 0 ? ((tiles_c[k] + wg[k] - 1) / wg[k]) * taps[k] : 0; };
-  while (total < 256) {
-    int best = -1;
-    for (int k = 0; k < 4; ++k)
-      if (wg[k] > 0 && wg[k] < tiles_c[k] && (best < 0 || cost(k) > cost(best))) best = k;
-    if (best < 0) break;
-    ++wg[best]; ++total;
-  }
-  S2ClassSched sch;
-  sch.first[0] = 0;
-  for (int k = 0; k < 4; ++k) {
-    sch.first[k + 1] = sch.first[k] + wg[k];
-    sch.iters[k] = 0; sch.lane[k] = nullptr; sch.tile[k] = nullptr; sch.mask[k] = nullptr;
-    if (wg[k] == 0) continue;
-    Conv3Params& p = pc[k];
-    p.n_win_instr = n_win_instr;
-    p.ntiles = tiles_c[k];
-    p.iters = (tiles_c[k] + wg[k] - 1) / wg[k];
-    Conv3Tables tb;
-    int rc = conv3_tables<1, NT, WAVES, (int)sizeof(T), MT>(p, L.cout / 64, 0, &tb, wg[k]);
-    if (rc) return rc;
-    sch.iters[k] = p.iters; sch.lane[k] = tb.lane; sch.tile[k] = tb.tile; sch.mask[k] = tb.mask;
-  }
-  (void)order;
-  Conv3Params pl = pc[0];
-  pl.n_win_instr = n_win_instr;
-  pl.lane_tab = nullptr; pl.tile_tab = nullptr; pl.mask_tab = nullptr; pl.stamps = nullptr;
-  if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&conv3x3_s2dgrad_kernel<T, NT, WAVES, MT>), 160 * 1024)) return rc;
-  hipLaunchKernelGGL((conv3x3_s2dgrad_kernel<T, NT, WAVES, MT>), dim3(sch.first[4]), dim3(WAVES * 64), lds, st, pl, sch);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
-}
-
-// Data gradient of a 3x3 / stride-2 / pad-1 convolution WITHOUT the zero-upsampled copy of dZ: four stride-1 convolutions, one per
-// parity class of the dX pixel (1, 2, 2 and 4 taps of the flipped + transposed operator `L.w_dev`; conv3x3.inc, CLS), side by side in ONE
-// launch (conv3x3_s2dgrad_kernel).  dz is [B][Ho][Wo][L.cin], dx (and res, the gradient joining from another branch, may be null)
-// [B][Hi][Wi][L.cout], NHWC.  (History: four launches on one stream -- each fills a fraction of the chip at batch 64; four streams forked
-// and joined by events -- slower still, 9.64 -> 10.63 ms per float32 step.)
-template <typename T>
-int launch_dgrad_s2(const ConvLayer& L, const void* dz, const void* res, void* dx, int B, int Ho, int Wo, int Hi, int Wi, hipStream_t st) {
-  DH_REQUIRE(Ho == (Hi + 2 - 3) / 2 + 1 && Wo == (Wi + 2 - 3) / 2 + 1, "dgrad s2: %dx%d is not the stride-2 output of %dx%d", Ho, Wo, Hi, Wi);
-  int rc;
-  const int re = (Hi + 1) / 2, ro = Hi / 2, ce = (Wi + 1) / 2, co = Wi / 2;   // rows / columns of dX with even / odd index
-  if (Hi % 2 == 0 && Wi % 2 == 0) {
-    // all four classes from one staged dZ window (conv3x3.inc, CLS == 4): a stride-1 convolution over the dZ grid with four accumulator
-    // sets; 256- or 128-pixel tiles (NT = 1)
-    Conv3Params p;
-    p.in_px_bytes = L.cin * (int)sizeof(T); p.in_chunk_bytes = CHUNK_BYTES;
-    p.out_px = L.cout; p.out_mt = 32; p.out_cb = 64;
-    p.o_img = (int64_t)Hi * Wi * L.cout; p.o_row = 2 * Wi * L.cout; p.o_px = 2 * L.cout; p.o_base = 0;
-    p.out_pr = 16; p.res_mt = p.out_mt; p.res_pr = 16; p.r_row = p.o_row; p.r_px = p.o_px; p.r_cb = p.out_cb; p.r_base = 0;
-    for (int c = 0; c < 4; ++c) p.cls_base[c] = ((c >> 1) * Wi + (c & 1)) * L.cout;
-    p.ds_w = nullptr; p.ds_scale = nullptr; p.ds_shift = nullptr; p.ds_out = nullptr;
-    p.in = dz; p.w = L.w_dev; p.scale = L.scale_dev; p.shift = L.shift_dev; p.res = res; p.out = dx;
-    p.B = B; p.Hi = Ho; p.Wi = Wo; p.Cin = L.cin; p.Cout = L.cout; p.Ho = re; p.Wo = ce;
-    p.relu = 0; p.stamps = nullptr; p.HPH = 0;
-    if ((rc = zero_page(&p.zero_page))) return rc;
-    struct CandA { int th, tw, imgs, hp, mt; };
-    CandA ca[2];
-    if (ce > 8) { ca[0] = {16, 16, 1, 18, 2}; ca[1] = {8, 8, 2, 12, 1}; }
-    else { ca[0] = {8, 8, 4, 12, 2}; ca[1] = {8, 8, 2, 12, 1}; }
-    auto ntiles = [&](const CandA& c) { return ((B + c.imgs - 1) / c.imgs) * ((re + c.th - 1) / c.th) * ((ce + c.tw - 1) / c.tw) * (L.cout / 64); };
-    const CandA& cd = ntiles(ca[0]) >= 256 ? ca[0] : ca[1];
-    p.TH = cd.th; p.TW = cd.tw; p.IMGS = cd.imgs; p.HP = cd.hp; p.HR = cd.th + 2; p.HC = cd.tw + 2;
-    p.tiles_y = (re + cd.th - 1) / cd.th; p.tiles_x = (ce + cd.tw - 1) / cd.tw;
-    return cd.mt == 2 ? launch_conv3x3_cfg<T, 1, 1, 8, false, 2, false, 4>(p, L, st) : launch_conv3x3_cfg<T, 1, 1, 8, false, 1, false, 4>(p, L, st);
-  }
-  // one tile shape for all classes, picked on the largest (even, even) class: the largest tile that still gives the launch 256 tiles
-  static const int order[4] = {3, 1, 2, 0};
-  const int rows_of[4] = {re, re, ro, ro}, cols_of[4] = {ce, co, ce, co};   // by class id (py, px) = (id >> 1, id & 1)
-  struct Cand { int th, tw, imgs, hp, variant; };
-  Cand cands[4];
-  int nc = 0;
-  if (ce > 16) {
-    const int slots_a = ((re + 15) / 16) * ((ce + 31) / 32), slots_b = ((re + 7) / 8) * ((ce + 63) / 64);
-    if (slots_b < slots_a) cands[nc++] = {8, 64, 1, 66, 0};
-    else cands[nc++] = {16, 32, 1, 34, 0};
-    cands[nc++] = {16, 16, 1, 18, 1};
-  } else if (ce > 8) {
-    cands[nc++] = {16, 16, 2, 18, 0};
-    cands[nc++] = {16, 16, 1, 18, 1};
-    cands[nc++] = {8, 8, 2, 12, 2};
-  } else {
-    cands[nc++] = {8, 8, 4, 12, 1};
-    cands[nc++] = {8, 8, 2, 12, 2};
-  }
-  auto tiles_of = [&](const Cand& c, int rows, int cols) {
-    return rows > 0 && cols > 0 ? ((B + c.imgs - 1) / c.imgs) * ((rows + c.th - 1) / c.th) * ((cols + c.tw - 1) / c.tw) * (L.cout / 64) : 0;
-  };
-  int pick = nc - 1;
-  for (int i = 0; i < nc; ++i) {
-    int tot = 0;
-    for (int id = 0; id < 4; ++id) tot += tiles_of(cands[i], rows_of[id], cols_of[id]);
-    if (tot >= 256) { pick = i; break; }
-  }
-  const Cand& cd = cands[pick];
-  Conv3Params pc[4];
-  int tiles_c[4];
-  const void* zp = nullptr;
-  if (int zrc = zero_page(&zp)) return zrc;
-  for (int k = 0; k < 4; ++k) {
-    const int id = order[k], rows = rows_of[id], cols = cols_of[id];
-    Conv3Params& p = pc[k];
-    p.in_px_bytes = L.cin * (int)sizeof(T); p.in_chunk_bytes = CHUNK_BYTES;
-    p.out_px = L.cout; p.out_mt = 32; p.out_cb = 64;
-    p.o_img = (int64_t)Hi * Wi * L.cout; p.o_row = 2 * Wi * L.cout; p.o_px = 2 * L.cout;
-    p.o_base = ((id >> 1) * Wi + (id & 1)) * L.cout;
-    p.out_pr = 16; p.res_mt = p.out_mt; p.res_pr = 16; p.r_row = p.o_row; p.r_px = p.o_px; p.r_cb = p.out_cb; p.r_base = p.o_base;
-    p.ds_w = nullptr; p.ds_scale = nullptr; p.ds_shift = nullptr; p.ds_out = nullptr;
-    p.in = dz; p.w = L.w_dev; p.scale = L.scale_dev; p.shift = L.shift_dev; p.res = res; p.out = dx;
-    p.B = B; p.Hi = Ho; p.Wi = Wo; p.Cin = L.cin; p.Cout = L.cout; p.Ho = rows; p.Wo = cols;
-    p.relu = 0; p.zero_page = zp; p.stamps = nullptr;
-    p.HPH = 0; p.TH = cd.th; p.TW = cd.tw; p.IMGS = cd.imgs; p.HP = cd.hp; p.HR = cd.th + 2; p.HC = cd.tw + 2;
-    p.tiles_y = (rows + cd.th - 1) / cd.th; p.tiles_x = (cols + cd.tw - 1) / cd.tw;
-    p.lane_tab = nullptr; p.tile_tab = nullptr; p.mask_tab = nullptr; p.ntiles = 0; p.iters = 0; p.n_win_instr = 0;
-    tiles_c[k] = tiles_of(cd, rows, cols);
-  }
-  return cd.variant == 0 ? launch_dgrad_s2_merged_cfg<T, 2, 8, 2>(pc, tiles_c, L, st)
-       : cd.variant == 1 ? launch_dgrad_s2_merged_cfg<T, 1, 8, 2>(pc, tiles_c, L, st)
-                         : launch_dgrad_s2_merged_cfg<T, 1, 8, 1>(pc, tiles_c, L, st);
-}
+#include "conv3x3_launch.inc"   // plan, tables, launch of the 3x3 kernels: launch_conv3x3, launch_dgrad_s2, stamp_row
 
 template <typename T>
 int run_conv(const ConvLayer& L, const void* in, const void* res, void* out, int B, int Hi, int Wi,
@@ -1122,9 +751,8 @@ int run_conv(const ConvLayer& L, const void* in, const void* res, void* out, int
   *Ho_out = Ho; *Wo_out = Wo;
   DH_REQUIRE((int64_t)B * Hi * Wi * L.cin * (int64_t)sizeof(T) < ((int64_t)1 << 32),
              "conv %s: input larger than 4 GiB, reduce the batch", L.name.c_str());
-  if (L.ks == 3 && L.stride == 1) return launch_conv3x3<T, 1>(L, in, res, out, B, Hi, Wi, relu, st, Ho, Wo, nullptr, nullptr, blocked, 0, 0, false, out16);
-  DH_REQUIRE(!out16, "conv %s: only the stride-1 3x3 kernel writes 16-channel planes", L.name.c_str());
-  if (L.ks == 3 && L.stride == 2) return launch_conv3x3<T, 2>(L, in, res, out, B, Hi, Wi, relu, st, Ho, Wo, nullptr, nullptr, blocked);
+  DH_REQUIRE(!out16 || (L.ks == 3 && L.stride == 1), "conv %s: only the stride-1 3x3 kernel writes 16-channel planes", L.name.c_str());
+  if (L.ks == 3 && (L.stride == 1 || L.stride == 2)) return launch_conv3x3<T>(L.stride, L, in, res, out, B, Hi, Wi, relu, st, Ho, Wo, nullptr, nullptr, blocked, false, out16);
   DH_REQUIRE(!blocked, "conv %s: only the 3x3 kernels read the channel-blocked layout", L.name.c_str());
   ConvParams p;
   p.in = in; p.w = L.w_dev; p.scale = L.scale_dev; p.shift = L.shift_dev; p.res = res; p.out = out;
@@ -1185,13 +813,8 @@ int launch_stem_pool(const ConvLayer& stem, const float* x, const uint8_t* slide
   const int grid = std::min(768, sp.nstrips);  // persistent: three 4-wave workgroups per CU
   sp.iters = ((sp.nstrips + grid - 1) / grid) * sp.tiles_y;
   sp.stamps = nullptr;
-  if (g_stamps_on && slide) {
-    if (!g_stamps_dev) {
-      DH_HIP(hipMalloc((void**)&g_stamps_dev, 64 * sizeof(unsigned long long)));
-      DH_HIP(hipMemset(g_stamps_dev, 0, 64 * sizeof(unsigned long long)));
-    }
-    sp.stamps = g_stamps_dev + 8 * 7;
-  }
+  if (g_stamps_on && slide)
+    if (int rc = stamp_row(7, &sp.stamps)) return rc;
   if (int rc = pc == 16 ? launch_stem_pool_pc<16>(sp, grid, st) : launch_stem_pool_pc<15>(sp, grid, st)) return rc;
   if (nseam) {   // first pooled column of every strip but an image's first: fold in the neighbour's last conv column
     const int64_t total = (int64_t)B * nseam * H2 * 8;
@@ -1297,7 +920,7 @@ int forward_impl(dh_resnet18* net, const float* x, const uint8_t* slide, int64_t
     if (has_ds) {
       // conv1 (3x3/2 + BN + ReLU) and the 1x1/2 downsample (+ BN) of the block in ONE launch
       Ho = (H + 2 - 3) / 2 + 1; Wo = (W + 2 - 3) / 2 + 1;
-      rc = launch_conv3x3<T, 2>(c1, X, nullptr, bufB, B, H, W, true, st, Ho, Wo, &net->convs[b.ds], other, BLK, 0, 0, x16, false);
+      rc = launch_conv3x3<T>(2, c1, X, nullptr, bufB, B, H, W, true, st, Ho, Wo, &net->convs[b.ds], other, BLK, x16, false);
       if (rc) return rc;
       if ((rc = tap_after<T>(tap, net->convs[b.ds].name, other, c1.cout, Ho, Wo, BLK ? 32 : c1.cout, st))) return rc;
       resid = other;

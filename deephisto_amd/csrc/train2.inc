@@ -203,8 +203,7 @@ int t2_conv3(dh_train2* t, int cin, int cout, int stride, const void* wp, const 
   L.w_dev = const_cast<void*>(wp); L.scale_dev = t->ones; L.shift_dev = t->zeros;
   const int Ho = (Hi + 2 - 3) / stride + 1, Wo = (Wi + 2 - 3) / stride + 1;
   DH_REQUIRE((int64_t)B * Hi * Wi * cin * 2 < ((int64_t)1 << 32), "conv3x3: input larger than 4 GiB, reduce the batch");
-  return stride == 1 ? launch_conv3x3<__bf16, 1>(L, in, res, out, B, Hi, Wi, false, st, Ho, Wo)
-                     : launch_conv3x3<__bf16, 2>(L, in, res, out, B, Hi, Wi, false, st, Ho, Wo);
+  return launch_conv3x3<__bf16>(stride, L, in, res, out, B, Hi, Wi, false, st, Ho, Wo);
 }
 
 struct BnFinal {   // per-channel arrays of one BN layer (forward statistics) and its affine parameters

@@ -42,7 +42,7 @@ class Case(NamedTuple):
 
 
 CASES = [
-    # stride-2 3x3 data gradient, one case per branch of the CLS == 4 candidate table of launch_dgrad_s2 (re = ce = H / 2 rows and columns
+    # stride-2 3x3 data gradient, one case per branch of the CLS == 4 candidate table of plan_dgrad_s2 (csrc/conv3_plan_host.h) (re = ce = H / 2 rows and columns
     # per parity class; tiles = ceil(B / imgs) * ceil(re / th) * ceil(ce / tw) * cin / 64; the first candidate with >= 256 tiles wins)
     Case("dgrad3_s2_16x16x1_mt2", 3, 2, 128, 128, 32, 40, 1, False, 1),   # ce = 20 > 8: 32 * 2 * 2 * 2 = 256 tiles; ragged 16 + 4
     Case("dgrad3_s2_8x8x2_mt1", 3, 2, 64, 128, 3, 24, 1, True, 2),        # ce = 12 > 8: 16x16x1 gives 3 tiles -> 8x8x2: 2 * 2 * 2 * 1 = 8; odd batch

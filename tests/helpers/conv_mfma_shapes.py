@@ -3,7 +3,7 @@ of the test at the three launch sizes that reach tile variants 0 / 1 / 2, throug
 images shared by the three launches are bit-equal, and saves to argv[1] (.npz) the first and last shared images of each shape plus the
 (variant, MFMA shape) of each launch as the library reports them (absent in a library without dh_debug_last_conv3).
 argv[2], optional: another build of the library to load instead of the in-tree one, e.g. the parent commit's
-(tests/test_gpu_conv_mfma_shape.py::test_knob_0_reproduces_the_parent_library, tools/mfma16_vs_parent.sh)."""
+(tests/test_gpu_conv_mfma_shape.py::test_knob_0_reproduces_the_parent_library, tools/vs_parent.sh)."""
 import ctypes as C
 import sys
 from pathlib import Path

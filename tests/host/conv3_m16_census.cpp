@@ -11,38 +11,22 @@
 //     tap of every column stays inside the staged window.
 // Prints per shape "census <name> <conflicts>" and "census32 <name> <conflicts>" (the same count for the 32x32x16 lanes of the shape, over the same
 // number of service-group passes per stage), and "OK <cases>".
-#include <cstdio>
-#include <cstdlib>
 #include <set>
 #include <string>
 
-#include "../../deephisto_amd/csrc/conv3_tables_host.h"
+#include "conv3_geom.h"
 
 using namespace dh_conv3;
 
-struct Geom {   // the geometry fields of Conv3Params
-  int B, Hi, Wi, Cin, Ho, Wo, Cout;
-  int in_px_bytes, in_chunk_bytes, out_px, out_cb, out_mt;
-  int64_t o_img; int o_row, o_px, o_base;
-  int out_pr, res_mt, res_pr, r_row, r_px, r_cb, r_base;
-  int TH, TW, IMGS, tiles_y, tiles_x, HR, HC, HP, HPH, WTAIL, FIT, IP, n_win_instr, ntiles, iters;
-};
-
-#define REQUIRE(cond, ...) do { if (!(cond)) { fprintf(stderr, "VIOLATION %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); abort(); } } while (0)
-
 static long g_cases = 0;
 
-template <int NT, int MT>
-static int census(Geom p, const char* what) {
-  constexpr int WAVES = 8, NB = 2 * NT, MAXJ = max_window_pieces<1, NT, WAVES>();
+// `v`, `p`, `ncb`: the library's plan of the layer on one tile candidate (main), here on 16x16x32 MFMAs whatever the layer ships on
+static int census(Variant v, const Geom& p, int ncb, const char* what) {
+  v.m16 = 1;
+  const int WAVES = kWaves, NT = v.nt, MT = v.mt, NB = 2 * NT, MAXJ = max_window_pieces(1, NT);
   const int win_px = p.IMGS * p.HR * p.HP + p.WTAIL;
-  p.n_win_instr = (win_px + 15) / 16;
-  const int ncb = p.Cout / 64;
-  p.ntiles = ((p.B + p.IMGS - 1) / p.IMGS) * p.tiles_y * p.tiles_x * ncb;
-  const int grid = std::min(256, p.ntiles);
-  p.iters = (p.ntiles + grid - 1) / grid;
   HostTables ht;
-  const char* why = build_tables<1, NT, WAVES, 2, MT, Geom, false, true>(p, ncb, 0, &ht);
+  const char* why = build_tables(v, 2, p, ncb, 0, &ht);
   REQUIRE(!why, "%s: %s", what, why);
   REQUIRE(ht.lane_stride == 2 * NT + NB + MAXJ, "%s: lane stride", what);
   const int IP = p.IP ? p.IP : p.HR * p.HP;
@@ -90,17 +74,11 @@ static int census(Geom p, const char* what) {
 
 // the same count for the 32x32x16 lanes of the shape (conv3x3.inc: lane l reads slot 2 ks + (l >> 5) of the pixel of slot l & 31, two k-steps per
 // tap; service groups A / B of each half-wave): what the M16 tables replace
-template <int NT, int MT>
-static int census32(Geom p, const char* what) {
-  constexpr int WAVES = 8;
-  const int win_px = p.IMGS * p.HR * p.HP + p.WTAIL;
-  p.n_win_instr = (win_px + 15) / 16;
-  const int ncb = p.Cout / 64;
-  p.ntiles = ((p.B + p.IMGS - 1) / p.IMGS) * p.tiles_y * p.tiles_x * ncb;
-  const int grid = std::min(256, p.ntiles);
-  p.iters = (p.ntiles + grid - 1) / grid;
+static int census32(Variant v, const Geom& p, int ncb, const char* what) {
+  v.m16 = 0;
+  const int WAVES = kWaves, NT = v.nt, MT = v.mt;
   HostTables ht;
-  const char* why = build_tables<1, NT, WAVES, 2, MT, Geom>(p, ncb, 0, &ht);
+  const char* why = build_tables(v, 2, p, ncb, 0, &ht);
   REQUIRE(!why, "%s: %s", what, why);
   int conflicts = 0;
   for (int wave = 0; wave < WAVES; ++wave) {
@@ -132,18 +110,18 @@ int main() {
       Cand c[kMaxCands];
       const int nc = stride1_candidates(H, H, c);
       for (int i = 0; i < nc; ++i) {
+        ConvShape s;   // bf16 inference: channel-blocked, batch 64
+        s.esz = 2; s.B = 64; s.Hi = s.Wi = s.Ho = s.Wo = H; s.cin = s.cout = C; s.stride = 1; s.blocked = true;
         Geom p{};
-        p.B = 64; p.Hi = p.Wi = p.Ho = p.Wo = H; p.Cin = p.Cout = C;
-        p.in_px_bytes = kChunkBytes; p.in_chunk_bytes = H * H * kChunkBytes; p.out_px = 32; p.out_mt = H * H * 32; p.out_cb = 2 * p.out_mt;
-        p.o_img = (int64_t)H * H * C; p.o_row = H * 32; p.o_px = 32; p.o_base = 0;
-        p.out_pr = 16; p.res_mt = p.out_mt; p.res_pr = 16; p.r_row = p.o_row; p.r_px = p.o_px; p.r_cb = p.out_cb; p.r_base = 0;
-        set_stride1_geometry(p, c[i], H, H);
+        Variant v;
+        Launch ln;
+        const char* why = plan_forward(s, Knobs{}, p, &v, &ln, &c[i]);
         const std::string name = std::to_string(c[i].imgs) + "x" + std::to_string(c[i].th) + "x" + std::to_string(c[i].tw) + "/pitch" + std::to_string(c[i].hp) +
                                  (c[i].fit ? "/fit" : "") + "/v" + std::to_string(c[i].variant) + "/map" + std::to_string(H);
         if (!seen.insert(name).second) continue;
-        if (c[i].variant == 0) { census<2, 2>(p, name.c_str()); census32<2, 2>(p, name.c_str()); }
-        else if (c[i].variant == 1) { census<1, 2>(p, name.c_str()); census32<1, 2>(p, name.c_str()); }
-        else { census<1, 1>(p, name.c_str()); census32<1, 1>(p, name.c_str()); }
+        REQUIRE(!why && tile_variant(v) == c[i].variant, "%s: %s", name.c_str(), why ? why : "planned on another tile variant");
+        census(v, p, ln.ncb, name.c_str());
+        census32(v, p, ln.ncb, name.c_str());
       }
     }
   }

@@ -12,7 +12,7 @@ at least IDENTICAL of them must equal the reference bit for bit, and two runs in
 leave no prefill behind.  The strided 1x1 data gradient stores its low-resolution product before adding it into dX: its gate carries
 the half ulp of that product (lr.stored_product_gate_mask, derived there), and its identical fraction is taken against the float64
 value of those two stored roundings.  The cases (oracle/train_conv_cases.py) are the smallest shapes that reach each branch of the
-CLS == 4 candidate table of launch_dgrad_s2 (16x16x1 / 8x8x2 / 8x8x4 tiles, MT 1 and 2, ragged tiles, an odd batch, a last group of one
+CLS == 4 candidate table of plan_dgrad_s2 (csrc/conv3_plan_host.h) (16x16x1 / 8x8x2 / 8x8x4 tiles, MT 1 and 2, ragged tiles, an odd batch, a last group of one
 image), each stride-1 tile variant up to the persistent 512-pixel one (tests/test_layer_reference_host.py checks that against
 pick_stride1), the non-downsample stride-2 forward variant, and the 1x1 GEMM paths.  Batches above 16 images are referenced on a
 selection (train_conv_cases.select); the other images are held to bit-equality between the two runs.

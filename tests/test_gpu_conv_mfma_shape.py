@@ -18,7 +18,7 @@
 2. One layer, every launch size, same bits, at DH_CONV_MFMA16 = 1 and = 0 (fresh processes: the variable is read once):
    tests/helpers/conv_mfma_shapes.py.
 3. DH_CONV_MFMA16 = 0 reproduces the parent commit's library bit for bit on those shapes.  No fixture is committed: the parent library is
-   built in the same session (tools/mfma16_vs_parent.sh builds it from git and runs this test) and named by DH_PARENT_LIB; without that
+   built in the same session (tools/vs_parent.sh builds it from git and runs this test) and named by DH_PARENT_LIB; without that
    variable the test cannot run and skips.
 """
 import os
@@ -40,7 +40,7 @@ import conv_mfma_shapes as cms  # noqa: E402
 
 IDENTICAL = 0.999   # tests/test_gpu_layer_parity.py, bf16
 IMGS = {(16, 0): 2, (16, 1): 1, (8, 0): 8, (8, 1): 4, (14, 0): 5, (14, 1): 1, (7, 0): 10, (7, 1): 5}   # images per tile; variant 2: 2
-# the layers (cin, cout) that ship on 16x16x32 (resnet_kernels.hip, conv3_mfma16_layer)
+# the layers (cin, cout) that ship on 16x16x32 (conv3_plan_host.h, conv3_mfma16_layer)
 MFMA16_LAYERS = {(64, 64), (256, 256), (512, 512)}
 
 CASES = [(cin, cout, H, k, Bs[k]) for cin, cout, H, Bs in cms.SHAPES for k in range(3)]
@@ -101,11 +101,11 @@ def _helper(out, knob, lib_path=None):
     return np.load(out)
 
 
-@pytest.mark.skipif(not os.environ.get("DH_PARENT_LIB"), reason="DH_PARENT_LIB: path of the parent commit's libdeephisto_hip.so (tools/mfma16_vs_parent.sh)")
+@pytest.mark.skipif(not os.environ.get("DH_PARENT_LIB"), reason="DH_PARENT_LIB: path of the parent commit's libdeephisto_hip.so (tools/vs_parent.sh)")
 def test_knob_0_reproduces_the_parent_library(dev, tmp_path):
     parent = Path(os.environ["DH_PARENT_LIB"])
     assert parent.exists(), parent
-    a = _helper(tmp_path / "parent.npz", "1", parent)   # (the parent reads no such variable)
+    a = _helper(tmp_path / "parent.npz", "0", parent)   # (a parent from before the 16x16x32 kernels reads no such variable)
     b = _helper(tmp_path / "knob0.npz", "0")
     for cin, cout, H, _ in cms.SHAPES:
         k = f"out_{cin}_{H}"

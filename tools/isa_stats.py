@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static instruction histogram of one kernel of resnet_kernels.hip (hipcc --save-temps in /tmp/isa). Tooling only.
+"""Static instruction histogram of one kernel of the resnet_kernels.hip translation unit -- the kernels of conv3x3.inc, stem_pool.inc and the other
+   includes; their host side (conv3x3_launch.inc, conv3_plan_host.h) has no part in it -- (hipcc --save-temps in /tmp/isa). Tooling only.
    python3 tools/isa_stats.py <substring of the mangled kernel name> [more substrings...]"""
 import collections, re, subprocess, sys
 from pathlib import Path
