@@ -41,7 +41,7 @@ static void dgrad(int esz, int B, int side, int cin, int cout) {
 int main() {
   struct L { int cin, cout, stride, shift; };
   const L layers[] = {{64, 64, 1, 0}, {64, 128, 2, 0}, {128, 128, 1, 1}, {128, 256, 2, 1}, {256, 256, 1, 2}, {256, 512, 2, 2}, {512, 512, 1, 3}};
-  for (int P : {32, 64, 96, 100, 224, 256, 330}) {
+  for (int P : {32, 64, 96, 100, 200, 224, 256, 330, 512, 1024}) {
     const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
     for (const L& ly : layers) {
       int Hi = H2;
@@ -55,6 +55,7 @@ int main() {
       }
     }
   }
+  forward(4, 2600, 64, 64, 64, 1, false);   // the float32 launch whose layer-1 map lies between 2^31 and 2^32 bytes
   for (int Hi : {56, 28, 14, 7})
     for (int c : {64, 128, 256, 512}) {
       forward(2, 64, Hi, c, c, 1, false);

@@ -8,7 +8,8 @@
 //   * every window piece whose mask bit is set reads 16 bytes INSIDE the input tensor, at the pixel / channel slot the LDS image
 //     expects, and every in-image pixel of the staged window IS covered by a set bit (no padding where data should be);
 //   * every output pixel x cout block is written exactly once, inside the output tensor;
-//   * window byte offsets and output element offsets fit the 32-bit unsigned words of the schedule, per-lane offsets fit int32;
+//   * window byte offsets and output element offsets fit the 32-bit unsigned words of the schedule, per-lane offsets fit int32 (one float32 case,
+//     n = 2 600 at P = 256, is REQUIRED to carry byte offsets past 2^31: the band between the signed and the unsigned limit);
 //   * a workgroup keeps one cout block over all iterations (resident weights), mask rows < 4096;
 //   * the stride-2 data gradients (sweep_dgrad): the same per launch, and across the four parity classes together -- through cls_base of the
 //     one-window launch, or through the class sets' own tables on their shares of the merged launch -- every dX pixel x cout block is written
@@ -23,6 +24,7 @@
 using namespace dh_conv3;
 
 static long g_cases = 0;
+static uint64_t g_max_win_byte = 0, g_max_out_byte = 0;   // the largest window / output BYTE offset of a valid tile descriptor since last reset
 
 // Replays the launch `plan` (the kernel variant `v`, the parameters `p` and the launch numbers `ln`, as the library's plan functions made them;
 // `plan_why`: their refusal) on the tables the library builds for it.
@@ -67,6 +69,7 @@ static void check_case(const Variant& v, int ESZ, const Geom& p, const Launch& l
       REQUIRE(wg_cb[w] == cb, "%s: workgroup %d changes its cout block (%d -> %d)", what, w, wg_cb[w], cb);
       if (!valid) continue;
       const uint32_t win_off = (uint32_t)td.y, out_off = (uint32_t)td.z;
+      g_max_win_byte = std::max<uint64_t>(g_max_win_byte, win_off); g_max_out_byte = std::max<uint64_t>(g_max_out_byte, (uint64_t)out_off * ESZ);
       // recover the tile position from the window offset (NHWC and blocked alike: img * img_bytes + (y * Wi + x) * px_bytes)
       const int64_t img_bytes = (int64_t)p.Hi * p.Wi * p.Cin * ESZ;
       const int img0 = (int)(win_off / img_bytes);
@@ -288,7 +291,7 @@ static void sweep_dgrad(int B, int side, int cin, int cout) {
 
 int main(int argc, char** argv) {
   const bool full = argc > 1 && std::string(argv[1]) == "full";
-  const int Ps[] = {32, 64, 96, 100, 224, 256, 330};
+  const int Ps[] = {32, 64, 96, 100, 200, 224, 256, 330, 512, 1024};
   const int ns_small[] = {1, 3, 64};
   const int ns_big[] = {1024, 3842, 4096};
   // ResNet-18 body: (cin, cout, stride, input map = pooled size / 2^stage)
@@ -300,6 +303,7 @@ int main(int argc, char** argv) {
       int Hi = H2;
       for (int s = 0; s < ly.shift; ++s) Hi = (Hi + 2 - 3) / 2 + 1;
       for (int n : ns_small) {
+        if (P >= 512 && n > 3) continue;   // 128- and 256-wide maps: the tile positions are the subject, not the batch
         sweep_layer<2>(n, Hi, ly.cin, ly.cout, ly.stride, true, "inf-bf16");    // bf16 inference: channel-blocked
         if (ly.stride == 1 && ly.cin == ly.cout) sweep_layer<2>(n, Hi, ly.cin, ly.cout, 1, true, "inf-bf16", true);   // ... writing 16-channel planes
         if (ly.stride == 2 && ly.cout % 128 == 0 && (Hi + 2 - 3) / 2 + 1 > 4) sweep_layer<2>(n, Hi, ly.cin, ly.cout, 2, true, "inf-bf16", false, true);   // the wide stride-2 variant
@@ -308,7 +312,7 @@ int main(int argc, char** argv) {
       }
       // the launch sizes the headline number is timed at: only where the coverage bitmap stays small enough for a unit test,
       // i.e. the large n on the layers of P in {64, 256} (P = 256, n = 4096, layer 1 is THE 2^31-byte map of VERDICT r3 missing #1)
-      if (P == 256 || P == 64 || full)
+      if (P == 256 || P == 64 || (full && P <= 330))
         for (int n : ns_big) {
           if (!full && P == 256 && ly.shift > 1 && n != 4096) continue;
           sweep_layer<2>(n, Hi, ly.cin, ly.cout, ly.stride, true, "inf-bf16");
@@ -322,6 +326,13 @@ int main(int argc, char** argv) {
   }
   // float32 at 4 096 tiles of 256^2: the layer-1 map is 2^32 bytes -- must be REFUSED, not wrapped
   sweep_layer<4>(4096, 64, 64, 64, 1, false, "f32-oversize");
+  // float32 at 2 600 tiles of 256^2: a layer-1 map of 2.73e9 bytes, inside the band (2^31, 2^32) the launch check admits -- the replay must
+  // pass with window and output byte offsets past 2^31 (the kernel reads the 32-bit words as unsigned)
+  g_max_win_byte = g_max_out_byte = 0;
+  sweep_layer<4>(2600, 64, 64, 64, 1, false, "f32-band");
+  REQUIRE(g_max_win_byte > ((uint64_t)1 << 31) && g_max_out_byte > ((uint64_t)1 << 31), "f32-band: largest window / output byte offset %" PRIu64 " / %" PRIu64 " does not exceed 2^31",
+          g_max_win_byte, g_max_out_byte);
+  printf("f32-band: largest window / output byte offset %" PRIu64 " / %" PRIu64 "\n", g_max_win_byte, g_max_out_byte);
   // odd maps of training shapes (224 -> 56 / 28 / 14 / 7) at batch 64 with the 3x3 layers of ResNet-50
   for (int Hi : {56, 28, 14, 7})
     for (int c : {64, 128, 256, 512}) {

@@ -35,7 +35,7 @@ import slide_scale as SS  # noqa: E402
 import stain_aug_ref as A  # noqa: E402
 import stain_ref as R  # noqa: E402
 
-import test_gpu_layer_parity as LP  # noqa: E402
+import layer_parity as LP  # noqa: E402
 from deephisto_amd import geom_aug as GA  # noqa: E402
 from deephisto_amd import stain as S  # noqa: E402
 from deephisto_amd._lib import DH_DTYPE_BF16, DH_DTYPE_F32, DH_LAYOUT_NCHW, DH_LAYOUT_NHWC  # noqa: E402

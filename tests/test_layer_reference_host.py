@@ -265,3 +265,77 @@ def test_stride1_cases_land_on_the_intended_tile_variant(tmp_path):
         assert (v, n) == (variant, tiles), (name, r.stdout)
         if c.B > 16:
             assert imgs == c.imgs, name
+
+
+@pytest.mark.skipif(__import__("shutil").which("g++") is None, reason="g++ not available")
+def test_range_cases_reach_the_launch_classes_their_table_claims(tmp_path):
+    """The ResNet-18 cases of tests/test_gpu_layer_parity_range.py (tests/helpers/layer_parity.py, RANGE_CASES) through the engine's own launch
+    plan (tests/host/conv3_plan_probe.cpp): their union reaches every class below, and each class is reached by the patch size the range
+    file's table names for it.  The plan is the authority: the table follows it."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    repo = Path(__file__).resolve().parents[1]
+    sys.path.insert(0, str(repo / "tests" / "helpers"))
+    import layer_parity as lp
+    exe = tmp_path / "conv3_plan_probe"
+    b = subprocess.run(["g++", "-std=c++17", "-O1", str(repo / "tests" / "host" / "conv3_plan_probe.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-2000:]
+    reached, seen = {}, {}
+    for arch, dtype, P, n in lp.RANGE_CASES:
+        if arch != "r18":
+            continue
+        for args in lp.r18_conv3_launches(dtype, P, n):
+            if args not in seen:
+                r = subprocess.run([str(exe)] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
+                assert r.returncode == 0 and "refused" not in r.stdout, (args, r.stdout, r.stderr)
+                f = r.stdout.split()
+                assert f[1] == "v" and f[11] == "tile", r.stdout
+                seen[args] = ([int(t) for t in f[2:10]], [int(t) for t in f[12:23]])
+            (stride, nt, mt, ds, wres, cls, half, m16), (TH, TW, IMGS, ty, tx, HR, HC, HP, HPH, WTAIL, FIT) = seen[args]
+            esz, B, Hi, cin, cout, s, blocked, out16, wide, _ = args
+            Ho = (Hi - 1) // s + 1
+            assert stride == s and half == wide
+            hit = []
+            if s == 1:
+                hit.append(f"stride-1 variant {0 if nt == 2 else 1 if mt == 2 else 2}")
+                if (TH, TW, FIT) == (8, 64, 0) and Ho % 8 and Ho % 64:
+                    hit.append("8x64 ragged")
+                if (TH, TW, FIT) == (16, 32, 0) and Ho % 16 and Ho % 32:
+                    hit.append("16x32 ragged")
+                if (TH, TW, IMGS) == (16, 16, 2):
+                    hit.append("16x16 two-image")
+                if FIT and (TH, IMGS) == (7, 10):
+                    hit.append(f"fit 7x7 x10 cout {cout}")
+                if FIT and (TH, IMGS) == (8, 8):
+                    hit.append(f"fit 8x8 x8 cout {cout}")
+                if m16 and wres:
+                    hit.append("m16 wres")
+            elif half:
+                if (TH, TW) == (16, 16):
+                    hit.append("wide stride-2 16x16")
+                if (TH, TW, IMGS) == (8, 8, 4) and Hi % 2:
+                    hit.append("wide stride-2 8x8x4 odd input")
+            else:
+                hit.append(f"128-pixel stride-2 Wo {Ho}")
+            for h in hit:
+                reached.setdefault(h, set()).add((dtype, P, n))
+        # the walk's last launch (layer4.1.conv2) runs the variant the GPU test requires of the engine's own report after the same forward
+        assert (0 if nt == 2 else 1 if mt == 2 else 2) == lp.LAST_VARIANT[(dtype, P, n)], (dtype, P, n)
+    # class -> a (dtype, P) of the table that must be among the cases reaching it
+    want = {"stride-1 variant 0": ("bf16", 200), "stride-1 variant 1": ("bf16", 330), "stride-1 variant 2": ("f32", 32),
+            "8x64 ragged": ("bf16", 200), "16x32 ragged": ("bf16", 97), "16x16 two-image": ("bf16", 97),
+            "fit 7x7 x10 cout 256": ("bf16", 97), "fit 7x7 x10 cout 512": ("bf16", 200), "fit 8x8 x8 cout 64": ("bf16", 32),
+            "m16 wres": ("bf16", 512), "wide stride-2 16x16": ("bf16", 512), "wide stride-2 8x8x4 odd input": ("bf16", 97),
+            "128-pixel stride-2 Wo 4": ("bf16", 32), "128-pixel stride-2 Wo 2": ("bf16", 32), "128-pixel stride-2 Wo 1": ("bf16", 32)}
+    for name in sorted(reached):
+        print(f"{name}: {sorted(reached[name])}")
+    for name, (dtype, P) in want.items():
+        assert name in reached, f"no case reaches '{name}'"
+        assert any((d, p) == (dtype, P) for d, p, _ in reached[name]), (name, sorted(reached[name]))
+    # 16x32 ragged BOTH ways (25 and 21), the odd-input wide tiles of both odd chains, and the 128-pixel 7 -> 4 of P = 97 (layer 3 must not write 16-channel planes)
+    assert {97, 330} <= {p for _, p, _ in reached["16x32 ragged"]} and {97, 330} <= {p for _, p, _ in reached["16x16 two-image"]}
+    assert any(p == 97 for _, p, _ in reached["128-pixel stride-2 Wo 4"])
+    # ten 7 x 7 images per tile at cout 512 take 256 tiles = 32 image groups x 8 cout blocks: n >= 311, not the table's first n = 300 (five per tile)
+    assert ("bf16", 200, 311) in reached["fit 7x7 x10 cout 512"] and ("bf16", 200, 300) not in reached["fit 7x7 x10 cout 512"]

@@ -166,7 +166,7 @@ def test_stem_reference_rejects_a_wrapped_tile(closed):
     elements, so a stem that wrapped could not pass tests/test_gpu_slide_scale.py."""
     import torch
     from oracle import layer_ref as lr
-    from test_gpu_layer_parity import _oracle
+    from layer_parity import _oracle
     ref = _oracle("r18")
     P = 96
     o = SS.spots(H, W, P)
