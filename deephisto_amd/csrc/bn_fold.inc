@@ -14,7 +14,7 @@
 //     shift / running statistics; dgamma / dbeta).  With <= 128 partial rows that is <= 64 KB of L2-resident reads per workgroup;
 //   * the partial rows come from the 1x1 GEMM's epilogue (gemm1x1.inc: one row per 128-pixel tile: 25 / 98 rows at 7 x 7 / 14 x 14)
 //     or from channel-sliced reduction kernels that leave ONE row per row group (<= 32 rows).
-// Arithmetic is that of bn_stat_finalize_onepass_kernel / bn_bwd_finalize_kernel (train.inc) and bn2_apply / bn2_bwd_apply
+// Arithmetic is that of bn_stat_finalize_onepass_kernel / bn_bwd_finalize_kernel (train_core_kernels.inc) and bn2_apply / bn2_bwd_apply
 // (train2_kernels.inc), partial rows added in the finalize kernels' own order: the same bits from the same rows.
 namespace {
 
@@ -22,7 +22,7 @@ constexpr int CS_CH = 64;          // channels per slice
 constexpr int CS_MAX_ROWS = 128;   // partial rows a consumer prologue accepts
 
 // column sums of partial[nb][2][C] for channels c0 .. c0 + 63 (two sums per channel), left in LDS as doubles s[k][ch].  The ORDER is
-// that of partial_colsum (train.inc), so a folded prologue and the finalize launch give the same bits from the same rows: 16 phases,
+// that of partial_colsum (train_core_kernels.inc), so a folded prologue and the finalize launch give the same bits from the same rows: 16 phases,
 // phase p adds rows p, p + 16, p + 32, ... in increasing order, the 16 phase sums are added in index order.  Thread = (channel, 4 phases).
 __device__ __forceinline__ void cs_colsum(const float* __restrict__ partial, int nb, int C, int c0, double (*s)[CS_CH]) {
   __shared__ double sh[16][2][CS_CH];

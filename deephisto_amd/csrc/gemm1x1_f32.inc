@@ -1,5 +1,5 @@
 // gemm1x1_f32.inc -- the 1x1 convolutions of the FLOAT32 training engine (train.inc) as an NT GEMM on v_mfma_f32_32x32x2_f32 (round 5).
-// Included before train.inc (same translation unit).
+// Included before train_core_kernels.inc / train.inc (same translation unit).
 //
 //   out[m][n] = sum_k A[row(m)][k] * W[n][k]  (+ res[m][n]),   m = output pixel, n = channel; both operands K-contiguous.
 //

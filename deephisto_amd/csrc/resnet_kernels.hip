@@ -1226,7 +1226,9 @@ extern "C" int dh_debug_stem_strip_width(int32_t pc) {
 }
 
 #include "gemm1x1_f32.inc"
+#include "train_core_kernels.inc"
 #include "train_core.inc"
+#include "train_kernels.inc"
 #include "train.inc"
 #include "train2_kernels.inc"
 #include "wgrad_ring.inc"

@@ -22,15 +22,8 @@
 // stream's hand-off are train_core.inc's, shared with the float32 engine.
 #include <type_traits>
 
-struct T2Conv : ConvDesc {   // the description (net_desc.inc) plus this engine's buffers
-  int Hi = 0, Wi = 0, Ho = 0, Wo = 0;
-  void* wp_f = nullptr;   // bf16 forward operand: 3x3 fragment order | 1x1 W[cout][cin] | 7x7 stem layout
-  void* wp_d = nullptr;   // bf16 dgrad operand: 3x3 flipped + transposed fragment order | 1x1 Wt[cin][cout]
-  bf16_t* Z = nullptr;    // conv output (pre-BN), NHWC
-  bf16_t* Y = nullptr;    // BN (+identity) (+ReLU) output, NHWC
+struct T2Conv : TrainConvT<bf16_t> {   // the shared record (train_core.inc); operands: 3x3 fragment order | 1x1 W[cout][cin] / Wt[cin][cout] | 7x7 stem layout
   uint8_t* Ybits = nullptr;   // top conv of a block: ReLU pattern of Y, one byte per 8 channels (st8_bits; read by the successor's dgrad GEMM)
-  bf16_t* dZ = nullptr;   // side-stream weight gradients only: this conv's own dZ buffer (read by the side stream long after it was written)
-  BnBufs bnb{};
 };
 
 struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order: every completion item is one convolution (or fc)
@@ -53,9 +46,7 @@ struct dh_train2 : TrainStore {   // the arenas are in BACKWARD-completion order
   bool last_training = false;
   bool bwd_done = false;    // a backward pass has run since the last forward: every dZ buffer holds THIS step's gradient (the dZ tap, train_hooks.inc)
   bool packed = false;
-  PackDesc* pack_desc = nullptr;   // device table of t2_pack_all (one launch packs every conv)
-  int pack_blocks = 0;
-  std::vector<int> pack_blk0;      // first workgroup of every conv's descriptor (+ the total), host copy
+  PackTable<PackDesc> pack;        // table of pack_all_kernel (one launch packs every conv); descriptor j = conv j
 };
 
 namespace {
@@ -86,10 +77,7 @@ void t2_layout(dh_train2* t) {
   int64_t done = 0;   // the arena up to here is covered by items
   auto item_done = [&]() { t->items.push_back({done, t->n_params - done}); done = t->n_params; };
   auto add_conv = [&](int i) {
-    const T2Conv& c = t->convs[i];
-    store_add(*t, c.bn + ".weight", c.cout); store_add(*t, c.bn + ".bias", c.cout);
-    store_add(*t, c.name + ".weight", (int64_t)c.cout * c.cin * c.ks * c.ks);
-    store_radd(*t, c.bn + ".running_mean", c.cout); store_radd(*t, c.bn + ".running_var", c.cout);
+    store_add_conv(*t, t->convs[i], false);
     item_done();
   };
   store_add(*t, "fc.weight", (int64_t)t->n_classes * t->feat); store_add(*t, "fc.bias", t->n_classes);
@@ -104,29 +92,20 @@ void t2_layout(dh_train2* t) {
 
 // packs the weights of convs [i0, i1) (all of them by default)
 int t2_pack(dh_train2* t, hipStream_t st, int i0 = 0, int i1 = -1) {
-  if (!t->pack_desc) {   // the descriptors only hold device addresses that stay put for the life of the handle
-    std::vector<PackDesc> d;
-    int blk = 0;
-    t->pack_blk0.clear();
+  if (!t->pack.dev) {
     for (const T2Conv& c : t->convs) {
-      t->pack_blk0.push_back(blk);
       const int64_t n = c.ks == 7 ? 7 * 2 * 2 * 64 * 8 : (int64_t)c.cout * c.cin * c.ks * c.ks;
-      d.push_back({t->Pm + t->slot[c.name + ".weight"].first, static_cast<bf16_t*>(c.wp_f), static_cast<bf16_t*>(c.wp_d), c.cout, c.cin,
-                   c.ks, blk});
-      if (c.ks == 3) blk += (c.cout / 64) * (c.cin / 64);                            // one workgroup per 64 x 64 tile (pack3_tile)
-      else if (c.ks == 1) blk += std::min(64, (c.cout / 64) * (c.cin / 64));             // 64 x 64 tiles, a few per workgroup
-      else blk += (int)std::max<int64_t>(1, std::min<int64_t>(64, (n + 8191) / 8192));   // stem: 32 elements per thread
+      t->pack.add({t->Pm + t->slot[c.name + ".weight"].first, static_cast<bf16_t*>(c.wp_f), static_cast<bf16_t*>(c.wp_d), c.cout, c.cin, c.ks, 0},
+                  c.ks == 3 ? (c.cout / 64) * (c.cin / 64)                                   // one workgroup per 64 x 64 tile (pack3_tile)
+                  : c.ks == 1 ? std::min(64, (c.cout / 64) * (c.cin / 64))                   // 64 x 64 tiles, a few per workgroup
+                              : (int)std::max<int64_t>(1, std::min<int64_t>(64, (n + 8191) / 8192)));   // stem: 32 elements per thread
     }
-    DH_HIP(hipMalloc(reinterpret_cast<void**>(&t->pack_desc), d.size() * sizeof(PackDesc)));
-    t->allocs.push_back(t->pack_desc);   // freed with the handle (not with the batch-shape buffers)
-    DH_HIP(hipMemcpy(t->pack_desc, d.data(), d.size() * sizeof(PackDesc), hipMemcpyHostToDevice));
-    t->pack_blocks = blk;
-    t->pack_blk0.push_back(blk);
+    if (int rc = t->pack.upload(*t)) return rc;
   }
   if (i1 < 0) i1 = (int)t->convs.size();
   if (int arc = ensure_dyn_lds(reinterpret_cast<const void*>(&pack_all_kernel), PACK3_LDS)) return arc;
-  hipLaunchKernelGGL(pack_all_kernel, dim3(t->pack_blk0[i1] - t->pack_blk0[i0]), dim3(256), PACK3_LDS, st, t->pack_desc + i0, i1 - i0,
-                     t->pack_blk0[i0]);
+  const auto l = t->pack.range(i0, i1);
+  hipLaunchKernelGGL(pack_all_kernel, dim3(l.grid), dim3(256), PACK3_LDS, st, l.first, l.count, l.blk_base);
   DH_LAUNCH_CHECK();
   return DH_OK;
 }
@@ -566,17 +545,13 @@ int t2_bn_pool_bwd(dh_train2* t, T2Conv& c, const bf16_t* dpool, const uint8_t* 
 // most STEM_WGRAD_SLABS runs of output rows on bf16 MFMA (stem_wgrad_bf16_kernel; `slabs`: STEM_WGRAD_SLABS * 64 * 160 floats), then
 // their fixed-order reduction.
 int t2_stem_wgrad(const bf16_t* dz, const float* x, float* slabs, float* dw, int B, int P, int Ho, int Wo, hipStream_t st) {
-  const int total_rows = B * Ho;
-  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
-  const int n_slabs = (total_rows + rpb - 1) / rpb;
+  const StemSlabs sl = stem_wgrad_split(B, Ho);
   DH_REQUIRE(Wo * 8 <= 2 * SWG_T && P + 6 <= SWG_T, "stem wgrad: patch %d too wide for the row staging", P);
   DH_REQUIRE(Wo % 16 == 0, "stem wgrad (bf16 MFMA): the output width %d is not a multiple of 16 pixels", Wo);
   const size_t lds = std::max<size_t>(((size_t)((21 * (P + 6) + 7) & ~7) + (size_t)Wo * 64) * 2, (size_t)64 * 160 * sizeof(float));
-  hipLaunchKernelGGL(stem_wgrad_bf16_kernel, dim3(n_slabs), dim3(SWG_T), lds, st, dz, x, slabs, B, P, Ho, Wo, rpb);
+  hipLaunchKernelGGL(stem_wgrad_bf16_kernel, dim3(sl.n_slabs), dim3(SWG_T), lds, st, dz, x, slabs, B, P, Ho, Wo, sl.rows_per_slab);
   DH_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw);
-  DH_LAUNCH_CHECK();
-  return DH_OK;
+  return stem_wgrad_reduce(slabs, sl.n_slabs, dw, st);
 }
 
 void t2_free_shape(dh_train2* t) {
@@ -593,30 +568,16 @@ int t2_shape(dh_train2* t, int B, int P) {
   const int H1 = (P + 6 - 7) / 2 + 1, H2 = (H1 + 2 - 3) / 2 + 1;
   int64_t maxact = (int64_t)B * H1 * H1 * 64;
   int rc;
-  auto setup = [&](int i, int hi, bool top = false) -> int {
-    T2Conv& c = t->convs[i];
-    c.Hi = c.Wi = hi;
-    c.Ho = c.Wo = (hi + 2 * (c.ks / 2) - c.ks) / c.stride + 1;
-    const int64_t nout = (int64_t)B * c.Ho * c.Wo * c.cout;
-    maxact = std::max(maxact, std::max(nout, (int64_t)B * hi * hi * std::max(c.cin, 8)));
-    maxact = std::max(maxact, (int64_t)B * hi * hi * c.cout);   // zero-upsampled gradient of a stride-2 conv
-    int r;
-    if ((r = store_alloc(*t, &c.Z, nout)) || (r = store_alloc(*t, &c.Y, nout))) return r;
-    if (top && (r = store_alloc(*t, &c.Ybits, nout / 8))) return r;
-    if (t->side_wgrad && i > 0 && (r = store_alloc(*t, &c.dZ, nout))) return r;
-    return DH_OK;
-  };
-  if ((rc = setup(0, P))) return done(rc);
-  int H = H2;
-  for (const BlockDesc& b : t->blocks) {
-    int h = H;
-    for (int i = 0; i < b.nconv; ++i) {
-      if ((rc = setup(b.conv[i], h, i + 1 == b.nconv))) return done(rc);
-      h = t->convs[b.conv[i]].Ho;
-    }
-    if (b.ds >= 0 && (rc = setup(b.ds, H))) return done(rc);
-    H = h;
-  }
+  if ((rc = conv_shapes(t->convs, t->blocks, P, [&](T2Conv& c, int i, bool top) -> int {
+        const int64_t nout = (int64_t)B * c.Ho * c.Wo * c.cout;
+        maxact = std::max(maxact, std::max(nout, (int64_t)B * c.Hi * c.Hi * std::max(c.cin, 8)));
+        maxact = std::max(maxact, (int64_t)B * c.Hi * c.Hi * c.cout);   // zero-upsampled gradient of a stride-2 conv
+        int r;
+        if ((r = store_alloc(*t, &c.Z, nout)) || (r = store_alloc(*t, &c.Y, nout))) return r;
+        if (top && (r = store_alloc(*t, &c.Ybits, nout / 8))) return r;
+        if (t->side_wgrad && i > 0 && (r = store_alloc(*t, &c.dZ, nout))) return r;
+        return DH_OK;
+      }))) return done(rc);
   const int64_t S1 = (int64_t)B * H2 * H2 * 64;
   if ((rc = store_alloc(*t, &t->X1, S1)) || (rc = store_alloc(*t, &t->pool_idx, S1)) || (rc = store_alloc(*t, &t->pooled, (int64_t)B * t->feat)))
     return done(rc);
@@ -644,7 +605,7 @@ extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_cla
   if (int erc = dh::env_check()) return erc;   // a mistyped DH_* switch stops here, named by dh_last_error()
   auto* t = new dh_train2();
   t->n_classes = n_classes; t->feat = desc->feat; t->blocks = desc->blocks;
-  for (const ConvDesc& d : desc->convs) t->convs.push_back(T2Conv{d});
+  convs_from_desc(t->convs, *desc);
   t2_layout(t);
   int rc;
   auto fail = [&](int r) { store_free_all(*t); delete t; return r; };
@@ -657,8 +618,7 @@ extern "C" int dh_train2_create(dh_train2** out, const char* arch, int32_t n_cla
     const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;   // operands in bf16
     if (c.ks == 7) { if ((rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_f), 7 * 2 * 2 * FRAG_BYTES / 2))) return fail(rc); }
     else if ((rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_f), nw)) || (rc = store_alloc(*t, reinterpret_cast<bf16_t**>(&c.wp_d), nw))) return fail(rc);
-    float** bb[7] = {&c.bnb.mean, &c.bnb.invstd, &c.bnb.scale, &c.bnb.shift, &c.bnb.k0, &c.bnb.k1, &c.bnb.k2};
-    for (auto q : bb) if ((rc = store_alloc(*t, q, c.cout))) return fail(rc);
+    if ((rc = store_alloc_bn(*t, c.bnb, c.cout))) return fail(rc);
   }
   store_set_buckets(*t, 0, nullptr, nullptr, nullptr);   // one bucket until the caller cuts its own
   // The weight-gradient kernels (one workgroup per CU, bound by their operand ingest) run on a side stream next to the HBM-bound
@@ -828,45 +788,14 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
   hipLaunchKernelGGL(fc_wgrad_kernel, dim3((ncls * t->feat + 255) / 256), dim3(256), 0, st, dlogits, t->pooled, B, t->feat, ncls,
                      t->G + t->slot["fc.weight"].first, t->G + t->slot["fc.bias"].first);
   bf16_t *dOut = t->GB[0], *Gm = t->GB[1], *dZ = t->GB[2], *dY = t->GB[3], *dX = t->GB[4], *scr = t->GB[5];
-  // Side-stream weight gradients.  Every convolution owns its dZ buffer (HBM is plentiful), so the main stream never waits for
-  // the side stream inside the pass; the weight-gradient launches of a group of blocks are queued behind ONE event of the main
-  // stream (an event record or wait stalls the recording queue for about 6 us: one hand-off per convolution cost 0.67 ms of a
-  // 7.7 ms ResNet-50 step, profiles/r03_exp_side_handoff.txt).  Buckets and the optimiser wait for the side stream.
+  // Which stream a weight gradient runs on, the hand-offs, the joins and the fused optimiser are BwdSched's (train_core.inc): this pass
+  // hands a block's weight gradients over behind the block and joins only where a bucket is due -- and in front of the stem's tail.
   const bool side = t->side_wgrad;
-  struct PendingW { T2Conv* c; const bf16_t* xin; const bf16_t* dz; };
-  std::vector<PendingW> pending;
+  auto sched = bwd_sched<bf16_t>(*t, st, fused, (int)t->convs.size(),
+      [&](int i, const bf16_t* xin, const bf16_t* dz, hipStream_t q) { return t2_wgrad(t, t->convs[i], xin, dz, q); },
+      [&](int lo, int hi, hipStream_t q) { return t2_pack(t, q, lo, hi + 1); }, (g_t2_abl & 8) != 0, (g_t2_abl & 8) != 0);
   auto next_dz = [&](T2Conv& c) { if (side && c.dZ) dZ = c.dZ; };
-  auto wgrad_of = [&](T2Conv& c, const bf16_t* xin) -> int {
-    if (!side) return t2_wgrad(t, c, xin, dZ, st);
-    pending.push_back({&c, xin, dZ});
-    return DH_OK;
-  };
-  int64_t adam_off = 0;   // fused optimiser: the arena up to here has been updated
-  auto flush_side = [&]() -> int {   // hand the queued weight gradients to the side stream
-    if (pending.empty()) return DH_OK;
-    int r = side_handoff(*t, st);
-    if (r) return r;
-    int lo = (int)t->convs.size(), hi = -1;
-    for (const PendingW& w : pending) {
-      if ((r = t2_wgrad(t, *w.c, w.xin, w.dz, t->side))) return r;
-      const int ci = (int)(w.c - t->convs.data());
-      lo = std::min(lo, ci); hi = std::max(hi, ci);
-    }
-    if (fused) {   // every gradient of the items marked done so far is complete once the side stream gets here
-      const int64_t upto = t->items[t->items_done - 1].first + t->items[t->items_done - 1].second;
-      DH_REQUIRE(hi - lo + 1 == (int)pending.size(), "train2 backward: the convolutions of a hand-off are not a contiguous range");
-      if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, upto - adam_off, t->side);
-      adam_off = upto;
-      if (!(g_t2_abl & 8) && (r = t2_pack(t, t->side, lo, hi + 1))) return r;
-    }
-    pending.clear();
-    return DH_OK;
-  };
-  auto join_side = [&]() -> int {   // everything handed to the side stream so far precedes what the main stream does next
-    if (!side) return DH_OK;
-    int r = flush_side();
-    return r ? r : side_join(*t, st);
-  };
+  auto wgrad_of = [&](int i, const bf16_t* xin) { return sched.queue(i, xin, dZ); };
   auto bucket_due = [&]() { return store_bucket_due(*t); };
   int top_rows = 0;   // rows of BN-backward sums the last dgrad GEMM left for the NEXT block's join BN (0: none)
   hipLaunchKernelGGL(avgpool_fc_dgrad2_kernel, dim3(B), dim3(256), 0, st, dlogits, t->Pm + t->slot["fc.weight"].first, HW, t->feat, ncls, dOut);
@@ -903,7 +832,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
       if (route && top && !pm && tap->g_out) hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(grid_for(n_c)), dim3(256), 0, st, Gm, tap->g_out, n_c);
       rows = 0;
       const bf16_t* xin = i == 0 ? Xin : t->convs[b.conv[i - 1]].Y;
-      if ((rc = wgrad_of(c, xin))) return rc;
+      if ((rc = wgrad_of(b.conv[i], xin))) return rc;
       if (i > 0) {
         const T2Conv* below = &t->convs[b.conv[i - 1]];   // its BN output feeds a ReLU directly: mode 2
         if ((rc = t2_conv_dgrad(t, c, dZ, nullptr, dY, scr, false, st, nullptr, below, 2, &rows))) return rc;
@@ -912,7 +841,7 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
         const T2Conv* prev_top = (in_mask && b.ds < 0) ? &t->convs[t->blocks[bi - 1].conv[t->blocks[bi - 1].nconv - 1]] : nullptr;
         if ((rc = t2_conv_dgrad(t, c, dZ, b.ds < 0 ? gm : nullptr, dX, scr, false, st, b.ds < 0 ? in_mask : nullptr, prev_top, 0, &top_rows))) return rc;
       }
-      if (bucket_due() && (rc = join_side())) return rc;
+      if (bucket_due() && (rc = sched.join(0))) return rc;
       mark_done();
     }
     if (b.ds >= 0) {
@@ -920,12 +849,12 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
       next_dz(d);
       int32_t* route = tap_in(d, gm, (int64_t)B * d.Ho * d.Wo * d.cout, 0, pm, false, 0, T2R_BRANCH_IS_DOWNSAMPLE);
       if ((rc = t2_bn_bwd(t, d, gm, nullptr, 0, dZ, nullptr, st, 0, route))) return rc;
-      if ((rc = wgrad_of(d, Xin))) return rc;
+      if ((rc = wgrad_of(b.ds, Xin))) return rc;
       if ((rc = t2_conv_dgrad(t, d, dZ, nullptr, dX, scr, true, st))) return rc;
-      if (bucket_due() && (rc = join_side())) return rc;
+      if (bucket_due() && (rc = sched.join(0))) return rc;
       mark_done();
     }
-    if (side && (rc = flush_side())) return rc;
+    if ((rc = sched.flush(0))) return rc;   // behind the block: its items are marked done
     std::swap(dOut, dX);
   }
   {   // stem: maxpool backward, BN + ReLU backward, weight gradient (f32 MFMA on the f32 input image)
@@ -940,15 +869,11 @@ int t2_backward(dh_train2* t, const float* dlogits, hipStream_t st, const AdamAr
     // not reproducible (ResNet-50, P = 96, B = 32: 8 to 39 of 39 identical steps differed in one to six channels of dgamma / dbeta by up to
     // 3 % of the largest, operands bit-identical; none without the side stream: tests/test_gpu_step_bwd.py, FOUND).  Nothing is handed to
     // the side stream after this point, so the join that the optimiser needs anyway moves in front of the tail.
-    if ((rc = join_side())) return rc;
+    if ((rc = sched.join(0))) return rc;
     if ((rc = t2_bn_pool_bwd(t, c, dOut, t->pool_idx, dZ, st))) return rc;   // maxpool + ReLU + BN backward, dY never materialised
     if ((rc = t2_stem_wgrad(dZ, t->x_in, t->stem_slabs, t->G + t->slot["conv1.weight"].first, B, t->P, c.Ho, c.Wo, st))) return rc;
     mark_done();   // the optimiser (and the last bucket) follow on the main stream, behind the join above
-    if (fused) {   // what the side stream has not updated: the stem (all of the arena without a side stream)
-      if (!(g_t2_abl & 8)) adam_range(*t, *fused, adam_off, t->n_params - adam_off, st);
-      if ((rc = adam_off == 0 ? t2_pack(t, st) : t2_pack(t, st, 0, 1))) return rc;
-      DH_LAUNCH_CHECK();
-    }
+    if ((rc = sched.tail())) return rc;   // fused: what the side stream has not updated -- the stem (all of the arena without a side stream)
   }
   t->bwd_done = true;
   return DH_OK;

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void bn2_stats_kernel(const bf16_t* __restrict
   }
 }
 
-// (mean / variance / coefficients from the partial rows: bn_stat_finalize_onepass_kernel, train.inc)
+// (mean / variance / coefficients from the partial rows: bn_stat_finalize_onepass_kernel, train_core_kernels.inc)
 // eval mode: scale / shift from the running statistics
 __global__ void bn2_eval_coef_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float* scale,
                                      float* shift, int C) {
@@ -707,7 +707,7 @@ __global__ __launch_bounds__(256) void avgpool_fc_dgrad2_kernel(const float* __r
 }
 // ---- stem weight gradient on the bf16 matrix pipe (round 3) ----
 // dW[co][e] = sum_px dZ[px][co] * x[b, c, 2oy+kh-3, 2ox+kw-3], e = (c*7+kh)*7+kw (147, padded to 160 = 5 column tiles), as stem_wgrad_kernel
-// (train.inc) does it on the float32 MFMA: K = output pixels, 2 per `32x32x2_f32` there, 16 per `v_mfma_f32_32x32x16_bf16` here (the
+// (train_kernels.inc) does it on the float32 MFMA: K = output pixels, 2 per `32x32x2_f32` there, 16 per `v_mfma_f32_32x32x16_bf16` here (the
 // matrix work of a 64 x 224^2 step drops from 105 us to 7 us; what remains is the row staging).  Per output row the 21 input-row
 // segments (bf16, the rounding the forward stem applies to x as well) and the dZ row sit in LDS in their natural order; a lane's
 // fragment is 8 consecutive pixels of ONE dZ channel (stride 128 B) or of ONE (c, kh, kw) column of x (stride 4 B): eight 2-byte LDS

@@ -1,32 +1,10 @@
 // train_core.inc -- what the float32 engine (train.inc, dh_train) and the bf16 engine (train2.inc, dh_train2) share on the host:
-// the parameter store (arenas, slot maps, allocations), the Adam launch, the gradient buckets of the data-parallel exchange and the
-// side stream's hand-off.  Included in resnet_kernels.hip in front of train.inc.  The engines differ in their kernels and in the ORDER
-// of their arenas (float32: forward order, bf16: backward-completion order); nothing here depends on that order.
-namespace {
-
-__global__ void fill_kernel(float* p, int64_t n, float v) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
-}
-
-// Adam (torch.optim.Adam defaults, no weight decay, no amsgrad) over one flat parameter arena
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2,
-                                                   float eps, float bc1, float bc2_sqrt) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i];
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - (lr / bc1) * (mi / denom);
-  }
-}
-
-inline int grid_for(int64_t n, int per = 256, int cap = 256 * 16) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, cap));
-}
-
-}  // namespace
+// the parameter store (arenas, slot maps, allocations), the Adam launch, the gradient buckets of the data-parallel exchange, the
+// side stream's hand-off, the record of one convolution with what is derived from it (slots, BN buffers, map sizes, pack table, stem
+// slab split) and the scheduler of a backward pass (BwdSched: every cross-stream ordering rule of a training step).  Included in
+// resnet_kernels.hip behind train_core_kernels.inc (the kernels both engines launch) and in front of train.inc.  The engines differ in
+// their kernels and in the ORDER of their arenas (float32: forward order, bf16: backward-completion order); nothing here depends on
+// that order.
 
 // A plain struct: it owns nothing by itself (no destructor); the engine that holds it calls store_free_all.  A test hook may fill
 // one on the stack with borrowed pointers.
@@ -185,6 +163,190 @@ int side_join(TrainStore& s, hipStream_t st) {
   DH_HIP(hipEventRecord(s.ev_join, s.side));
   DH_HIP(hipStreamWaitEvent(st, s.ev_join, 0));
   return DH_OK;
+}
+
+}  // namespace
+
+// ---- one convolution of a training engine ---------------------------------------------------------------------------------------
+// The description (net_desc.inc) plus the engine's buffers; E = the element type of its activations (float / bf16_t).
+template <typename E> struct TrainConvT : ConvDesc {
+  int Hi = 0, Wi = 0, Ho = 0, Wo = 0;   // input / output map of the current batch shape (conv_shapes)
+  void* wp_f = nullptr;   // packed forward operand, in E (the stem: its own layout; float32 1x1: unused, the GEMM reads the master tensor)
+  void* wp_d = nullptr;   // packed data-gradient operand, in E; not for the stem
+  E* Z = nullptr;         // conv output (pre-BN), NHWC
+  E* Y = nullptr;         // BN (+identity) (+ReLU) output, NHWC
+  E* dZ = nullptr;        // with a side stream: this conv's own dZ (the side stream's weight-gradient kernels read it long after it was written)
+  BnBufs bnb{};
+};
+typedef TrainConvT<float> TrainConv;
+
+namespace {
+
+template <typename C> void convs_from_desc(std::vector<C>& convs, const NetDesc& d) {
+  for (const ConvDesc& cd : d.convs) { convs.emplace_back(); static_cast<ConvDesc&>(convs.back()) = cd; }
+}
+
+// the five slots of a conv at the running ends of the arenas.  The order of the calls IS the arena order, inside a conv too: the float32
+// engine (forward order) puts the conv weight first, the bf16 engine (backward-completion order) last.
+void store_add_conv(TrainStore& s, const ConvDesc& c, bool weight_first) {
+  const int64_t nw = (int64_t)c.cout * c.cin * c.ks * c.ks;
+  if (weight_first) store_add(s, c.name + ".weight", nw);
+  store_add(s, c.bn + ".weight", c.cout); store_add(s, c.bn + ".bias", c.cout);
+  if (!weight_first) store_add(s, c.name + ".weight", nw);
+  store_radd(s, c.bn + ".running_mean", c.cout); store_radd(s, c.bn + ".running_var", c.cout);
+}
+
+int store_alloc_bn(TrainStore& s, BnBufs& b, int C) {
+  for (float** q : {&b.mean, &b.invstd, &b.scale, &b.shift, &b.k0, &b.k1, &b.k2})
+    if (int rc = store_alloc(s, q, C)) return rc;
+  return DH_OK;
+}
+
+// The map sizes of patch size P: every conv gets Hi / Ho, then `setup(conv, index, top)` runs (the engine's allocations; top: the last
+// conv of a block), in forward order: the stem, then block by block its convs and its downsample conv.
+template <typename C, typename Setup>
+int conv_shapes(std::vector<C>& convs, const std::vector<BlockDesc>& blocks, int P, Setup setup) {
+  auto place = [&](int i, int hi, bool top) -> int {
+    C& c = convs[i];
+    c.Hi = c.Wi = hi;
+    c.Ho = c.Wo = (hi + 2 * (c.ks / 2) - c.ks) / c.stride + 1;
+    return setup(c, i, top);
+  };
+  int rc = place(0, P, false);
+  if (rc) return rc;
+  int H = (convs[0].Ho + 2 - 3) / 2 + 1;   // behind the 3x3/2 maxpool
+  for (const BlockDesc& b : blocks) {
+    int h = H;
+    for (int i = 0; i < b.nconv; ++i) {
+      if ((rc = place(b.conv[i], h, i + 1 == b.nconv))) return rc;
+      h = convs[b.conv[i]].Ho;
+    }
+    if (b.ds >= 0 && (rc = place(b.ds, H, false))) return rc;
+    H = h;
+  }
+  return DH_OK;
+}
+
+// The descriptor table of an engine's pack-everything kernel: one Desc (with a field blk0 = its first workgroup) per packed conv, in
+// conv order.  `add` them all, `upload` once (the descriptors hold device addresses that stay put for the life of the engine), then
+// `range(j0, j1)` is the launch over descriptors [j0, j1): grid, first descriptor, count, blk0 of the first.
+template <typename Desc> struct PackTable {
+  Desc* dev = nullptr;
+  std::vector<Desc> host;   // until upload
+  std::vector<int> blk0;    // first workgroup of every descriptor (+ the total)
+  int blocks = 0;
+  void add(Desc d, int n_blocks) { d.blk0 = blocks; blk0.push_back(blocks); host.push_back(d); blocks += n_blocks; }
+  int upload(TrainStore& s) {
+    DH_HIP(hipMalloc(reinterpret_cast<void**>(&dev), host.size() * sizeof(Desc)));
+    s.allocs.push_back(dev);   // freed with the engine (not with the batch-shape buffers)
+    DH_HIP(hipMemcpy(dev, host.data(), host.size() * sizeof(Desc), hipMemcpyHostToDevice));
+    blk0.push_back(blocks);
+    host.clear();
+    return DH_OK;
+  }
+  struct Launch { int grid; const Desc* first; int count, blk_base; };
+  Launch range(int j0, int j1) const { return {blk0[j1] - blk0[j0], dev + j0, j1 - j0, blk0[j0]}; }
+};
+
+// The stem's weight gradient: at most STEM_WGRAD_SLABS runs of `rows_per_slab` output rows (b, oy), one workgroup of the engine's kernel
+// and one 64 x 160 slab each, then the fixed-order sum of the slabs into dw [64][3][7][7].
+struct StemSlabs { int rows_per_slab, n_slabs; };
+StemSlabs stem_wgrad_split(int B, int Ho) {
+  const int total_rows = B * Ho;
+  const int rpb = (total_rows + STEM_WGRAD_SLABS - 1) / STEM_WGRAD_SLABS;
+  return {rpb, (total_rows + rpb - 1) / rpb};
+}
+int stem_wgrad_reduce(const float* slabs, int n_slabs, float* dw, hipStream_t st) {
+  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((64 * 147 + 31) / 32), dim3(256), 0, st, slabs, n_slabs, dw);
+  DH_LAUNCH_CHECK();
+  return DH_OK;
+}
+
+// the element range of the completion items [i0, i1): consecutive items are contiguous in the arena (ascending for the bf16 engine,
+// descending for the float32 engine), so their union is one range; count 0 when they are not (or the interval is empty)
+TrainStore::Range store_item_range(const TrainStore& s, size_t i0, size_t i1) {
+  if (i0 >= i1 || i1 > s.items.size()) return {0, 0};
+  int64_t lo = s.items[i0].first, hi = lo, sum = 0;
+  for (size_t i = i0; i < i1; ++i) {
+    lo = std::min(lo, s.items[i].first); hi = std::max(hi, s.items[i].first + s.items[i].second);
+    sum += s.items[i].second;
+  }
+  return {lo, sum == hi - lo ? sum : 0};
+}
+
+// ---- the scheduler of a backward pass --------------------------------------------------------------------------------------------
+// Which stream a weight gradient runs on, and what orders the two streams: the ONE copy of the rules both engines' passes follow.
+// Without a side stream (s.side null) a weight gradient is launched on the main stream where it is queued and flush / join do nothing.
+// With one, every convolution owns its dZ buffer (HBM is plentiful), so the main stream never waits for the side stream inside the pass;
+// queued weight gradients are handed over in groups behind ONE event of the main stream (an event record or wait stalls the recording
+// queue for about 6 us: one hand-off per convolution cost 0.67 ms of a 7.7 ms ResNet-50 step, profiles/r03_exp_side_handoff.txt).
+//   queue   a conv's weight gradient (conv index, its input x, its dZ)
+//   flush   one side_handoff, the queued gradients in queue order on the side stream; in a fused pass then the Adam update of the
+//           completion items that are complete once the side stream gets there, and the repack of the flushed convs [lo, hi]
+//   join    flush + side_join: everything handed over so far precedes what the main stream does next.  A gradient bucket's gradients,
+//           the side stream's included, must precede the callback that fires it (store_mark_done): the engine joins before it marks
+//           such an item done.  The optimiser after the pass needs one too.
+//   tail    after the last item is marked done (and a join): in a fused pass Adam over what the side stream has not updated and the
+//           repack of those convs, on the main stream -- the stem; the whole arena without a side stream
+// `fused` (single-rank training): the Adam update and the repack of a group's tensors follow that group's weight gradients on the side
+// stream, instead of one update of the whole arena after the pass (same arithmetic per element: identical parameters).  The cursor of
+// that update counts COMPLETION ITEMS: items [0, cursor) are updated.  `completes` (flush, join) = how many items beyond those already
+// marked done the queued gradients complete (float32 flushes a block before it marks it: 1; bf16 after: 0).
+// The engine supplies  wgrad(conv, x, dz, stream)  and  repack(lo, hi, stream)  (convs lo .. hi inclusive; conv 0 is the stem).
+// no_adam / no_side_repack: the timing-only ablations of diagnostic builds (DH_T1_ABL / DH_T2_ABL), false in the shipped library.
+template <typename E, typename Wgrad, typename Repack> struct BwdSched {
+  TrainStore& s;
+  hipStream_t st;          // the main stream of the pass
+  const AdamArgs* fused;   // null: no optimiser in the pass
+  int n_convs;
+  Wgrad wgrad;
+  Repack repack;
+  bool no_adam, no_side_repack;
+  struct Pending { int conv; const E* x; const E* dz; };
+  std::vector<Pending> pending;
+  size_t cursor = 0;
+
+  int queue(int conv, const E* x, const E* dz) {
+    if (!s.side) return wgrad(conv, x, dz, st);
+    pending.push_back({conv, x, dz});
+    return DH_OK;
+  }
+  int flush(size_t completes) {
+    if (pending.empty()) return DH_OK;
+    int rc = side_handoff(s, st);
+    if (rc) return rc;
+    int lo = n_convs, hi = -1;
+    for (const Pending& w : pending) {
+      if ((rc = wgrad(w.conv, w.x, w.dz, s.side))) return rc;
+      lo = std::min(lo, w.conv); hi = std::max(hi, w.conv);
+    }
+    if (fused) {
+      const size_t upto = s.items_done + completes;
+      const TrainStore::Range r = store_item_range(s, cursor, upto);
+      DH_REQUIRE(hi - lo + 1 == (int)pending.size() && r.second > 0, "backward: the convolutions of a hand-off are not a contiguous range");
+      if (!no_adam) adam_range(s, *fused, r.first, r.second, s.side);
+      cursor = upto;
+      if (!no_side_repack && (rc = repack(lo, hi, s.side))) return rc;
+    }
+    pending.clear();
+    return DH_OK;
+  }
+  int join(size_t completes) {
+    if (!s.side) return DH_OK;
+    const int rc = flush(completes);
+    return rc ? rc : side_join(s, st);
+  }
+  int tail() {
+    if (!fused) return DH_OK;
+    const TrainStore::Range r = store_item_range(s, cursor, s.items.size());
+    if (!no_adam) adam_range(s, *fused, r.first, r.second, st);
+    return repack(0, cursor == 0 ? n_convs - 1 : 0, st);
+  }
+};
+template <typename E, typename Wgrad, typename Repack>
+BwdSched<E, Wgrad, Repack> bwd_sched(TrainStore& s, hipStream_t st, const AdamArgs* fused, int n_convs, Wgrad wgrad, Repack repack,
+                                     bool no_adam = false, bool no_side_repack = false) {
+  return {s, st, fused, n_convs, wgrad, repack, no_adam, no_side_repack, {}, 0};
 }
 
 }  // namespace

@@ -153,13 +153,13 @@ extern "C" int dh_resnet18_train_debug_act(dh_resnet18* net, const char* conv_na
   DH_REQUIRE(net && net->train && conv_name && out_dev && net->train->B > 0 && net->train->x_in, "train debug: bad arguments / no training forward");
   DH_REQUIRE(what >= 0 && what <= 3, "train debug: what = %d (0 Z, 1 Y, 2 dZ, 3 X1)", what);
   const dh_train* t = net->train;
-  for (size_t i = 0; i < net->convs.size(); ++i)
-    if (net->convs[i].name == conv_name) {
-      const TrainConv& tc = t->tc[i];
+  for (size_t i = 0; i < t->convs.size(); ++i)
+    if (t->convs[i].name == conv_name) {
+      const TrainConv& tc = t->convs[i];
       DH_REQUIRE(what != 3 || i == 0, "train debug: what = 3 (X1, the pooled block input) goes with 'conv1', not '%s'", conv_name);
       DH_REQUIRE(what != 1 || i != 0, "train debug: what = 1 (Y) of 'conv1' is not kept (the stem pools in its BN pass: what = 3)");
       const int H2 = (tc.Ho + 2 - 3) / 2 + 1;
-      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * tc.Ho * tc.Wo * net->convs[i].cout;
+      const int64_t n = what == 3 ? (int64_t)t->B * H2 * H2 * 64 : (int64_t)t->B * tc.Ho * tc.Wo * tc.cout;
       DH_REQUIRE(n == n_elem, "train debug: n_elem = %lld, '%s' (what = %d) has %lld elements", (long long)n_elem, conv_name, what, (long long)n);
       if (what == 2) {
         DH_REQUIRE(t->side != nullptr, "train debug: what = 2 (dZ) needs the per-convolution dZ buffers of the side-stream engine (created with DH_T1_SIDE=0)");
@@ -246,10 +246,10 @@ extern "C" int dh_debug_wgrad_f32(const float* dz_dev, const float* x_dev, float
   float* slabs;
   int rc = sc.get(&slabs, (int64_t)WGRAD3_WGS * 9 * 64 * 64);
   if (rc) return rc;
-  ConvLayer c{{"dbg", "dbg", cin, cout, ks, stride}};
-  TrainConv tc;
-  tc.Hi = Hi; tc.Wi = Wi; tc.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; tc.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
-  if ((rc = tr_wgrad(slabs, dw_dev, c, tc, x_dev, dz_dev, B, st, mode == 1))) return rc;
+  TrainConv c;
+  c.name = c.bn = "dbg"; c.cin = cin; c.cout = cout; c.ks = ks; c.stride = stride;
+  c.Hi = Hi; c.Wi = Wi; c.Ho = (Hi + 2 * (ks / 2) - ks) / stride + 1; c.Wo = (Wi + 2 * (ks / 2) - ks) / stride + 1;
+  if ((rc = tr_wgrad(slabs, dw_dev, c, x_dev, dz_dev, B, st, mode == 1))) return rc;
   return dbg_finish(st, "debug wgrad");
 }
 

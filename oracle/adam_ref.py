@@ -1,4 +1,4 @@
-"""float64 reference of the engines' Adam step (adam_kernel, csrc/train.inc) and the element-wise gate its parameters are held to
+"""float64 reference of the engines' Adam step (adam_kernel, csrc/train_core_kernels.inc) and the element-wise gate its parameters are held to
 (tests/test_gpu_adam.py; the reference and the gate are checked by tests/test_adam_ref_host.py).
 
 The kernel, per element, all in float32 with -ffp-contract=off (a contracted multiply-add would only drop roundings):

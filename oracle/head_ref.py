@@ -4,7 +4,7 @@ fc forward, fc weight / bias gradient, average-pool + fc data gradient), the cro
 
 Gates follow oracle/layer_ref.py: |got - want| <= gamma(K) A (+ one unit of the storage format where the result is stored narrower than
 float32), want = the float64 value of the same expression on the same operands, K = the float32 roundings any term passes on its way
-into the stored value, A = the sum of the magnitudes of the terms.  K and A are read from the kernels (csrc/train.inc, train2_kernels.inc):
+into the stored value, A = the sum of the magnitudes of the terms.  K and A are read from the kernels (csrc/train_core_kernels.inc, train_kernels.inc, train2_kernels.inc):
 
   pooled[b][c] = (sum_q x[b][q][c]) / HW       HW - 1 additions + the division                      K = HW        A = mean_q |x|
   logits[b][k] = sum_c pooled w + bias          per lane C / 64 multiply-adds (one rounding each), 6 butterfly additions, + bias:

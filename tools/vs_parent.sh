@@ -5,6 +5,7 @@
 # default selection: every such test --
 #   tests/test_gpu_conv3_vs_parent.py                          every launch path of the 3x3 convolutions
 #   tests/test_gpu_conv_mfma_shape.py -k parent_library        DH_CONV_MFMA16=0 on the shapes of tests/helpers/conv_mfma_shapes.py
+#   tests/test_gpu_train_vs_parent.py                          training steps of the three engines, side stream on and off (tests/helpers/train_paths.py)
 set -e -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 PARENT=HEAD~1
@@ -15,5 +16,5 @@ if [ -z "$DH_PARENT_LIB" ]; then
   (cd $T/parent && python3 -m deephisto_amd.build > $T/build.log 2>&1) || { tail -20 $T/build.log; exit 1; }
   export DH_PARENT_LIB=$T/parent/deephisto_amd/libdeephisto_hip.so
 fi
-if [ $# -eq 0 ]; then set -- tests/test_gpu_conv3_vs_parent.py tests/test_gpu_conv_mfma_shape.py -k parent_library; fi
+if [ $# -eq 0 ]; then set -- tests/test_gpu_conv3_vs_parent.py tests/test_gpu_train_vs_parent.py tests/test_gpu_conv_mfma_shape.py -k parent_library; fi
 timeout -k 10 900 python3 -m pytest "$@" -q -rs
